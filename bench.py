@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — self-play throughput of the MI355X engine on BASELINE.json's metric.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     N > 1 runs one process per GPU either way:
       * under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...):
         RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment;
@@ -19,9 +19,14 @@ Scaling  : weak — every rank plays its own GAMES_PER_STEP games per step (game
            data path). Timed region = barrier + device sync on both sides, max over ranks.
 Roofline : the fused kernel's achieved rate against both roofs — f32 MFMA (60,288 FLOP per leaf evaluation,
            SURVEY.md §8d) and HBM (event-counted algorithmic bytes, formula of SURVEY.md §8d) — the nearer roof is
-           reported as "roofline", the other under "roofline_other". Kernel time = HIP events on the engine's stream.
+           reported as "roofline", the other under "roofline_other". Kernel time = HIP events on the engine's stream. Event
+           counts: an instrumented re-run of one game per tree slot of the last timed step, scaled to the step.
 CPU side : the oracle (restated reference CPU path, thread-per-worker with PolicyWithCache like gather_experience)
            timed on this box's host cores on a bounded sample of the same workload — rank 0, N = 1 only.
+Extras   : the CPU baseline and the side legs (f16x2 and conv networks, trained weights, PolicyWithCache, launch tail, 4096
+           concurrent games, learner, ...) run only with --extras. Without it a run is the warm-up, the timed steps, the counted
+           re-run and the learning-loop record, so that its length follows --steps and --warmup.
+Outputs  : --dump-outputs DIR writes what the last timed step returned (the plies of each of rank 0's games) as DIR/plies.npy.
 """
 import argparse
 import json
@@ -169,6 +174,24 @@ def cpu_baseline_single_thread(blob, explores, games=16):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """--dump-outputs: every array as DIR/<name>.npy in float32. The arrays share their first axis (one row per game); if they would
+    exceed DUMP_LIMIT_BYTES, the same fixed, seeded sample of rows is written from each, and the row numbers as sample_rows.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(4 * int(np.prod(a.shape[1:])) for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)   # (room for the .npy headers)
+    rows = None
+    if n * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(seed).choice(n, budget // (row_bytes + 8), replace=False))
+        np.save(os.path.join(dirname, "sample_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), (a if rows is None else a[rows]).astype(np.float32))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N ranks (one process per GPU, RANK = LOCAL_RANK = 0..N-1) as
     children of this process, which has not touched the GPU and will not. Returns the worst exit status."""
@@ -211,20 +234,24 @@ def main():
                     help="concurrent games (tree slots) per GPU: 768 per CU = 12 waves of 64 trees, what the headline launch plays on "
                          "(rounds 1-5 created 262,144 slots and played on 196,608 of them); BASELINE configs[1] names 4096, reported as extra")
     ap.add_argument("--games-per-step", type=int, default=2097152, help="self-play games per GPU per step (10.7 per tree slot at the default engine size)")
-    ap.add_argument("--no-4096", action="store_true", help="skip the extra 4096-concurrent-games measurement")
+    ap.add_argument("--no-4096", action="store_true", help="with --extras: skip the extra 4096-concurrent-games measurement")
     ap.add_argument("--explores", type=int, default=800)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --extras: skip the CPU baseline")
     ap.add_argument("--full-warmup", action="store_true", help="warm-up steps at full size (the kernel-trace pass: every launch of the "
                     "kernel then has the timed steps' duration, so the trace's per-kernel average is the step's)")
     ap.add_argument("--skip-counted", action="store_true", help="profiling passes: only the warm-up and timed launches, a reduced line")
     ap.add_argument("--no-learner-loop", action="store_true", help="skip the three iterations of the N-rank learning loop (learner_loop)")
-    ap.add_argument("--no-policy-cache", action="store_true", help="skip the extra PolicyWithCache measurement")
+    ap.add_argument("--no-policy-cache", action="store_true", help="with --extras: skip the extra PolicyWithCache measurement")
     ap.add_argument("--only-policy-cache", "--only-extra-legs", dest="only_policy_cache", action="store_true",
                     help="run nothing but the extra self-play legs (PolicyWithCache, reference configuration, trained network, conv network) "
                          "at their bench size: the command tools/collect_profiles.sh profiles for their rooflines")
-    ap.add_argument("--no-extras", action="store_true", help="skip the trained-weights / replay-output / reference-config / conv / tail / learner legs")
-    ap.add_argument("--time-budget-s", type=float, default=1500.0, help="wall-clock budget of the whole run: the extra legs (never the timed "
-                    "steps, the roofline or the CPU baseline) are skipped, least important first, once they would overrun it")
+    ap.add_argument("--extras", action="store_true", help="N = 1: also run, after the timed steps, the CPU baseline (the restated reference CPU "
+                    "path on this host's cores: BASELINE's comparison in the same run, ~20 s) and the extra legs (f16x2, trained weights, "
+                    "replay outputs, PolicyWithCache + reference configuration, conv network, launch tail, Policy::eval call, 4096 concurrent "
+                    "games, learner): minutes that --steps does not govern, so a default run leaves them out and lasts about "
+                    "(steps + warmup / 4) step times plus start-up")
+    ap.add_argument("--time-budget-s", type=float, default=1500.0, help="with --extras: wall-clock budget of the whole run; the extra legs (never the "
+                    "timed steps, the roofline or the CPU baseline) are skipped, least important first, once they would overrun it")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank) | gloo (dry run: every rank "
                                                            "on GPU 0, used to exercise the N>1 path on a 1-GPU box)")
     ap.add_argument("--cpu-sample-games", type=int, default=0, help="0 = 64 games per worker thread")
@@ -232,9 +259,16 @@ def main():
     ap.add_argument("--check-launch", action="store_true",
                     help="start the ranks, rendezvous, barrier and reduce exactly as a bench run does, print the rank "
                          "layout and stop before any GPU work (launch-plumbing test; prints no bench line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0's games) as "
+                         "DIR/<name>.npy in float32, so that two builds can be compared output for output on identical inputs")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.only_policy_cache:
+        raise SystemExit("--dump-outputs writes the timed steps' outputs: --only-policy-cache runs no timed steps")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))   # (the ranks inherit this process's stdout as it is)
     # ONE JSON line on stdout, whatever the libraries print: RCCL writes its version banner to stdout when a communicator is created
@@ -517,9 +551,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed, (plies,) = dist_util.reduce_scalars(dist, reduce_device, elapsed, [plies])
+    if args.dump_outputs and rank == 0:
+        # what selfplay(outputs=False) hands its caller: the plies of every game of the last timed step (game indices and seeds are
+        # fixed by the arguments, so the inputs are the same in every run)
+        dump_outputs(args.dump_outputs, {"plies": r["plies"]})
 
-    # Event counts of exactly the games of the last timed step (trajectories are deterministic, so an instrumented
-    # re-run outside the timed region gives the counts of the timed run).
+    # Event counts of the games of the last timed step: an instrumented re-run, outside the timed region, of its first `concurrent`
+    # games (one per tree slot; trajectories are deterministic, so these are the timed run's games), scaled to the step's games — the
+    # estimator of every extra leg. An instrumented run of the whole step would add a step's time that --steps does not govern.
     if args.skip_counted:
         # tools/collect_profiles.sh's counter passes only need the launches themselves: no instrumented re-run, no roofline objects
         if rank == 0:
@@ -533,9 +572,11 @@ def main():
             dist.barrier()
             dist.destroy_process_group()
         return
-    rc = step(args.warmup + args.steps - 1, counters=True)
-    c = rc["counters"]
-    shape, sgrid, sthreads = eng.last_launch_shape()
+    shape, sgrid, sthreads = eng.last_launch_shape()   # (of the last timed launch)
+    first, count = dist_util.step_game_range(args.warmup + args.steps - 1, rank, world, gps)
+    counted_games = min(count, args.concurrent)
+    c = eng.selfplay(cfg, base_seed=0, n_games=counted_games, first_game=first, outputs=False, counters=True)["counters"]
+    c = {k: v if k == "max_depth" else v * count / counted_games for k, v in c.items()}
     kernel_name = {1: "selfplay_kernel<WPS=1>", 2: "selfplay_kernel<WPS=2>", 3: "selfplay_kernel_quads",
                    4: "selfplay_kernel_lanes", 5: "selfplay_kernel_pc", 6: "selfplay_kernel_lanes2"}.get(shape, "?") + f" <<<{sgrid}, {sthreads}>>>"
     last_ms = kernel_ms[-1]
@@ -610,6 +651,7 @@ def main():
         for rf in (mfma, hbm):
             rf["traffic"] = traffic            # HBM bytes per launch (FETCH_SIZE x2 + WRITE_SIZE, guide §HBM), PMC passes
             rf["traffic_source"] = src         # the committed rocprofv3 run of this configuration and these kernel sources
+            rf["event_counts"] = f"instrumented re-run of {counted_games} of the step's {count} games, scaled to the step"
         hbm["algorithmic_bytes_per_launch"] = algorithmic_bytes(c)
         near, other = (mfma, hbm) if mfma["frac"] >= hbm["frac"] else (hbm, mfma)
         out = {
@@ -635,7 +677,7 @@ def main():
         #      trained-network and policy-cache legs) on the headline concurrency, so that the whole list fits beside the driver's
         #      K = 20 / W = 5 run (20 full + 5 quarter launches + the counted re-run = ~670 s of an ~870 s budget); a leg is skipped —
         #      and named — only if it would still overrun --time-budget-s. A shorter launch carries a larger share of tail (tree
-        #      slots emptying at its end: ~5 % at a full step, ~9 % at half, ~15 % at a quarter). The CPU baseline always runs.
+        #      slots emptying at its end: ~5 % at a full step, ~9 % at half, ~15 % at a quarter). With --extras the CPU baseline always runs.
         t_step = elapsed / args.steps
         t_q = t_step * gx / gps          # a quarter launch of the headline configuration
         skipped = []
@@ -646,7 +688,8 @@ def main():
                 skipped.append(name)
             return ok
 
-        if world == 1 and not args.no_cpu_baseline:
+        extras = world == 1 and args.extras
+        if extras and not args.no_cpu_baseline:
             budget, quota = host_cpu_budget()
             # two worker threads per usable CPU (measured best on the 16-CPU-quota boxes: 16 -> 103, 32 -> 130 games/s)
             threads = args.cpu_threads or min(os.cpu_count() or 1, 2 * budget)
@@ -658,7 +701,6 @@ def main():
             except Exception as ex:  # noqa: BLE001
                 out["cpu_baseline"]["single_thread"] = {"error": str(ex)[:200]}
         next_first = (args.warmup + args.steps) * gps   # game indices never reused by a later leg
-        extras = world == 1 and not args.no_extras
         if extras and fits("with_f16x2_network", 5.5 * t_q + 12):
             try:
                 out["with_f16x2_network"] = f16x2_leg(eng, gh, next_first)
@@ -691,9 +733,9 @@ def main():
                 del ro
             else:
                 out["with_replay_outputs_to_host"] = {"skipped": "not enough host memory for the 4.3 KB per game of outputs"}
-        if world == 1 and not args.no_policy_cache and fits("with_policy_cache+reference_selfplay_config", 5.0 * t_q + 40):
+        if extras and not args.no_policy_cache and fits("with_policy_cache+reference_selfplay_config", 5.0 * t_q + 40):
             # (a second engine beside the first: 2 x 60 GB of node pools + the 17 GB table fit the 288 GB of HBM)
-            out.update(policy_cache_leg(gh, trained_blob if extras else None, reference_mcts=extras))
+            out.update(policy_cache_leg(gh, trained_blob, reference_mcts=True))
         if extras and fits("with_conv_policy", 3.0 * t_q + 8):
             out["with_conv_policy"] = conv_leg(eng, gh, next_first)
             next_first += args.concurrent + gh
@@ -732,7 +774,7 @@ def main():
                                            "kernel, synchronisation; positions and results cross the host link in place (pinned, mapped memory)"}
             except Exception as ex:  # noqa: BLE001
                 out["policy_eval_call"] = {"error": str(ex)[:200]}
-        if world == 1 and not args.no_4096 and fits("at_4096_concurrent_games", 15):
+        if extras and not args.no_4096 and fits("at_4096_concurrent_games", 15):
             # BASELINE configs[1] names 4096 concurrent games: same engine code at 16 trees per CU (latency-optimised
             # kernel, weights in registers), one 16,384-game step, reported beside the headline configuration
             e2 = sa.Engine(concurrent_games=4096, max_explores=args.explores, device=local_rank)

@@ -383,6 +383,24 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus():
     assert r.returncode != 0 and b"WORLD_SIZE=2" in r.stderr
 
 
+def test_bench_dump_outputs_is_float32_within_64_mb_and_seeded(tmp_path):
+    """--dump-outputs: a step's plies go out whole as float32; a step too large for 64 MB goes out as the same seeded sample of
+    games in every run, with the games' row numbers beside it."""
+    import bench
+
+    small = np.random.default_rng(1).integers(7, 64, 1000).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"plies": small})
+    got = np.load(tmp_path / "a" / "plies.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small) and not (tmp_path / "a" / "sample_rows.npy").exists()
+    big = np.random.default_rng(2).integers(7, 64, 20_000_000).astype(np.int32)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"plies": big})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= 64 << 20
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "sample_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "plies.npy"), big[rows.astype(np.int64)])
+
+
 def test_bench_multi_rank_fails_loudly_without_gpus():
     """No GPU here: every rank of `bench.py --gpus 2` must refuse to run (there is no CPU fallback) and the launcher must
     exit non-zero without printing a bench line."""

@@ -199,6 +199,31 @@ def test_bench_two_ranks_on_one_gpu():
     assert 7 <= line["plies_per_game"] <= 63
 
 
+def test_bench_dumps_the_last_timed_steps_plies(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the LAST timed step's selfplay() returned: its plies equal a direct selfplay() of that
+    step's game range (warm-up steps come first in the game numbering) and not the previous step's."""
+    import synthesis_amd as sa
+    from bench import make_weights
+    from synthesis_amd.dist_util import step_game_range
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.check_output(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--concurrent", "4096",
+         "--games-per-step", "8192", "--explores", "100", "--no-learner-loop", "--dump-outputs", str(tmp_path)],
+        env=env, stderr=subprocess.DEVNULL, timeout=900).decode()
+    line = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["config"]["games_per_step_per_gpu"] == 8192
+    dumped = np.load(tmp_path / "plies.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (8192,)
+    eng = sa.Engine(concurrent_games=4096, max_explores=100, device=0)
+    eng.load_weights(make_weights())
+    cfg = sa.parity_rollout_config(100)
+    last, prev = (eng.selfplay(cfg, base_seed=0, n_games=n, first_game=f, outputs=False)["plies"]
+                  for f, n in (step_game_range(2, 0, 1, 8192), step_game_range(1, 0, 1, 8192)))
+    eng.close()
+    assert np.array_equal(dumped, last.astype(np.float32)) and not np.array_equal(dumped, prev.astype(np.float32))
+
+
 def test_rccl_process_group_at_world_size_1():
     """What of the N > 1 plumbing a one-GPU box can run over RCCL itself (backend "nccl"): bench.py's process group with a device id,
     barrier, the MAX / SUM reductions of dist_util.reduce_scalars on the device, an all-reduce of the learner's 30,492-float gradient

@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 # the kernel trace runs the full default line (with its roofline objects); the counter passes only need the launches
-TRACE="bench.py --steps 2 --warmup 1 --full-warmup --no-cpu-baseline --no-4096 --no-policy-cache --no-extras --no-learner-loop"
+TRACE="bench.py --steps 2 --warmup 1 --full-warmup --no-cpu-baseline --no-4096 --no-policy-cache --no-learner-loop"
 BENCH="bench.py --steps 1 --warmup 1 --skip-counted --no-learner-loop"
 CACHE="bench.py --only-extra-legs"
 run() {  # name, rocprof args..., -- program
