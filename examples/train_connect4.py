@@ -67,6 +67,8 @@ def main():
                     "(north_star's Conv2d over the bitplanes + Linear heads)")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"], help="arithmetic of the conv learner's gradient step: bf16 = bf16 "
                     "matrix cores with f32 accumulation, master weights and Adam (BASELINE configs[4]: \"bf16 conv\"; --net conv only)")
+    ap.add_argument("--network-arithmetic", default="f32", choices=["f32", "f16x2"], help="arithmetic self-play evaluates the network in: "
+                    "f16x2 = every operand a pair of f16 numbers on the f16 matrix cores (syn_set_network_arithmetic; --net mlp and conv)")
     ap.add_argument("--data-parallel", action="store_true", help="gradient all-reduce per optimiser step on every rank instead of "
                     "the learner on rank 0 + one weight broadcast per iteration")
     args = ap.parse_args()
@@ -98,7 +100,8 @@ def main():
     loop = learner = None
     if args.data_parallel:
         (eng.load_weights_conv if conv else eng.load_weights)(blob)
-        learner = DataParallelLearner(eng, blob, dist=dist, device=local_rank, net=args.net, **hyper)
+        learner = DataParallelLearner(eng, blob, dist=dist, device=local_rank, net=args.net, network_arithmetic=args.network_arithmetic,
+                                      **hyper)
         if args.precision != "f32":
             eng.trainer_set_precision(args.precision)
         # replay buffer: positions as bitboards + targets + the game each step came from
@@ -107,7 +110,8 @@ def main():
         games_played = 0
     else:
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
-                            precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler, **hyper)
+                            precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
+                            network_arithmetic=args.network_arithmetic, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -126,11 +126,13 @@ int syn_load_weights(syn_engine* h, const float* blob, size_t n_floats);
  * out[0..9], value = softmax(out[9..12]). The reference ships the layers but no such network, so the architecture is this
  * library's (oracle/nn.hpp Connect4ConvNet restates it). blob = conv.weight[16][2][3][3], conv.bias[16], head.weight[12][1008],
  * head.bias[12]; n_floats must be 12412. Replaces the engine's network: syn_policy_eval_batch*, syn_mcts_search and
- * syn_selfplay_run then evaluate this network (lane-per-tree kernels: max_explores <= 7280, else SYN_ERR_UNSUPPORTED);
- * syn_load_weights / syn_trainer_publish_weights switch back to Connect4Net. Empties the policy cache. */
+ * syn_selfplay_run then evaluate this network (lane-per-tree kernels: max_explores <= 7280, else SYN_ERR_UNSUPPORTED), in the
+ * engine's network arithmetic (an engine in SYN_NET_ARITH_F16X2 builds the network's f16x2 image first; a blob without an f16x2 plan
+ * is then refused and changes nothing); syn_load_weights / syn_trainer_publish_weights switch back to Connect4Net. Empties the
+ * policy cache. */
 int syn_load_weights_conv(syn_engine* h, const float* blob, size_t n_floats);
 
-/* The arithmetic Connect4Net is evaluated in. The reference's own is f32 (libtorch `y = x W^T + b`, study-connect4/src/policies.rs:
+/* The arithmetic the network (Connect4Net or Connect4ConvNet) is evaluated in. The reference's own is f32 (libtorch `y = x W^T + b`, study-connect4/src/policies.rs:
  * 28-44; slimnn/src/linear.rs:17-25 in its Rust-only form); both choices below compute that function and differ in rounding only.
  *   SYN_NET_ARITH_F32   (default) every product and sum in f32 on v_mfma_f32_16x16x4_f32, ascending input order, fused
  *                       multiply-add per term: bit for bit oracle/nn.hpp's ACC_FMA, within 1e-5 of slimnn's order.
@@ -140,15 +142,21 @@ int syn_load_weights_conv(syn_engine* h, const float* blob, size_t n_floats);
  *                       oracle/nn_f16x2.hpp (which restates the instruction's accumulation, identified on MI355X); as close to
  *                       an f64 evaluation as the f32 arithmetic is (profiles/r05_f16_split.txt: 1.0e-7 against 1.0e-7 on the
  *                       random-init network, 1.8e-4 against 2.3e-4 on logits of magnitude 258 of a trained one).
- * The choice holds for syn_policy_eval_batch*, syn_eval_ctx_*, syn_mcts_search and syn_selfplay_run until changed; it empties the
- * policy cache. F16X2 needs Connect4Net (not Connect4ConvNet: SYN_ERR_UNSUPPORTED), max_explores <= 7280 (lane-per-tree kernels) and
- * finite parameters. Results under the two arithmetics differ in the last bits of the logits, so searches may differ where two
+ *                       Connect4ConvNet: the conv layer's weights split the same way against its exact 0 / 1 inputs (w_hi.x +
+ *                       w_lo.x), the head as above on the conv tile's activations (csrc/conv_f16x2_tile.cuh states the definition;
+ *                       222 instead of 567 matrix instructions per 16 positions, each half the cycles of an f32 one; measured
+ *                       self-play at 800 explores: 1.65x the f32 conv network's games/s).
+ * The choice holds for syn_policy_eval_batch*, syn_eval_ctx_*, syn_mcts_search and syn_selfplay_run — and for parameters loaded or
+ * published later (syn_load_weights, syn_load_weights_conv, syn_trainer_publish_weights of either learner keep it) — until changed;
+ * either switch empties the policy cache. F16X2 needs max_explores <= 7280 (lane-per-tree kernels) and finite parameters whose scales
+ * fit the f32-safe window; a refused switch or load changes nothing. Results under the two arithmetics differ in the last bits of the logits, so searches may differ where two
  * moves are within rounding of each other — which is why the choice is the caller's and never made silently. */
 enum { SYN_NET_ARITH_F32 = 0, SYN_NET_ARITH_F16X2 = 1 };
 int syn_set_network_arithmetic(syn_engine* h, int arithmetic);
-/* The scales of the f16x2 plan of the engine's current Connect4Net (valid = 0 when there is none): layer l's inputs are multiplied
+/* The scales of the f16x2 plan of the engine's current network (valid = 0 when there is none): layer l's inputs are multiplied
  * by 2^activation_exp[l], its weights by 2^weight_exp[l]; bound[l] = the bound on layer l's outputs the next exponent was chosen
- * from; raw outputs = accumulators * 2^out_exp. arithmetic / plan may be NULL. */
+ * from; raw outputs = accumulators * 2^out_exp. Connect4Net: layers 0..4. Connect4ConvNet: layer 0 = the conv layer (its 0 / 1
+ * inputs unscaled: activation_exp[0] = 0), layer 1 = the head, entries 2..4 zero. arithmetic / plan may be NULL. */
 typedef struct syn_f16x2_plan {
     int valid;
     int activation_exp[5];
@@ -158,7 +166,8 @@ typedef struct syn_f16x2_plan {
 } syn_f16x2_plan;
 int syn_get_network_arithmetic(syn_engine* h, int* arithmetic, syn_f16x2_plan* plan);
 /* The same plan for a parameter blob without an engine (pure host code, no GPU needed): what syn_set_network_arithmetic would choose for
- * these parameters. SYN_OK with plan->valid = 0 when the blob has no plan (non-finite parameters). */
+ * these parameters; n_floats selects the network (30492: Connect4Net, 12412: Connect4ConvNet, else SYN_ERR_INVALID_ARGUMENT). SYN_OK
+ * with plan->valid = 0 when the blob has no plan (non-finite parameters). */
 int syn_f16x2_plan_of_blob(const float* blob, size_t n_floats, syn_f16x2_plan* plan);
 
 /* ---- leaf evaluation ------------------------------------------------------------------------------------------- */
@@ -357,7 +366,7 @@ int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const sy
 /* The same for Connect4ConvNet (syn_load_weights_conv's network and blob order, 12412 floats): the trainer then runs that
  * network through syn_train_step / syn_train_gradients_device + syn_train_apply_device / syn_train_set_data + syn_train_epoch
  * (minibatches of at most 32 positions, else SYN_ERR_UNSUPPORTED), syn_trainer_get_state copies 12412 floats per array, and
- * syn_trainer_publish_weights makes the trained conv network the engine's policy. f32, the arithmetic order of
+ * syn_trainer_publish_weights makes the trained conv network the engine's policy (in the engine's network arithmetic). f32, the arithmetic order of
  * oracle/train.hpp::ConvTrainer (checked against torch float64 goldens); an engine trains one network at a time. Like
  * syn_trainer_init, the first call on an engine runs a self-check (eight steps on a synthetic batch through the four-workgroup
  * epoch kernel and through the one-workgroup kernel, compared bit for bit) and thereby discards a data set uploaded before it. */
@@ -391,7 +400,9 @@ int syn_trainer_set_precision(syn_engine* h, int precision);
 /* Copies out parameters / Adam moments / last gradient (each may be NULL) and the optimiser step count. */
 int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads);
 /* Replaces: vs.save(model_{i+1}.ot) + the workers' vs.load (alpha_zero.rs:97,194): the trained parameters become the
- * engine's policy for syn_policy_eval_batch / syn_mcts_search / syn_selfplay_run. */
+ * engine's policy for syn_policy_eval_batch / syn_mcts_search / syn_selfplay_run, in the arithmetic the engine is in (both learners:
+ * an engine in SYN_NET_ARITH_F16X2 gets the published network's f16x2 image). Before this library's Connect4ConvNet f16x2 support,
+ * the conv learner's publish reset an f16x2 engine to SYN_NET_ARITH_F32; it no longer does. */
 int syn_trainer_publish_weights(syn_engine* h);
 /* Epochs without the host in the loop. syn_train_set_data uploads the de-duplicated buffer once per iteration (the
  * tensors `states / target_pis / target_vs` of alpha_zero.rs:52-58, positions as bitboards); syn_train_epoch then runs

@@ -29,6 +29,7 @@
 #include "train_mfma.cuh"
 #include "train_epoch.cuh"
 #include "convnet.cuh"
+#include "conv_f16x2_tile.cuh"
 #include "layer_kernels.cuh"
 #include "train_conv.cuh"
 #include "train_conv_mfma.cuh"
@@ -84,6 +85,7 @@ SYN_LANES_GEN_LIST(SYN_X)
 SYN_LANES_REF_LIST(SYN_X)
 SYN_LANES_F16_LIST(SYN_X)
 SYN_LANES_F16_GEN_LIST(SYN_X)
+SYN_LANES_CONV_F16_LIST(SYN_X)
 #undef SYN_X
 // ... and (DEBUG_SHAPES=1 builds only) the pool kernels (pool_kernel.cuh) in engine_pool.hip / engine_pool_f16.hip
 #ifdef SYN_DEBUG_SHAPES
@@ -142,8 +144,9 @@ struct syn_engine {
     uint4* d_edge = nullptr;
     float* d_wimg = nullptr;
     int net_kind = 0;  // which network d_wimg holds: 0 = Connect4Net (mlp.cuh), 1 = Connect4ConvNet (convnet.cuh)
-    // Connect4Net in the f16x2 arithmetic (f16x2_tile.cuh; syn_set_network_arithmetic): its image, the parameters it is built from
-    // (host copy, refreshed by syn_load_weights / syn_trainer_publish_weights) and whether the image is current
+    // The network in the f16x2 arithmetic (syn_set_network_arithmetic; Connect4Net: f16x2_tile.cuh, Connect4ConvNet:
+    // conv_f16x2_tile.cuh): its image, the parameters it is built from (host copy of the current network's blob, refreshed by
+    // syn_load_weights* / syn_trainer_publish_weights) and whether the image is current
     int net_arith = SYN_NET_ARITH_F32;
     uint32_t* d_wimg16 = nullptr;
     std::vector<float> host_blob;
@@ -173,7 +176,7 @@ struct syn_engine {
     // scratch for host-pointer entry points
     void* d_scratch = nullptr;
     size_t scratch_bytes = 0;
-    std::atomic<bool> eval_attr_set[5] = {{false}, {false}, {false}, {false}, {false}};   // launch_policy_eval: the kernels' LDS attribute is set
+    std::atomic<bool> eval_attr_set[6] = {{false}, {false}, {false}, {false}, {false}, {false}};   // launch_policy_eval: the kernels' LDS attribute is set
     size_t eval_poll_max = 1024;       // contexts: batches up to this size signal completion through pinned memory (SYN_DEBUG=1 SYN_EVAL_POLL_MAX)
     size_t eval_zero_copy_out = 4096;  // contexts: results of up to this many positions are written into the pinned buffer by the kernel itself
     struct syn_eval_ctx* eval_ctx = nullptr;   // syn_policy_eval_batch's own evaluation context (created on first use)
@@ -469,7 +472,7 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
         const bool needs_noise2 = P.mcts.fpu == 2 || P.mcts.noise == 2;
         if (const char* ev = debug_env("SYN_LANES2")) nw2 = std::atoi(ev);
         if (PROF) nw2 = 0;
-        if ((nw2 == 8 || nw2 == 12) && h->cap <= LANE_MAX_CAP) {
+        if ((nw2 == 8 || nw2 == 12) && h->cap <= LANE_MAX_CAP && !(h->net_kind == 1 && h->net_arith == SYN_NET_ARITH_F16X2)) {
             (void)needs_noise2;
             const int per_wg = 128 * nw2;
             const int lgrid = (want_slots + per_wg - 1) / per_wg;
@@ -608,6 +611,8 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
         const bool conv = h->net_kind == 1;
         // Connect4Net in the f16x2 arithmetic (f16x2_tile.cuh) is evaluated by the lane-per-tree kernels only, at every size
         const bool f16x2 = !conv && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
+        // ... and Connect4ConvNet in it (conv_f16x2_tile.cuh, POLICY 4)
+        const bool conv16 = conv && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
         if (f16x2) {
             if (h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
             if (debug_env("SYN_LANES") == nullptr || !(nw == 4 || nw == 8 || nw == 12 || nw == 16))
@@ -615,7 +620,15 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
         }
         if (conv) {
             if (h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
-            nw = want_slots > h->num_cus * 512 ? 16 : (want_slots > h->num_cus * 256 ? 8 : 4);
+            if (conv16) {
+                // the f16x2 tile ships where its instantiations keep their registers (profiles/r07_conv_f16x2_resource_usage.txt): the
+                // parity family at 4 and 8 waves (at most 512 trees per CU), the runtime-switched configurations at 4 (at most 256)
+                const bool forced = debug_env("SYN_LANES") != nullptr && (nw == 4 || nw == 8);
+                if (!forced) nw = want_slots > h->num_cus * 256 ? 8 : 4;
+                if (!fast) nw = 4;
+                if (want_slots > h->num_cus * 64 * nw) want_slots = h->num_cus * 64 * nw;
+            } else
+                nw = want_slots > h->num_cus * 512 ? 16 : (want_slots > h->num_cus * 256 ? 8 : 4);
         }
         // The runtime-switched (general) instantiations need 300-450 more registers than the 128 of a 16-wave workgroup and are
         // bound by their own scratch traffic there (PMC: 8.8x the algorithmic bytes; Fpu::ParentQ 29.5k games/s against 42.4k,
@@ -688,6 +701,14 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
         if (e != hipSuccess) return e;                                                                             \
         hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
     }
+#define SYN_LAUNCH_LC16(NW, FAST)                                                                                  \
+    {                                                                                                              \
+        auto k = selfplay_kernel_lanes<MODE, COUNT, FAST, NW, false, 4>;                                           \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
+        if (e != hipSuccess) return e;                                                                             \
+        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
+    }
             // the reference's own self-play configuration (Fpu::Func folded at compile time: mcts.cuh cfg_family) has instantiations of
             // its own at 8 and 16 waves
             const bool ref_family = !conv && (!PROF || (MODE == MODE_SELFPLAY && !COUNT)) && cfg_family(P.mcts) == 2 && (nw == 8 || nw == 12 || nw == 16);
@@ -717,6 +738,11 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
             if (ref_family) {
                 if (nw == 8) SYN_LAUNCH_LR(8) else if (nw == 12) SYN_LAUNCH_LR(12) else SYN_LAUNCH_LR(16)
             } else
+            if (conv16) {
+                if (nw == 8 && fast) SYN_LAUNCH_LC16(8, true)
+                else if (fast) SYN_LAUNCH_LC16(4, true)
+                else SYN_LAUNCH_LC16(4, false)
+            } else
             if (conv) {
                 if (nw == 4) { if (fast) SYN_LAUNCH_LC(4, true) else SYN_LAUNCH_LC(4, false) }
                 else if (nw == 8) { if (fast) SYN_LAUNCH_LC(8, true) else SYN_LAUNCH_LC(8, false) }
@@ -728,6 +754,7 @@ static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, 
             else { if (fast) SYN_LAUNCH_L(16, true) else SYN_LAUNCH_L(16, false) }
 #undef SYN_LAUNCH_L
 #undef SYN_LAUNCH_LC
+#undef SYN_LAUNCH_LC16
 #undef SYN_LAUNCH_LR
             h->last_shape = 4; h->last_grid = lgrid; h->last_threads = 64 * nw;
             if (out_grid) *out_grid = -lgrid;  // negative: lane kernel (profile layout differs)
@@ -949,12 +976,47 @@ int syn_engine_destroy(syn_engine* h) {
 // The f16x2 image of the engine's Connect4Net (f16x2_tile.cuh: build_f16x2_image). State is committed only after the image exists:
 // a blob without an f16x2 plan (non-finite values, scales outside the window) leaves the engine exactly as it was — arithmetic,
 // parameters, both images and the policy cache — so nothing can evaluate a stale or missing image afterwards.
-static int upload_f16x2_image(syn_engine* h, const F16Image& im) {
+// (Connect4ConvNet's image, conv_f16x2_tile.cuh, lives in the same buffer: it is the smaller of the two)
+static int upload_f16x2_image(syn_engine* h, const std::vector<uint32_t>& words) {
     HIP_TRY(h, hipSetDevice(h->device));   // (reached through common_params before the entry point's own hipSetDevice)
     if (!h->d_wimg16) HIP_TRY(h, hipMalloc(&h->d_wimg16, (size_t)F16Geom::IMG_WORDS * 4));
-    HIP_TRY(h, hipMemcpyAsync(h->d_wimg16, im.words.data(), (size_t)F16Geom::IMG_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_wimg16, words.data(), words.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
+}
+// the f16x2 image of a blob of network `kind` (0 = Connect4Net, 1 = Connect4ConvNet); false = the blob has no f16x2 plan
+static bool build_f16x2_words(int kind, const float* blob, std::vector<uint32_t>& words) {
+    if (kind == 1) {
+        ConvF16Image im;
+        if (!build_conv_f16x2_image(blob, im)) return false;
+        words.swap(im.words);
+        return true;
+    }
+    F16Image im;
+    if (!build_f16x2_image(blob, im)) return false;
+    words.swap(im.words);
+    return true;
+}
+// the plan of a blob, selected by its size (30,492 floats: Connect4Net, five layers; 12,412: Connect4ConvNet, layer 0 = the conv
+// layer whose inputs enter unscaled, layer 1 = the head, entries 2..4 zero); plan->valid = 0 when it has none
+static void fill_f16x2_plan(const float* blob, size_t n_floats, syn_f16x2_plan* plan) {
+    std::memset(plan, 0, sizeof(*plan));
+    if (n_floats == (size_t)MlpGeom::NUM_PARAMS) {
+        F16Image im;
+        if (build_f16x2_image(blob, im)) {
+            plan->valid = 1;
+            for (int l = 0; l < 5; l++) { plan->activation_exp[l] = im.s[l]; plan->weight_exp[l] = im.t[l]; plan->bound[l] = im.bound[l]; }
+            plan->out_exp = im.out_exp;
+        }
+    } else if (n_floats == (size_t)ConvGeom::NUM_PARAMS) {
+        ConvF16Image im;
+        if (build_conv_f16x2_image(blob, im)) {
+            plan->valid = 1;
+            plan->activation_exp[0] = 0; plan->weight_exp[0] = im.tc; plan->bound[0] = im.bound[0];
+            plan->activation_exp[1] = im.s1; plan->weight_exp[1] = im.th; plan->bound[1] = im.bound[1];
+            plan->out_exp = im.out_exp;
+        }
+    }
 }
 static int no_f16x2_plan(syn_engine* h) {
     return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values or scales outside the f32-safe window); "
@@ -963,19 +1025,19 @@ static int no_f16x2_plan(syn_engine* h) {
 // (re)builds the image from the engine's own copy of the parameters when it is not current (after syn_trainer_publish_weights)
 static int ensure_f16x2_image(syn_engine* h) {
     if (h->img16_current) return SYN_OK;
-    if (h->net_kind != 0 || h->host_blob.size() != (size_t)MlpGeom::NUM_PARAMS)
-        return fail(h, SYN_ERR_UNSUPPORTED, "the f16x2 arithmetic exists for Connect4Net only");
-    F16Image im;
-    if (!build_f16x2_image(h->host_blob.data(), im))
+    if (h->host_blob.size() != (size_t)(h->net_kind == 1 ? ConvGeom::NUM_PARAMS : MlpGeom::NUM_PARAMS))
+        return fail(h, SYN_ERR_UNSUPPORTED, "the engine holds no host copy of its parameters to build the f16x2 image from");
+    std::vector<uint32_t> words;
+    if (!build_f16x2_words(h->net_kind, h->host_blob.data(), words))
         return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values or scales outside the f32-safe window)");
-    const int rc = upload_f16x2_image(h, im);
+    const int rc = upload_f16x2_image(h, words);
     if (rc != SYN_OK) return rc;
     h->img16_current = true;
     return SYN_OK;
 }
-// every path that evaluates Connect4Net in the f16x2 arithmetic checks this first
+// every path that evaluates a network in the f16x2 arithmetic checks this first
 static int require_f16x2_image(syn_engine* h) {
-    if (h->net_arith != SYN_NET_ARITH_F16X2 || h->net_kind != 0) return SYN_OK;
+    if (h->net_arith != SYN_NET_ARITH_F16X2) return SYN_OK;
     if (!h->img16_current || !h->d_wimg16)
         return fail(h, SYN_ERR_UNSUPPORTED, "the engine is in the f16x2 arithmetic but holds no f16x2 image of its parameters");
     return SYN_OK;
@@ -987,9 +1049,9 @@ int syn_load_weights(syn_engine* h, const float* blob, size_t n_floats) {
     if (n_floats != (size_t)MlpGeom::NUM_PARAMS)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4Net has %d parameters, got %zu", MlpGeom::NUM_PARAMS, n_floats);
     HIP_TRY(h, hipSetDevice(h->device));
-    F16Image im16;
+    std::vector<uint32_t> im16;
     const bool want16 = h->net_arith == SYN_NET_ARITH_F16X2;
-    if (want16 && !build_f16x2_image(blob, im16)) return no_f16x2_plan(h);   // (before anything of the engine changes)
+    if (want16 && !build_f16x2_words(0, blob, im16)) return no_f16x2_plan(h);   // (before anything of the engine changes)
     std::vector<float> img;
     build_weight_image(blob, img);
     if (want16) {
@@ -1018,17 +1080,15 @@ int syn_set_network_arithmetic(syn_engine* h, int arithmetic) {
         if (h->cap > LANE_MAX_CAP)
             return fail(h, SYN_ERR_UNSUPPORTED, "the f16x2 arithmetic runs in the lane-per-tree kernels: max_explores must be <= %u",
                         (LANE_MAX_CAP - 1u) / 9u - 1u);
-        if (h->has_weights && h->net_kind != 0)
-            return fail(h, SYN_ERR_UNSUPPORTED, "the f16x2 arithmetic exists for Connect4Net only (the engine holds Connect4ConvNet)");
     }
     HIP_TRY(h, hipSetDevice(h->device));
     if (arithmetic == SYN_NET_ARITH_F16X2 && h->has_weights && !h->img16_current) {
-        // the image first; the switch is committed only when it exists
-        if (h->net_kind != 0 || h->host_blob.size() != (size_t)MlpGeom::NUM_PARAMS)
-            return fail(h, SYN_ERR_UNSUPPORTED, "the f16x2 arithmetic exists for Connect4Net only");
-        F16Image im;
-        if (!build_f16x2_image(h->host_blob.data(), im)) return no_f16x2_plan(h);
-        const int rc = upload_f16x2_image(h, im);
+        // the image first (of whichever network the engine holds); the switch is committed only when it exists
+        if (h->host_blob.size() != (size_t)(h->net_kind == 1 ? ConvGeom::NUM_PARAMS : MlpGeom::NUM_PARAMS))
+            return fail(h, SYN_ERR_UNSUPPORTED, "the engine holds no host copy of its parameters to build the f16x2 image from");
+        std::vector<uint32_t> words;
+        if (!build_f16x2_words(h->net_kind, h->host_blob.data(), words)) return no_f16x2_plan(h);
+        const int rc = upload_f16x2_image(h, words);
         if (rc != SYN_OK) return rc;
         h->img16_current = true;
     }
@@ -1046,27 +1106,15 @@ int syn_get_network_arithmetic(syn_engine* h, int* arithmetic, syn_f16x2_plan* p
     if (arithmetic) *arithmetic = h->net_arith;
     if (plan) {
         std::memset(plan, 0, sizeof(*plan));
-        if (h->has_weights && h->net_kind == 0 && !h->host_blob.empty()) {
-            F16Image im;
-            if (build_f16x2_image(h->host_blob.data(), im)) {
-                plan->valid = 1;
-                for (int l = 0; l < 5; l++) { plan->activation_exp[l] = im.s[l]; plan->weight_exp[l] = im.t[l]; plan->bound[l] = im.bound[l]; }
-                plan->out_exp = im.out_exp;
-            }
-        }
+        if (h->has_weights && !h->host_blob.empty()) fill_f16x2_plan(h->host_blob.data(), h->host_blob.size(), plan);
     }
     return SYN_OK;
 }
 
 int syn_f16x2_plan_of_blob(const float* blob, size_t n_floats, syn_f16x2_plan* plan) {
-    if (!blob || !plan || n_floats != (size_t)MlpGeom::NUM_PARAMS) return SYN_ERR_INVALID_ARGUMENT;
-    std::memset(plan, 0, sizeof(*plan));
-    F16Image im;
-    if (build_f16x2_image(blob, im)) {
-        plan->valid = 1;
-        for (int l = 0; l < 5; l++) { plan->activation_exp[l] = im.s[l]; plan->weight_exp[l] = im.t[l]; plan->bound[l] = im.bound[l]; }
-        plan->out_exp = im.out_exp;
-    }
+    if (!blob || !plan || (n_floats != (size_t)MlpGeom::NUM_PARAMS && n_floats != (size_t)ConvGeom::NUM_PARAMS))
+        return SYN_ERR_INVALID_ARGUMENT;
+    fill_f16x2_plan(blob, n_floats, plan);
     return SYN_OK;
 }
 
@@ -1079,16 +1127,25 @@ int syn_load_weights_conv(syn_engine* h, const float* blob, size_t n_floats) {
         return fail(h, SYN_ERR_UNSUPPORTED, "Connect4ConvNet runs in the lane-per-tree kernels: max_explores must be <= %d",
                     (LANE_MAX_CAP - 1) / 9 - 1);
     HIP_TRY(h, hipSetDevice(h->device));
+    // an engine in the f16x2 arithmetic evaluates the new network in it: its image first (conv_f16x2_tile.cuh), before anything of
+    // the engine changes
+    std::vector<uint32_t> im16;
+    const bool want16 = h->net_arith == SYN_NET_ARITH_F16X2;
+    if (want16 && !build_f16x2_words(1, blob, im16)) return no_f16x2_plan(h);
     std::vector<float> img((size_t)ConvGeom::IMG_FLOATS);
     build_conv_image(blob, img.data());
+    if (want16) {
+        h->img16_current = false;
+        const int rc = upload_f16x2_image(h, im16);
+        if (rc != SYN_OK) return rc;
+    }
     HIP_TRY(h, hipMemcpyAsync(h->d_wimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));  // a new network: empty cache
     h->has_weights = true;
     h->net_kind = 1;
-    h->host_blob.clear();
-    h->img16_current = false;
-    h->net_arith = SYN_NET_ARITH_F32;   // (Connect4ConvNet has the f32 arithmetic only)
+    h->host_blob.assign(blob, blob + n_floats);
+    h->img16_current = want16;
     return SYN_OK;
 }
 
@@ -1117,6 +1174,21 @@ static hipError_t launch_policy_eval(syn_engine* h, hipStream_t st, const uint64
         hipLaunchKernelGGL(k, dim3(grid), dim3(NT), (LDS), st, h->d_wimg, reinterpret_cast<const unsigned long long*>(d_my),    \
                            reinterpret_cast<const unsigned long long*>(d_op), n, d_logits, d_value);                           \
     }
+    if (h->net_kind == 1 && h->net_arith == SYN_NET_ARITH_F16X2) {
+        // Connect4ConvNet in the f16x2 arithmetic (conv_f16x2_tile.cuh): the throughput kernel at every size, two waves per SIMD
+        auto k = policy_eval_conv_f16x2_kernel<512>;
+        if (!h->eval_attr_set[5].load(std::memory_order_acquire)) {
+            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(ConvF16Geom::IMG_WORDS * 4))) != hipSuccess)
+                return e;
+            h->eval_attr_set[5].store(true, std::memory_order_release);
+        }
+        int grid = (ntiles + 512 / 64 - 1) / (512 / 64);
+        if (grid > h->num_cus) grid = h->num_cus;
+        hipLaunchKernelGGL(k, dim3(grid), dim3(512), (size_t)ConvF16Geom::IMG_WORDS * 4, st, h->d_wimg16,
+                           reinterpret_cast<const unsigned long long*>(d_my), reinterpret_cast<const unsigned long long*>(d_op), n,
+                           d_logits, d_value);
+    } else
     if (h->net_kind == 0 && h->net_arith == SYN_NET_ARITH_F16X2) {
         // Connect4Net in the f16x2 arithmetic: the throughput kernel at every size (its tile is 3x shorter than the f32 one's)
 #define SYN_LAUNCH_EVAL16(NT, SLOT)                                                                                            \
@@ -1261,7 +1333,7 @@ int syn_eval_ctx_submit(syn_eval_ctx* c, const uint64_t* my_bb, const uint64_t* 
     if (c->pending != 0) return ctx_fail(c, SYN_ERR_INVALID_ARGUMENT, "syn_eval_ctx_submit: the previous batch has not been waited for");
     syn_engine* h = c->h;
     if (!h->has_weights) return ctx_fail(c, SYN_ERR_NO_WEIGHTS, "call syn_load_weights first");
-    if (h->net_arith == SYN_NET_ARITH_F16X2 && h->net_kind == 0 && (!h->img16_current || !h->d_wimg16))
+    if (h->net_arith == SYN_NET_ARITH_F16X2 && (!h->img16_current || !h->d_wimg16))
         return ctx_fail(c, SYN_ERR_UNSUPPORTED, "the engine is in the f16x2 arithmetic but holds no f16x2 image of its parameters");
     if (n == 0) return SYN_OK;
     CTX_TRY(c, hipSetDevice(h->device));
@@ -1551,7 +1623,7 @@ static int common_params(syn_engine* h, EngineParams& P, int explores, bool need
     if (explores > h->max_explores)
         return fail(h, SYN_ERR_CAPACITY, "explores %d exceeds the engine's max_explores %d", explores, h->max_explores);
     std::memset(&P, 0, sizeof(P));
-    P.wimg = (h->net_arith == SYN_NET_ARITH_F16X2 && h->net_kind == 0) ? reinterpret_cast<const float*>(h->d_wimg16) : h->d_wimg;
+    P.wimg = h->net_arith == SYN_NET_ARITH_F16X2 ? reinterpret_cast<const float*>(h->d_wimg16) : h->d_wimg;
     P.stat = h->d_stat;
     P.edge = h->d_edge;
     P.cap = h->cap;
@@ -2598,11 +2670,15 @@ int syn_trainer_publish_weights(syn_engine* h) {
         HIP_TRY(h, hipGetLastError());
         if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));
         HIP_TRY(h, hipStreamSynchronize(h->stream));
+        // the f16x2 image is built on the host from the canonical parameters (conv_f16x2_tile.cuh): keep a copy of what was
+        // published; an engine in the f16x2 arithmetic stays in it, as Connect4Net's publish below does
+        h->host_blob.resize((size_t)ConvGeom::NUM_PARAMS);
+        HIP_TRY(h, hipMemcpyAsync(h->host_blob.data(), h->d_tw, (size_t)ConvGeom::NUM_PARAMS * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
         h->has_weights = true;
         h->net_kind = 1;
-        h->host_blob.clear();
         h->img16_current = false;
-        h->net_arith = SYN_NET_ARITH_F32;
+        if (h->net_arith == SYN_NET_ARITH_F16X2) return ensure_f16x2_image(h);
         return SYN_OK;
     }
     // the trainer keeps its weights in the inference fragment order as well (train_mfma.cuh): publishing is one device copy

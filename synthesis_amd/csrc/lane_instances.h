@@ -63,3 +63,13 @@
     X(MODE_SELFPLAY, false, 2, 12, 3) X(MODE_SELFPLAY, true, 2, 12, 3) X(MODE_SEARCH, false, 2, 12, 3)           \
     X(MODE_SELFPLAY, false, 1, 8, 3) X(MODE_SELFPLAY, true, 1, 8, 3) X(MODE_SEARCH, false, 1, 8, 3)              \
     X(MODE_SELFPLAY, false, 2, 8, 3) X(MODE_SELFPLAY, true, 2, 8, 3) X(MODE_SEARCH, false, 2, 8, 3)
+// Connect4ConvNet in the f16x2 arithmetic (POLICY 4, conv_f16x2_tile.cuh; engine_conv_f16.hip): search, self-play and self-play with
+// counters, as POLICY 2 ships them, at the wave counts whose instantiations keep their registers: the parity family (FAST true) at 4 and
+// 8 waves, the runtime-switched family (FAST false: also the reference's own configuration) at 4
+#define SYN_LANES_CONV_F16_LIST(X)                                                                               \
+    X(MODE_SEARCH, false, true, 4, false, 4) X(MODE_SEARCH, false, true, 8, false, 4)                            \
+    X(MODE_SEARCH, false, false, 4, false, 4)                                                                    \
+    X(MODE_SELFPLAY, false, true, 4, false, 4) X(MODE_SELFPLAY, false, true, 8, false, 4)                        \
+    X(MODE_SELFPLAY, false, false, 4, false, 4)                                                                  \
+    X(MODE_SELFPLAY, true, true, 4, false, 4) X(MODE_SELFPLAY, true, true, 8, false, 4)                          \
+    X(MODE_SELFPLAY, true, false, 4, false, 4)

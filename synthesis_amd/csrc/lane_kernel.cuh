@@ -24,6 +24,7 @@
 #include "noise.cuh"
 #include "convnet.cuh"
 #include "f16x2_tile.cuh"
+#include "conv_f16x2_tile.cuh"
 
 namespace syn {
 
@@ -1411,6 +1412,7 @@ SYN_DEV uint64_t shfl_u64(uint64_t v, int src) {
 // POLICY: 0 = Connect4Net on the matrix cores, 1 = RolloutPolicy (policies/rollout.rs; searches only),
 //         2 = Connect4ConvNet on the matrix cores (convnet.cuh: its image takes the first 66 KB of the Connect4Net image's LDS)
 //         3 = Connect4Net in the f16x2 arithmetic (f16x2_tile.cuh: two-term f16 split on v_mfma_f32_16x16x32_f16; P.wimg is that image)
+//         4 = Connect4ConvNet in the f16x2 arithmetic (conv_f16x2_tile.cuh; P.wimg is that image, 67.7 KB of the same LDS region)
 template <int MODE, bool COUNT, int FAST, int NW, bool PROF = false, int POLICY = 0>
 __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -1423,10 +1425,11 @@ __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams
 
     if (POLICY == 0) stage_weight_image(wimg, P.wimg, tid, NT);
     if (POLICY == 2) stage_conv_image(wimg, P.wimg, tid, NT);
-    if (POLICY == 3) {
+    if (POLICY == 3 || POLICY == 4) {
         const uint4* src = reinterpret_cast<const uint4*>(P.wimg);
         uint4* dst = reinterpret_cast<uint4*>(smem_raw);
-        for (int i = tid; i < F16Geom::IMG_WORDS / 4; i += NT) dst[i] = src[i];
+        constexpr int IMG_WORDS = POLICY == 3 ? F16Geom::IMG_WORDS : ConvF16Geom::IMG_WORDS;
+        for (int i = tid; i < IMG_WORDS / 4; i += NT) dst[i] = src[i];
     }
     // RolloutPolicy needs no weights: the image's LDS holds the waves' ChaCha12 block rings instead (12 KB per wave)
     RolloutRing ring;
@@ -1560,6 +1563,15 @@ __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams
                 uint32_t img_off = 0;  // opaque per tile: the image reads stay LDS reads next to their MFMAs
                 asm volatile("" : "+v"(img_off));
                 o = conv_tile16(wimg + img_off, lane, tmy, top);
+            } else if (POLICY == 4) {
+                const uint64_t tmy = shfl_u64(Wk.my, src), top = shfl_u64(Wk.op, src);
+                uint32_t img_off = 0;  // opaque per tile: the image reads stay LDS reads next to their MFMAs
+                asm volatile("" : "+v"(img_off));
+                const uint32_t* img16 = reinterpret_cast<const uint32_t*>(smem_raw) + img_off;
+                o = conv_f16x2_tile16(img16, lane, tmy, top);
+                const float os = reinterpret_cast<const float*>(img16 + ConvF16Geom::SCALE_W0)[1];   // exact power of two
+#pragma unroll
+                for (int r = 0; r < 4; r++) o[r] *= os;
             } else if (POLICY == 3) {
                 uint64_t hi, lo;
                 feature_boards(Wk.my, Wk.op, hi, lo);

@@ -170,9 +170,20 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _network_of(n_params):
+    return "Connect4ConvNet" if n_params == CONV_NUM_PARAMS else "Connect4Net"
+
+
+def _plan_dict(pl, network):
+    """syn_f16x2_plan as a dict; "network" names the network it belongs to (Connect4ConvNet: layer 0 = the conv layer, 1 = the head,
+    2..4 zero)."""
+    return dict(network=network, activation_exp=list(pl.activation_exp), weight_exp=list(pl.weight_exp), out_exp=pl.out_exp,
+                bound=list(pl.bound))
+
+
 def f16x2_plan_of_blob(blob):
-    """The f16x2 plan (power-of-two scales) syn_set_network_arithmetic would choose for a Connect4Net blob — host code only, no GPU.
-    None when the blob has no plan (non-finite parameters)."""
+    """The f16x2 plan (power-of-two scales) syn_set_network_arithmetic would choose for a Connect4Net (30,492 floats) or Connect4ConvNet
+    (12,412 floats) blob — host code only, no GPU. None when the blob has no plan (non-finite parameters)."""
     lib = load_library()
     blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
     pl = CF16x2Plan()
@@ -181,7 +192,7 @@ def f16x2_plan_of_blob(blob):
         raise SynthesisAmdError(rc, "syn_f16x2_plan_of_blob: bad arguments")
     if not pl.valid:
         return None
-    return dict(activation_exp=list(pl.activation_exp), weight_exp=list(pl.weight_exp), out_exp=pl.out_exp, bound=list(pl.bound))
+    return _plan_dict(pl, _network_of(blob.size))
 
 
 def shard_games(n_games, rank, world_size):
@@ -252,6 +263,7 @@ class Engine:
         self.concurrent_games = int(concurrent_games)
         self.max_explores = int(max_explores)
         self.device = int(device)
+        self._net_params = None   # parameter count of the network the engine evaluates (set by the loads and the learner's publish)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -290,27 +302,30 @@ class Engine:
     def load_weights(self, blob):
         blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
         self._check(self._lib.syn_load_weights(self._h, _p(blob), blob.size))
+        self._net_params = NUM_PARAMS
 
     def load_weights_conv(self, blob):
         """Connect4ConvNet (Conv2d<2,16,3,pad 1> + ReLU + Linear<1008,12>; include/synthesis_amd.h) becomes the engine's policy."""
         blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
         self._check(self._lib.syn_load_weights_conv(self._h, _p(blob), blob.size))
+        self._net_params = CONV_NUM_PARAMS
 
-    # ---- the arithmetic Connect4Net is evaluated in (include/synthesis_amd.h: SYN_NET_ARITH_*)
+    # ---- the arithmetic the network is evaluated in (include/synthesis_amd.h: SYN_NET_ARITH_*)
     def set_network_arithmetic(self, arithmetic):
-        """"f32" (default: v_mfma_f32_16x16x4_f32, the oracle's ACC_FMA) or "f16x2" (two-term f16 split on v_mfma_f32_16x16x32_f16, the
-        oracle's ACC_F16X2); holds for policy_eval, evaluation contexts, mcts_search and selfplay until changed."""
+        """"f32" (default: v_mfma_f32_16x16x4_f32, the oracle's ACC_FMA) or "f16x2" (two-term f16 split on v_mfma_f32_16x16x32_f16: the
+        oracle's ACC_F16X2 for Connect4Net, conv_f16x2_tile.cuh for Connect4ConvNet); holds for policy_eval, evaluation contexts,
+        mcts_search and selfplay — and for weights loaded or published later — until changed."""
         code = {"f32": 0, "f16x2": 1}.get(arithmetic, arithmetic)
         self._check(self._lib.syn_set_network_arithmetic(self._h, int(code)))
 
     def network_arithmetic(self):
-        """(name, plan): plan = None or a dict of the f16x2 scales of the current Connect4Net."""
+        """(name, plan): plan = None or a dict of the f16x2 scales of the engine's current network ("network" says which)."""
         a = C.c_int()
         pl = CF16x2Plan()
         self._check(self._lib.syn_get_network_arithmetic(self._h, C.byref(a), C.byref(pl)))
         plan = None
         if pl.valid:
-            plan = dict(activation_exp=list(pl.activation_exp), weight_exp=list(pl.weight_exp), out_exp=pl.out_exp, bound=list(pl.bound))
+            plan = _plan_dict(pl, _network_of(self._net_params))
         return ("f16x2" if a.value == 1 else "f32"), plan
 
     # ---- Policy::eval, batched (policies.rs:47-59)
@@ -602,6 +617,7 @@ class Engine:
 
     def trainer_publish_weights(self):
         self._check(self._lib.syn_trainer_publish_weights(self._h))
+        self._net_params = self._trainer_params
 
     def replay_deduplicate(self, my_bb, op_bb, pis, vs):
         my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()

@@ -50,12 +50,15 @@ class LearningLoop:
                  advanced epoch after epoch: the reference's algorithm and generator TYPE, not its stream — in a reference run
                  `tch::manual_seed(seed)` (alpha_zero.rs:28) is followed by `P::new(&vs)` (:31), whose parameter initialisation draws
                  from that same global generator before the first randperm, so the permutations of a Rust run differ
+    network_arithmetic  "f32" (default) | "f16x2": the arithmetic this rank's engine evaluates the network in during self-play
+                 (include/synthesis_amd.h syn_set_network_arithmetic; both networks). The learner itself trains in `precision`.
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
     """
 
-    def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy", **hyper):
+    def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
+                 network_arithmetic="f32", **hyper):
         import torch
 
         self._torch = torch
@@ -71,6 +74,8 @@ class LearningLoop:
         assert blob.size == self.n_params
         self._load = engine.load_weights_conv if net == "conv" else engine.load_weights
         self._load(blob)
+        if network_arithmetic != "f32":   # (later loads and the learner's publish keep the engine's arithmetic)
+            engine.set_network_arithmetic(network_arithmetic)
         self.weights = blob.copy()
         # the buffer the broadcast moves: on the GPU for RCCL, on the host for gloo
         on_gpu = self.dist is not None and self.dist.get_backend() == "nccl"
@@ -235,9 +240,10 @@ class LearningLoop:
 class DataParallelLearner:
     """Gradient all-reduce per optimiser step (see the module docstring). Every rank holds identical weights and Adam moments."""
 
-    def __init__(self, engine, blob, dist=None, device=0, net="mlp", collective_at_world_1=False, **hyper):
+    def __init__(self, engine, blob, dist=None, device=0, net="mlp", collective_at_world_1=False, network_arithmetic="f32", **hyper):
         """collective_at_world_1: keep the all-reduce in the step when the group has one rank (bench.py's `data_parallel_world1`:
-        the literal gradients -> RCCL all-reduce -> Adam path of BASELINE configs[4] on a one-GPU box)."""
+        the literal gradients -> RCCL all-reduce -> Adam path of BASELINE configs[4] on a one-GPU box).
+        network_arithmetic: "f32" | "f16x2", the arithmetic the engine's self-play evaluates the published network in."""
         import torch
 
         self._torch = torch
@@ -248,6 +254,8 @@ class DataParallelLearner:
         self.device = torch.device(f"cuda:{device}")
         self.n_params = CONV_NUM_PARAMS if net == "conv" else NUM_PARAMS
         (engine.trainer_init_conv if net == "conv" else engine.trainer_init)(blob, **hyper)
+        if network_arithmetic != "f32":
+            engine.set_network_arithmetic(network_arithmetic)
         # [gradients | pi-loss sum | v-loss sum]: one buffer, one all-reduce per step
         self.buf = torch.zeros(self.n_params + 2, dtype=torch.float32, device=self.device)
         self._staged = self.dist is not None and self.dist.get_backend() != "nccl"

@@ -22,8 +22,11 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fh
 
 # the device translation units of the DEFAULT library (synthesis_amd/csrc/Makefile without DEBUG_SHAPES); `--debug-shapes` adds the
 # forced-only kernels (two trees per lane, trees unbound from the lanes)
-TUS = ["engine", "engine_conv", "engine_lanes_fast", "engine_lanes_gen", "engine_lanes_ref", "engine_lanes_f16", "engine_lanes_f16_gen",
-       "engine_free"]
+TUS = ["engine", "engine_conv", "engine_conv_f16", "engine_lanes_fast", "engine_lanes_gen", "engine_lanes_ref", "engine_lanes_f16",
+       "engine_lanes_f16_gen", "engine_free"]
+# `--tu NAME` (repeatable): only these translation units (e.g. --tu engine_conv_f16 for the Connect4ConvNet f16x2 instantiations)
+if "--tu" in sys.argv:
+    TUS = [sys.argv[i + 1] for i, a in enumerate(sys.argv) if a == "--tu"]
 if "--debug-shapes" in sys.argv:
     TUS += ["engine_lanes2", "engine_pool", "engine_pool_f16"]
     FLAGS.append("-DSYN_DEBUG_SHAPES")
@@ -94,7 +97,8 @@ def main():
         print("# kernel-resource-usage of every shipped self-play kernel instantiation (gfx950; hipcc -Rpass-analysis=kernel-resource-usage,")
         print("# the Makefile's flags). scratch ops = static scratch_load/store instructions: whole kernel / inside the MFMA range / inside loops.")
         print("# template arguments: selfplay_kernel_lanes<MODE (0 self-play, 1 search), COUNT, FAST, waves, PROF, POLICY (0 Connect4Net, 1 rollout, 2 conv)>,")
-        print("#                     (POLICY 3 = Connect4Net in the f16x2 arithmetic; FAST 0 runtime-switched, 1 parity family, 2 the reference's self-play configuration)")
+        print("#                     (POLICY 3 = Connect4Net in the f16x2 arithmetic, POLICY 4 = Connect4ConvNet in the f16x2 arithmetic; FAST 0 runtime-switched,")
+        print("#                      1 parity family, 2 the reference's self-play configuration)")
         print("#                     selfplay_kernel<MODE, COUNT, WPS, FAST, PROF>, selfplay_kernel_quads<MODE, COUNT, FAST, NQ, PROF>, selfplay_kernel_free<MODE, COUNT, FAST, PROF>,")
         print("#                     selfplay_kernel_lanes2<MODE, COUNT, FAST, waves, POLICY, TILE>, selfplay_kernel_pool<MODE, COUNT, FAST, waves, POLICY>")
         print("%-96s %5s %5s %5s %4s %8s %7s %7s  %s" % ("kernel", "VGPR", "AGPR", "SGPR", "occ", "scratchB", "vspill", "sspill", "scratch ops all/mfma/loops"))
