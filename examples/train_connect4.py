@@ -2,7 +2,8 @@
 """The reference's learning loop (synthesis/src/alpha_zero.rs:16-118, configured like study-connect4/src/main.rs:11-52)
 with every heavy step on the MI355X: self-play (fused MCTS + network kernel), replay de-duplication (sort + segmented
 reduce) and the optimiser steps (HIP forward/backward/Adam), the trained weights going back to the self-play network on
-the device. Host code only moves indices: the replay buffer lives in numpy arrays, batches are drawn by a seeded
+the device. Host code only moves indices: the replay buffer lives in numpy arrays — or, with --replay device, in the engine's
+device memory, so that the positions never cross the host link (Engine.replay_*) — and batches are drawn by a seeded
 permutation (BatchRandSampler, data.rs:6-64, drop_last = true).
 
     python examples/train_connect4.py --iterations 3 --games-per-train 4096 --explores 200
@@ -71,7 +72,12 @@ def main():
                     "f16x2 = every operand a pair of f16 numbers on the f16 matrix cores (syn_set_network_arithmetic; --net mlp and conv)")
     ap.add_argument("--data-parallel", action="store_true", help="gradient all-reduce per optimiser step on every rank instead of "
                     "the learner on rank 0 + one weight broadcast per iteration")
+    ap.add_argument("--replay", default="host", choices=["host", "device"], help="where the learning loop's replay buffer lives: host = "
+                    "numpy arrays on rank 0 (self-play downloads its padded outputs); device = the engine's device memory (compaction, "
+                    "keep-window and de-duplication on the GPU, same bits); learning loop only")
     args = ap.parse_args()
+    if args.replay != "host" and args.data_parallel:
+        raise SystemExit("--replay device belongs to the learning loop: --data-parallel keeps one replay buffer per rank on the host")
 
     import torch  # noqa: F401  (before the engine: one HIP runtime per process)
 
@@ -111,7 +117,7 @@ def main():
     else:
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
-                            network_arithmetic=args.network_arithmetic, **hyper)
+                            network_arithmetic=args.network_arithmetic, replay=args.replay, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -430,6 +430,58 @@ int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t*
                            const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v,
                            uint32_t* out_num, size_t* out_count);
 
+/* ---- The replay buffer in device memory (the reference's ReplayBuffer, synthesis/src/data.rs:107-235, between gather_experience and
+ * the epochs of alpha_zero.rs:42-100). It belongs to the engine: five structure-of-arrays sections my | op | gid | pi[9] | v[3] of
+ * `capacity` positions each, 72 bytes per position, plus a second buffer of the same size once a keep-window has dropped something.
+ * Positions keep buffer order through every call below (game order, then ply order; appended parts in call order) — the
+ * de-duplication sums the targets of identical states in that order, so the learner's data set is bit for bit what the host path
+ * (syn_selfplay_run's padded arrays -> mask by plies -> concatenate -> filter by game id -> syn_replay_deduplicate ->
+ * syn_train_set_data) produces from the same games. All calls are ordered on the engine's stream and wait for the device only where
+ * a count has to reach the host. Device pointers a caller passes in must be ready (their producer's stream synchronised) and must stay
+ * valid until the next call on the handle that waits for the device. One handle, one calling thread at a time, as for the rest.
+ *
+ * syn_replay_reserve: ReplayBuffer::new(n) (data.rs:117-130) — allocates, or grows keeping the contents; never shrinks.
+ * syn_replay_clear / syn_replay_size: drop everything / curr_steps() (data.rs:148-150). */
+int syn_replay_reserve(syn_engine* h, size_t capacity_positions);
+int syn_replay_clear(syn_engine* h);
+int syn_replay_size(syn_engine* h, size_t* n_positions);
+/* The positions of the LAST syn_selfplay_run on this handle (which always leaves its outputs on the device, whatever host pointers it
+ * was given), compacted into caller-owned device sections: game slot g contributes its plies[g] positions in ply order, games in slot
+ * order, gid = first_gid + g; games that never started (plies == 0 after syn_cancel) contribute nothing. This is run_n_games'
+ * buffer (alpha_zero.rs:181-209) without the padded download — what a rank that is not the learner hands to the gather.
+ * *n_positions = sum of plies. SYN_ERR_INVALID_ARGUMENT when no self-play has completed on the handle (or the last one failed);
+ * SYN_ERR_CAPACITY, nothing written, when the sections (room for `capacity` positions each) are too small. Returns after the
+ * sections are complete. */
+int syn_selfplay_positions_device(syn_engine* h, int64_t first_gid, uint64_t* d_my, uint64_t* d_op, int64_t* d_gid, float* d_pi,
+                                  float* d_v, size_t capacity, size_t* n_positions);
+/* ReplayBuffer::extend (data.rs:132-146) for the last self-play launch: the same compaction straight onto the tail of the engine's
+ * buffer. *n_appended (may be NULL) = positions added. */
+int syn_replay_append_selfplay(syn_engine* h, int64_t first_gid, size_t* n_appended);
+/* ReplayBuffer::extend for positions that came from elsewhere (other ranks' games, a caller's own): n positions from device sections /
+ * from host arrays (my_bb[n], op_bb[n], gid[n], pis[n][9], vs[n][3]) onto the tail. Every append that would exceed the reserved
+ * capacity returns SYN_ERR_CAPACITY and leaves the buffer exactly as it was. */
+int syn_replay_append_device(syn_engine* h, const uint64_t* d_my, const uint64_t* d_op, const int64_t* d_gid, const float* d_pi,
+                             const float* d_v, size_t n);
+int syn_replay_append(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const int64_t* gid, const float* pis, const float* vs,
+                      size_t n);
+/* ReplayBuffer::keep_last_n_games (data.rs:160-194) with the window given as its first game: every position with gid < min_gid is
+ * dropped, the others keep their order (stable for any order of ids, not only non-decreasing ones). An empty result is legal. */
+int syn_replay_keep_games_from(syn_engine* h, int64_t min_gid);
+/* Copies the buffer out (tests, logs): arrays sized for `capacity` positions, any of them may be NULL; *n_positions (may be NULL) =
+ * the buffer's size, also when SYN_ERR_CAPACITY says the arrays are too small (nothing is copied then). */
+int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gid, float* pis, float* vs, size_t capacity,
+                    size_t* n_positions);
+/* ReplayBuffer::deduplicate (data.rs:196-235) + the tensors of alpha_zero.rs:52-58 without a host copy: de-duplicates the buffer
+ * (syn_replay_deduplicate's device core: same order, same sums) and makes the unique set the learner's data set, i.e. the state
+ * syn_train_set_data would have left; the buffer itself is unchanged. *n_unique (may be NULL) = its size. Needs syn_trainer_init*
+ * first (SYN_ERR_NO_WEIGHTS); an empty buffer is SYN_ERR_INVALID_ARGUMENT. */
+int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique);
+/* The learner's current data set (syn_train_set_data / syn_replay_deduplicate_to_trainer) copied out — what alpha_zero.rs:98-100
+ * writes as latest_*.npy. Arrays sized for `capacity` states, any may be NULL; *n (may be NULL) = the set's size, also on
+ * SYN_ERR_CAPACITY. */
+int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity,
+                       size_t* n);
+
 /* Timing of the last syn_selfplay_run / syn_mcts_search / *_device call on this handle, measured with HIP events on
  * the engine stream: kernel_ms = device time of the dominant kernel launch(es), n_launches = how many. */
 int syn_last_timing(const syn_engine* h, float* kernel_ms, int* n_launches);

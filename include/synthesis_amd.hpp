@@ -12,6 +12,8 @@
 //                                                    eval = batch of one, eval_batch = the throughput form
 //   synthesis::ReplayBuffer                          synthesis/src/data.rs:107-235 (new_game, add, extend,
 //                                                    keep_last_n_games, deduplicate, the counters)
+//   synthesis::DeviceReplayBuffer                    the same buffer in the engine's device memory (syn_replay_*): extend from the
+//                                                    last self-play launch, keep_last_n_games, deduplicate into the learner
 //   synthesis::run_n_games                           synthesis/src/alpha_zero.rs:181-209
 //   synthesis::vanilla_mcts_search                   MCTS over RolloutPolicy (policies/rollout.rs:8-31; mcts.rs:691-868)
 //   synthesis::frozen_mcts_exploit / mcts_vs_mcts /  the evaluator's baseline and its three match loops,
@@ -372,6 +374,50 @@ public:
 private:
     size_t game_id_ = 0, steps_ = 0;
     std::vector<size_t> game_ids_;
+};
+
+// ReplayBuffer in the engine's device memory (syn_replay_*, include/synthesis_amd.h): the positions of a self-play launch never
+// cross the host link — extend_from_selfplay compacts the last launch's device outputs onto the tail, keep_last_n_games trims on the
+// device, deduplicate_to_trainer leaves the unique set as the learner's data set (what syn_train_set_data would have been given).
+// Game ids count from 0 in the order the games were appended (the host ReplayBuffer's start at 1: the window is the same games).
+class DeviceReplayBuffer {
+public:
+    // n = capacity in positions (72 bytes each)
+    DeviceReplayBuffer(Engine& e, size_t n) : e_(e) {
+        e_.check(syn_replay_clear(e_.handle()));
+        e_.check(syn_replay_reserve(e_.handle(), n));
+    }
+    size_t total_games_played() const { return game_id_; }
+    size_t total_steps() const { return steps_; }
+    size_t curr_steps() const {
+        size_t n = 0;
+        e_.check(syn_replay_size(e_.handle(), &n));
+        return n;
+    }
+    // extend (data.rs:132-146) with the num_games games of the engine's last syn_selfplay_run (all output pointers may have been NULL);
+    // returns the positions added. Throws Error(SYN_ERR_CAPACITY), buffer unchanged, when they do not fit.
+    size_t extend_from_selfplay(size_t num_games) {
+        size_t n = 0;
+        e_.check(syn_replay_append_selfplay(e_.handle(), (int64_t)game_id_, &n));
+        game_id_ += num_games;
+        steps_ += n;
+        return n;
+    }
+    void keep_last_n_games(size_t n) {
+        if (game_id_ <= n) return;
+        e_.check(syn_replay_keep_games_from(e_.handle(), (int64_t)(game_id_ - n)));
+    }
+    // deduplicate (data.rs:196-235) straight into the learner of this engine (Learner / syn_trainer_init first); returns the number
+    // of unique states syn_train_epoch then indexes
+    size_t deduplicate_to_trainer() {
+        size_t m = 0;
+        e_.check(syn_replay_deduplicate_to_trainer(e_.handle(), &m));
+        return m;
+    }
+
+private:
+    Engine& e_;
+    size_t game_id_ = 0, steps_ = 0;
 };
 
 // run_n_games (alpha_zero.rs:181-209): games [first_game, first_game + num_games) played on the GPU; game g draws from

@@ -26,6 +26,7 @@
 #endif
 #include "frozen_kernel.cuh"
 #include "train_kernels.cuh"
+#include "replay_kernels.cuh"
 #include "train_mfma.cuh"
 #include "train_epoch.cuh"
 #include "convnet.cuh"
@@ -159,6 +160,12 @@ struct syn_engine {
     unsigned long long last_cache_hits = 0, last_cache_misses = 0;
     void* d_train_data = nullptr;  // syn_train_set_data: [my u64 n][op u64 n][pi 9 f32 n][v 3 f32 n]
     size_t train_data_cap = 0, train_data_n = 0;
+    // the device-resident replay buffer (syn_replay_*; replay_kernels.cuh): sections my | op | gid | pi | v of replay_cap positions each
+    // in ONE allocation; d_replay_alt is the keep-window's second buffer (same size, allocated when a keep first drops something)
+    unsigned char* d_replay = nullptr;
+    unsigned char* d_replay_alt = nullptr;
+    size_t replay_cap = 0, replay_n = 0;
+    int last_selfplay_games = -1;  // games of the last syn_selfplay_run whose outputs are in d_plies / d_states / d_pis / d_vs (-1: none yet)
     uint4* d_path = nullptr;   // lane kernel's per-wave descent logs
     size_t path_bytes = 0;
     unsigned char* d_vw = nullptr;  // producer/consumer kernel: per-virtual-wave parked state + network outputs
@@ -942,6 +949,8 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_path);
     hipFree(h->d_vw);
     hipFree(h->d_train_data);
+    hipFree(h->d_replay);
+    hipFree(h->d_replay_alt);
     hipFree(h->d_cache);
     hipFree(h->d_cache_stats);
     hipFree(h->d_counters);
@@ -1856,6 +1865,8 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
     if (rc != SYN_OK) return rc;
     if ((rc = check_lane_only(h, P.mcts)) != SYN_OK) return rc;
     if (counters) std::memset(counters, 0, sizeof(*counters));
+    // what syn_replay_append_selfplay / syn_selfplay_positions_device compact: nothing until this launch has ended without an error
+    h->last_selfplay_games = n_games == 0 ? 0 : -1;
     if (n_games == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     rc = ensure_outputs(h, n_games);
@@ -2022,6 +2033,7 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
     if (kerr) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
     HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
     h->last_launches = 1;
+    h->last_selfplay_games = n_games;
     // decided by what finished, not by the flag: a cancel that arrives after the last game was handed out cancels nothing
     if (scope.cancelled() && games_finished < n_games)
         return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel: %d of %d games were played (to the end); the others have plies == 0",
@@ -2696,55 +2708,57 @@ int syn_trainer_publish_weights(syn_engine* h) {
 }
 
 // ------------------------------------------------------------------------------------------------ deduplicate
-int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis,
-                           const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v,
-                           uint32_t* out_num, size_t* out_count) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!out_count) return fail(h, SYN_ERR_INVALID_ARGUMENT, "out_count is NULL");
-    *out_count = 0;
-    if (n == 0) return SYN_OK;
-    if (!my_bb || !op_bb || !pis || !vs || !out_my || !out_op || !out_pi || !out_v || !out_num || n > 0x7FFFFFFFu)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_replay_deduplicate");
-    HIP_TRY(h, hipSetDevice(h->device));
+// The device core of ReplayBuffer::deduplicate (data.rs:196-235): n positions at device pointers -> the unique states in ascending
+// (my_bb, op_bb) order, targets summed in buffer order. `work` is the caller's scratch of dedup_work_bytes(n) bytes; the outputs
+// point into it. Stream-ordered on h->stream with ONE synchronise in the middle (the number of unique states sizes the reduce's grid).
+struct DedupOut {
+    unsigned long long* my = nullptr;
+    unsigned long long* op = nullptr;
+    float* pi = nullptr;
+    float* v = nullptr;
+    unsigned* num = nullptr;
+    int m = 0;
+};
+static size_t dedup_align(size_t x) { return (x + 255) & ~(size_t)255; }
+static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total) {
     const int ni = (int)n;
-    // device layout: inputs | sort keys/values (double buffers) | heads | scan | seg_start | outputs | cub temp
     size_t tmp_sort = 0, tmp_scan = 0;
     HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const unsigned long long*)nullptr,
                                                   (unsigned long long*)nullptr, (const unsigned*)nullptr,
                                                   (unsigned*)nullptr, ni, 0, 64, h->stream));
     HIP_TRY(h, hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni,
                                                 h->stream));
-    size_t tmp = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    *tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
+    // sort keys/values (double buffers) | heads | scan | seg_start | outputs | cub temp
+    *total = 2 * dedup_align(n * 8) + 2 * dedup_align(n * 4) + 3 * dedup_align(n * 4) + 2 * dedup_align(n * 8) + dedup_align(n * 36) +
+             dedup_align(n * 12) + dedup_align(n * 4) + dedup_align(*tmp_bytes);
+    return SYN_OK;
+}
+static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsigned long long* d_my, const unsigned long long* d_op,
+                             const float* d_pi, const float* d_v, size_t n, DedupOut* out) {
+    const int ni = (int)n;
     size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += al(bytes); return o; };
-    size_t o_my = take(n * 8), o_op = take(n * 8), o_pi = take(n * 36), o_v = take(n * 12);
+    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
     size_t o_k0 = take(n * 8), o_k1 = take(n * 8), o_i0 = take(n * 4), o_i1 = take(n * 4);
     size_t o_head = take(n * 4), o_scan = take(n * 4), o_start = take(n * 4);
     size_t o_omy = take(n * 8), o_oop = take(n * 8), o_opi = take(n * 36), o_ov = take(n * 12), o_on = take(n * 4);
     size_t o_tmp = take(tmp);
-    int rc = ensure_scratch(h, off + 256);
-    if (rc != SYN_OK) return rc;
-    char* base = static_cast<char*>(h->d_scratch);
+    char* base = work;
     auto P8 = [&](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     auto P4 = [&](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
     auto PF = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
-    HIP_TRY(h, hipMemcpyAsync(P8(o_my), my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(P8(o_op), op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(PF(o_pi), pis, n * 36, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(PF(o_v), vs, n * 12, hipMemcpyHostToDevice, h->stream));
     const int blocks = (ni + 255) / 256;
     // stable LSD sort of the buffer indices by the 128-bit key: first by op_bb, then by my_bb
     hipLaunchKernelGGL(iota_kernel, dim3(blocks), dim3(256), 0, h->stream, P4(o_i0), ni);
     size_t t1 = tmp;
-    HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, t1, P8(o_op), P8(o_k0), P4(o_i0), P4(o_i1), ni, 0, 64,
+    HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, t1, d_op, P8(o_k0), P4(o_i0), P4(o_i1), ni, 0, 64,
                                                   h->stream));
-    hipLaunchKernelGGL(gather_u64_kernel, dim3(blocks), dim3(256), 0, h->stream, P8(o_my), P4(o_i1), ni, P8(o_k1));
+    hipLaunchKernelGGL(gather_u64_kernel, dim3(blocks), dim3(256), 0, h->stream, d_my, P4(o_i1), ni, P8(o_k1));
     t1 = tmp;
     HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(base + o_tmp, t1, P8(o_k1), P8(o_k0), P4(o_i1), P4(o_i0), ni, 0, 64,
                                                   h->stream));
     // o_k0 = my_bb sorted, o_i0 = buffer indices in (my, op, index) order; op_bb in that order:
-    hipLaunchKernelGGL(gather_u64_kernel, dim3(blocks), dim3(256), 0, h->stream, P8(o_op), P4(o_i0), ni, P8(o_k1));
+    hipLaunchKernelGGL(gather_u64_kernel, dim3(blocks), dim3(256), 0, h->stream, d_op, P4(o_i0), ni, P8(o_k1));
     hipLaunchKernelGGL(dedup_heads_kernel, dim3(blocks), dim3(256), 0, h->stream, P8(o_k0), P8(o_k1), ni, P4(o_head));
     t1 = tmp;
     HIP_TRY(h, hipcub::DeviceScan::InclusiveSum(base + o_tmp, t1, P4(o_head), P4(o_scan), ni, h->stream));
@@ -2755,16 +2769,359 @@ int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t*
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const int m = (int)m_u;
     hipLaunchKernelGGL(dedup_reduce_kernel, dim3((m * 16 + 255) / 256), dim3(256), 0, h->stream, P4(o_i0), P4(o_start),
-                       m, ni, P8(o_my), P8(o_op), PF(o_pi), PF(o_v), P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov),
-                       P4(o_on));
+                       m, ni, d_my, d_op, d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out_my, P8(o_omy), (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_op, P8(o_oop), (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_pi, PF(o_opi), (size_t)m * 36, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_v, PF(o_ov), (size_t)m * 12, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_num, P4(o_on), (size_t)m * 4, hipMemcpyDeviceToHost, h->stream));
+    out->my = P8(o_omy);
+    out->op = P8(o_oop);
+    out->pi = PF(o_opi);
+    out->v = PF(o_ov);
+    out->num = P4(o_on);
+    out->m = m;
+    return SYN_OK;
+}
+
+int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis,
+                           const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v,
+                           uint32_t* out_num, size_t* out_count) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!out_count) return fail(h, SYN_ERR_INVALID_ARGUMENT, "out_count is NULL");
+    *out_count = 0;
+    if (n == 0) return SYN_OK;
+    if (!my_bb || !op_bb || !pis || !vs || !out_my || !out_op || !out_pi || !out_v || !out_num || n > 0x7FFFFFFFu)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_replay_deduplicate");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // device layout: inputs | the core's work area
+    size_t tmp = 0, work = 0;
+    int rc = dedup_work_bytes(h, n, &tmp, &work);
+    if (rc != SYN_OK) return rc;
+    const size_t o_my = 0, o_op = o_my + dedup_align(n * 8), o_pi = o_op + dedup_align(n * 8), o_v = o_pi + dedup_align(n * 36);
+    const size_t o_work = o_v + dedup_align(n * 12);
+    rc = ensure_scratch(h, o_work + work + 256);
+    if (rc != SYN_OK) return rc;
+    char* base = static_cast<char*>(h->d_scratch);
+    unsigned long long* d_my = reinterpret_cast<unsigned long long*>(base + o_my);
+    unsigned long long* d_op = reinterpret_cast<unsigned long long*>(base + o_op);
+    float* d_pi = reinterpret_cast<float*>(base + o_pi);
+    float* d_v = reinterpret_cast<float*>(base + o_v);
+    HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_pi, pis, n * 36, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_v, vs, n * 12, hipMemcpyHostToDevice, h->stream));
+    DedupOut o;
+    rc = dedup_device_core(h, base + o_work, tmp, d_my, d_op, d_pi, d_v, n, &o);
+    if (rc != SYN_OK) return rc;
+    const size_t m = (size_t)o.m;
+    HIP_TRY(h, hipMemcpyAsync(out_my, o.my, m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_op, o.op, m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_pi, o.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_v, o.v, m * 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_num, o.num, m * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out_count = (size_t)m;
+    *out_count = m;
+    return SYN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ device-resident replay buffer
+// (data.rs:107-235 on the device; kernels in replay_kernels.cuh). Everything is ordered on h->stream; the host waits only where a
+// count has to reach it.
+struct ReplaySections {
+    unsigned long long* my;
+    unsigned long long* op;
+    long long* gid;
+    float* pi;
+    float* v;
+};
+static ReplaySections replay_sections(unsigned char* base, size_t cap) {
+    ReplaySections s;
+    s.my = reinterpret_cast<unsigned long long*>(base);
+    s.op = reinterpret_cast<unsigned long long*>(base + cap * 8);
+    s.gid = reinterpret_cast<long long*>(base + cap * 16);
+    s.pi = reinterpret_cast<float*>(base + cap * 24);
+    s.v = reinterpret_cast<float*>(base + cap * 60);
+    return s;
+}
+static ReplaySections replay_tail(const ReplaySections& s, size_t at) {
+    ReplaySections t;
+    t.my = s.my + at;
+    t.op = s.op + at;
+    t.gid = s.gid + at;
+    t.pi = s.pi + at * 9;
+    t.v = s.v + at * 3;
+    return t;
+}
+// n positions from `src` to `dst` (five block copies of the given kind)
+static int replay_copy(syn_engine* h, const ReplaySections& dst, const ReplaySections& src, size_t n, hipMemcpyKind kind) {
+    if (n == 0) return SYN_OK;
+    if (dst.my && src.my) HIP_TRY(h, hipMemcpyAsync(dst.my, src.my, n * 8, kind, h->stream));
+    if (dst.op && src.op) HIP_TRY(h, hipMemcpyAsync(dst.op, src.op, n * 8, kind, h->stream));
+    if (dst.gid && src.gid) HIP_TRY(h, hipMemcpyAsync(dst.gid, src.gid, n * 8, kind, h->stream));
+    if (dst.pi && src.pi) HIP_TRY(h, hipMemcpyAsync(dst.pi, src.pi, n * 36, kind, h->stream));
+    if (dst.v && src.v) HIP_TRY(h, hipMemcpyAsync(dst.v, src.v, n * 12, kind, h->stream));
+    return SYN_OK;
+}
+
+// The last syn_selfplay_run's positions, compacted to `dst` (room for `room` positions): exclusive sum of plies, the total to the
+// host (one synchronise), then one wave per game. Nothing is written when the total does not fit (SYN_ERR_CAPACITY).
+static int replay_compact_last_selfplay(syn_engine* h, long long first_gid, const ReplaySections& dst, size_t room, size_t* n_out) {
+    *n_out = 0;
+    if (h->last_selfplay_games < 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "no syn_selfplay_run has completed on this engine: there are no positions to compact");
+    const int ng = h->last_selfplay_games;
+    if (ng == 0) return SYN_OK;
+    size_t tmp = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const int*)nullptr, (unsigned*)nullptr, ng, h->stream));
+    const size_t off_bytes = ((size_t)ng * 4 + 255) & ~(size_t)255;
+    int rc = ensure_scratch(h, off_bytes + tmp + 256);
+    if (rc != SYN_OK) return rc;
+    unsigned* d_off = static_cast<unsigned*>(h->d_scratch);
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(static_cast<char*>(h->d_scratch) + off_bytes, tmp, h->d_plies, d_off, ng, h->stream));
+    unsigned last_off = 0;
+    int last_plies = 0;
+    HIP_TRY(h, hipMemcpyAsync(&last_off, d_off + (ng - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last_plies, h->d_plies + (ng - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t total = (size_t)last_off + (size_t)(last_plies > 0 ? last_plies : 0);
+    if (total > room)
+        return fail(h, SYN_ERR_CAPACITY, "the last self-play launch has %zu positions, there is room for %zu", total, room);
+    if (total) {
+        hipLaunchKernelGGL(replay_compact_kernel, dim3((unsigned)(((size_t)ng * 64 + 255) / 256)), dim3(256), 0, h->stream, h->d_plies,
+                           d_off, ng, h->d_states, h->d_pis, h->d_vs, first_gid, (unsigned long long)room, dst.my, dst.op, dst.gid,
+                           dst.pi, dst.v);
+        HIP_TRY(h, hipGetLastError());
+    }
+    *n_out = total;
+    return SYN_OK;
+}
+
+int syn_replay_reserve(syn_engine* h, size_t capacity_positions) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (capacity_positions > 0x7FFFFFFFu) return fail(h, SYN_ERR_INVALID_ARGUMENT, "a replay buffer holds at most 2^31 - 1 positions");
+    if (capacity_positions <= h->replay_cap) return SYN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    unsigned char* fresh = nullptr;
+    HIP_TRY(h, hipMalloc(&fresh, capacity_positions * 72));
+    if (h->replay_n) {
+        int rc = replay_copy(h, replay_sections(fresh, capacity_positions), replay_sections(h->d_replay, h->replay_cap), h->replay_n,
+                             hipMemcpyDeviceToDevice);
+        if (rc != SYN_OK) {
+            (void)hipFree(fresh);
+            return rc;
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(h->d_replay);
+    (void)hipFree(h->d_replay_alt);   // (the keep-window's second buffer follows the capacity: allocated again when next needed)
+    h->d_replay = fresh;
+    h->d_replay_alt = nullptr;
+    h->replay_cap = capacity_positions;
+    return SYN_OK;
+}
+
+int syn_replay_clear(syn_engine* h) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));   // (like every entry point of a handle; appends in flight are ordered before later ones by the stream)
+    h->replay_n = 0;
+    return SYN_OK;
+}
+
+int syn_replay_size(syn_engine* h, size_t* n_positions) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!n_positions) return fail(h, SYN_ERR_INVALID_ARGUMENT, "n_positions is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    *n_positions = h->replay_n;
+    return SYN_OK;
+}
+
+int syn_selfplay_positions_device(syn_engine* h, int64_t first_gid, uint64_t* d_my, uint64_t* d_op, int64_t* d_gid, float* d_pi,
+                                  float* d_v, size_t capacity, size_t* n_positions) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!n_positions) return fail(h, SYN_ERR_INVALID_ARGUMENT, "n_positions is NULL");
+    *n_positions = 0;
+    if (capacity && (!d_my || !d_op || !d_gid || !d_pi || !d_v))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_selfplay_positions_device");
+    HIP_TRY(h, hipSetDevice(h->device));
+    ReplaySections dst;
+    dst.my = reinterpret_cast<unsigned long long*>(d_my);
+    dst.op = reinterpret_cast<unsigned long long*>(d_op);
+    dst.gid = reinterpret_cast<long long*>(d_gid);
+    dst.pi = d_pi;
+    dst.v = d_v;
+    int rc = replay_compact_last_selfplay(h, (long long)first_gid, dst, capacity, n_positions);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the sections belong to the caller, who reads them on a stream of their own
+    return SYN_OK;
+}
+
+int syn_replay_append_selfplay(syn_engine* h, int64_t first_gid, size_t* n_appended) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_appended) *n_appended = 0;
+    HIP_TRY(h, hipSetDevice(h->device));
+    size_t n = 0;
+    int rc = replay_compact_last_selfplay(h, (long long)first_gid, replay_tail(replay_sections(h->d_replay, h->replay_cap), h->replay_n),
+                                          h->replay_cap - h->replay_n, &n);
+    if (rc != SYN_OK) return rc;
+    h->replay_n += n;
+    if (n_appended) *n_appended = n;
+    return SYN_OK;
+}
+
+static int replay_append_impl(syn_engine* h, const ReplaySections& src, size_t n, hipMemcpyKind kind) {
+    if (n == 0) return SYN_OK;
+    if (!src.my || !src.op || !src.gid || !src.pi || !src.v) return fail(h, SYN_ERR_INVALID_ARGUMENT, "a section pointer is NULL");
+    if (n > h->replay_cap - h->replay_n)
+        return fail(h, SYN_ERR_CAPACITY, "%zu positions do not fit: the replay buffer holds %zu of %zu (syn_replay_reserve)", n,
+                    h->replay_n, h->replay_cap);
+    int rc = replay_copy(h, replay_tail(replay_sections(h->d_replay, h->replay_cap), h->replay_n), src, n, kind);
+    if (rc != SYN_OK) return rc;
+    if (kind == hipMemcpyHostToDevice) HIP_TRY(h, hipStreamSynchronize(h->stream));   // pageable host memory: the caller may reuse it
+    h->replay_n += n;
+    return SYN_OK;
+}
+
+int syn_replay_append_device(syn_engine* h, const uint64_t* d_my, const uint64_t* d_op, const int64_t* d_gid, const float* d_pi,
+                             const float* d_v, size_t n) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    ReplaySections src;
+    src.my = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d_my));
+    src.op = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d_op));
+    src.gid = reinterpret_cast<long long*>(const_cast<int64_t*>(d_gid));
+    src.pi = const_cast<float*>(d_pi);
+    src.v = const_cast<float*>(d_v);
+    return replay_append_impl(h, src, n, hipMemcpyDeviceToDevice);
+}
+
+int syn_replay_append(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const int64_t* gid, const float* pis, const float* vs,
+                      size_t n) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    ReplaySections src;
+    src.my = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(my_bb));
+    src.op = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(op_bb));
+    src.gid = reinterpret_cast<long long*>(const_cast<int64_t*>(gid));
+    src.pi = const_cast<float*>(pis);
+    src.v = const_cast<float*>(vs);
+    return replay_append_impl(h, src, n, hipMemcpyHostToDevice);
+}
+
+int syn_replay_keep_games_from(syn_engine* h, int64_t min_gid) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    const size_t n = h->replay_n;
+    if (n == 0) return SYN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const int ni = (int)n;
+    size_t tmp = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    const size_t sec = (n * 4 + 255) & ~(size_t)255;
+    int rc = ensure_scratch(h, 2 * sec + tmp + 256);
+    if (rc != SYN_OK) return rc;
+    char* sc = static_cast<char*>(h->d_scratch);
+    unsigned* d_keep = reinterpret_cast<unsigned*>(sc);
+    unsigned* d_dst = reinterpret_cast<unsigned*>(sc + sec);
+    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    hipLaunchKernelGGL(replay_keep_flags_kernel, dim3((ni + 255) / 256), dim3(256), 0, h->stream, cur.gid, ni, (long long)min_gid,
+                       d_keep);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(sc + 2 * sec, tmp, d_keep, d_dst, ni, h->stream));
+    unsigned last[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(&last[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last[1], d_keep + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t kept = (size_t)last[0] + last[1];
+    if (kept == n) return SYN_OK;   // nothing to drop: the buffer stays where it is
+    if (kept == 0) {
+        h->replay_n = 0;
+        return SYN_OK;
+    }
+    // stable scatter into the second buffer, which then becomes the buffer
+    if (!h->d_replay_alt) HIP_TRY(h, hipMalloc(&h->d_replay_alt, h->replay_cap * 72));
+    const ReplaySections alt = replay_sections(h->d_replay_alt, h->replay_cap);
+    auto U = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+    auto W = [](void* p) { return reinterpret_cast<unsigned*>(p); };
+    hipLaunchKernelGGL(replay_keep_scatter_kernel, dim3((unsigned)((n * 9 + 255) / 256), 5), dim3(256), 0, h->stream, d_keep, d_dst, ni,
+                       U(cur.my), U(cur.op), U(cur.gid), U(cur.pi), U(cur.v), W(alt.my), W(alt.op), W(alt.gid), W(alt.pi), W(alt.v));
+    HIP_TRY(h, hipGetLastError());
+    unsigned char* t = h->d_replay;
+    h->d_replay = h->d_replay_alt;
+    h->d_replay_alt = t;
+    h->replay_n = kept;
+    return SYN_OK;
+}
+
+int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gid, float* pis, float* vs, size_t capacity,
+                    size_t* n_positions) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_positions) *n_positions = h->replay_n;
+    if (h->replay_n > capacity)
+        return fail(h, SYN_ERR_CAPACITY, "the replay buffer holds %zu positions, the caller's arrays %zu", h->replay_n, capacity);
+    HIP_TRY(h, hipSetDevice(h->device));
+    ReplaySections dst;
+    dst.my = reinterpret_cast<unsigned long long*>(my_bb);
+    dst.op = reinterpret_cast<unsigned long long*>(op_bb);
+    dst.gid = reinterpret_cast<long long*>(gid);
+    dst.pi = pis;
+    dst.v = vs;
+    int rc = replay_copy(h, dst, replay_sections(h->d_replay, h->replay_cap), h->replay_n, hipMemcpyDeviceToHost);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
+}
+
+int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_unique) *n_unique = 0;
+    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    const size_t n = h->replay_n;
+    if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "the replay buffer is empty");
+    HIP_TRY(h, hipSetDevice(h->device));
+    size_t tmp = 0, work = 0;
+    int rc = dedup_work_bytes(h, n, &tmp, &work);
+    if (rc != SYN_OK) return rc;
+    rc = ensure_scratch(h, work + 256);
+    if (rc != SYN_OK) return rc;
+    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    DedupOut o;
+    rc = dedup_device_core(h, static_cast<char*>(h->d_scratch), tmp, cur.my, cur.op, cur.pi, cur.v, n, &o);
+    if (rc != SYN_OK) return rc;
+    const size_t m = (size_t)o.m;
+    if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n);
+    // the unique set becomes the learner's data set (the state syn_train_set_data leaves): syn_train_epoch stages in d_scratch too,
+    // so it moves to d_train_data before this call returns
+    if (m > h->train_data_cap) {
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_train_data);
+        h->d_train_data = nullptr;
+        h->train_data_cap = 0;
+        h->train_data_n = 0;
+        const size_t want = m + m / 4;   // (the unique count drifts from iteration to iteration: do not reallocate for every rise)
+        HIP_TRY(h, hipMalloc(&h->d_train_data, want * 64));
+        h->train_data_cap = want;
+    }
+    unsigned char* base = static_cast<unsigned char*>(h->d_train_data);
+    HIP_TRY(h, hipMemcpyAsync(base, o.my, m * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(base + m * 8, o.op, m * 8, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(base + m * 16, o.pi, m * 36, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(base + m * 52, o.v, m * 12, hipMemcpyDeviceToDevice, h->stream));
+    h->train_data_n = m;
+    if (n_unique) *n_unique = m;
+    return SYN_OK;
+}
+
+int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity,
+                       size_t* n) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    const size_t m = h->train_data_n;
+    if (n) *n = m;
+    if (m > capacity) return fail(h, SYN_ERR_CAPACITY, "the learner's data set has %zu states, the caller's arrays %zu", m, capacity);
+    if (m == 0) return SYN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const unsigned char* base = static_cast<const unsigned char*>(h->d_train_data);
+    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, base, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, base + m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, base + m * 16, m * 36, hipMemcpyDeviceToHost, h->stream));
+    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, base + m * 52, m * 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
 

@@ -23,6 +23,9 @@ ABI_SYMBOLS = [
     "syn_conv2d_forward", "syn_activation_forward", "syn_mcts_search", "syn_mcts_search_rollout", "syn_mcts_search_lockstep", "syn_selfplay_run_lockstep", "syn_frozen_search_rollout", "syn_selfplay_run", "syn_progress", "syn_cancel", "syn_trainer_set_precision", "syn_last_timing", "syn_last_launch_shape", "syn_last_cache_stats", "syn_debug_stdrng_u32",
     "syn_debug_math", "syn_debug_fast_div", "syn_debug_small_int_math", "syn_debug_calibrate", "syn_trainer_init", "syn_trainer_init_conv", "syn_train_step", "syn_train_gradients_device",
     "syn_train_apply_device", "syn_train_gradients_enqueue", "syn_train_apply_enqueue", "syn_trainer_get_state", "syn_trainer_publish_weights", "syn_replay_deduplicate", "syn_train_set_data", "syn_train_epoch",
+    "syn_replay_reserve", "syn_replay_clear", "syn_replay_size", "syn_selfplay_positions_device", "syn_replay_append_selfplay",
+    "syn_replay_append_device", "syn_replay_append", "syn_replay_keep_games_from", "syn_replay_read",
+    "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
 ]
 
 
@@ -162,6 +165,17 @@ def load_library():
     lib.syn_replay_deduplicate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_size_t)]
+    lib.syn_replay_reserve.argtypes = [C.c_void_p, C.c_size_t]
+    lib.syn_replay_clear.argtypes = [C.c_void_p]
+    lib.syn_replay_size.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    lib.syn_selfplay_positions_device.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.syn_replay_append_selfplay.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_size_t)]
+    lib.syn_replay_append_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_size_t]
+    lib.syn_replay_append.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_size_t]
+    lib.syn_replay_keep_games_from.argtypes = [C.c_void_p, C.c_int64]
+    lib.syn_replay_read.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.syn_replay_deduplicate_to_trainer.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
+    lib.syn_train_get_data.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 
@@ -632,6 +646,79 @@ class Engine:
                                                      _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), _p(o["num"]),
                                                      C.byref(cnt)))
         return {k: a[: cnt.value] for k, a in o.items()}
+
+    # ---- the replay buffer in device memory (data.rs:107-235; include/synthesis_amd.h syn_replay_*)
+    def replay_reserve(self, capacity_positions):
+        """Allocates the engine's buffer for that many positions (72 bytes each), or grows it keeping the contents."""
+        self._check(self._lib.syn_replay_reserve(self._h, int(capacity_positions)))
+
+    def replay_clear(self):
+        self._check(self._lib.syn_replay_clear(self._h))
+
+    def replay_size(self):
+        n = C.c_size_t()
+        self._check(self._lib.syn_replay_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def selfplay_positions_device(self, first_gid, d_my, d_op, d_gid, d_pi, d_v, capacity):
+        """The last selfplay()'s positions compacted into caller-owned device sections (ints = raw device addresses, e.g. torch tensor
+        .data_ptr(); room for `capacity` positions each): game order, then ply order, gid = first_gid + game slot. Returns their number."""
+        n = C.c_size_t()
+        self._check(self._lib.syn_selfplay_positions_device(self._h, int(first_gid), C.c_void_p(d_my), C.c_void_p(d_op), C.c_void_p(d_gid),
+                                                            C.c_void_p(d_pi), C.c_void_p(d_v), int(capacity), C.byref(n)))
+        return int(n.value)
+
+    def replay_append_selfplay(self, first_gid):
+        """The last selfplay()'s positions onto the tail of the buffer (no padded download: selfplay(..., outputs=False) is enough)."""
+        n = C.c_size_t()
+        self._check(self._lib.syn_replay_append_selfplay(self._h, int(first_gid), C.byref(n)))
+        return int(n.value)
+
+    def replay_append(self, my_bb, op_bb, gid, pis, vs):
+        """Positions from host arrays (other ranks' games under a host transport, a caller's own) onto the tail."""
+        my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(op_bb, dtype=np.uint64).ravel()
+        g = np.ascontiguousarray(gid, dtype=np.int64).ravel()
+        n = int(my.size)
+        if op.size != n or g.size != n:
+            raise ValueError("my_bb, op_bb and gid must have the same length")
+        pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, 9)
+        vs = np.ascontiguousarray(vs, dtype=np.float32).reshape(n, 3)
+        self._check(self._lib.syn_replay_append(self._h, _p(my), _p(op), _p(g), _p(pis), _p(vs), n))
+
+    def replay_append_device(self, d_my, d_op, d_gid, d_pi, d_v, n):
+        """n positions from device sections (raw addresses; their producer's stream must have been synchronised) onto the tail."""
+        self._check(self._lib.syn_replay_append_device(self._h, C.c_void_p(d_my), C.c_void_p(d_op), C.c_void_p(d_gid), C.c_void_p(d_pi),
+                                                       C.c_void_p(d_v), int(n)))
+
+    def replay_keep_games_from(self, min_gid):
+        """keep_last_n_games (data.rs:160-194): drops every position of a game before min_gid, keeps the order of the rest."""
+        self._check(self._lib.syn_replay_keep_games_from(self._h, int(min_gid)))
+
+    def replay_read(self):
+        """The buffer as host arrays: dict(my, op, gid, pi [n, 9], v [n, 3]) in buffer order."""
+        n = self.replay_size()
+        o = dict(my=np.zeros(n, np.uint64), op=np.zeros(n, np.uint64), gid=np.zeros(n, np.int64), pi=np.zeros((n, 9), np.float32),
+                 v=np.zeros((n, 3), np.float32))
+        got = C.c_size_t()
+        self._check(self._lib.syn_replay_read(self._h, _p(o["my"]), _p(o["op"]), _p(o["gid"]), _p(o["pi"]), _p(o["v"]), n, C.byref(got)))
+        return o
+
+    def replay_deduplicate_to_trainer(self):
+        """De-duplicates the buffer on the device and makes the unique set the learner's data set (what replay_deduplicate +
+        train_set_data leave, without the host copies). Returns the number of unique states."""
+        n = C.c_size_t()
+        self._check(self._lib.syn_replay_deduplicate_to_trainer(self._h, C.byref(n)))
+        return int(n.value)
+
+    def train_get_data(self):
+        """The learner's current data set as host arrays: dict(my_bb, op_bb, pis [n, 9], vs [n, 3]) — replay_deduplicate's keys."""
+        n = C.c_size_t()
+        self._check(self._lib.syn_train_get_data(self._h, None, None, None, None, 1 << 62, C.byref(n)))
+        n = int(n.value)
+        o = dict(my_bb=np.zeros(n, np.uint64), op_bb=np.zeros(n, np.uint64), pis=np.zeros((n, 9), np.float32), vs=np.zeros((n, 3), np.float32))
+        self._check(self._lib.syn_train_get_data(self._h, _p(o["my_bb"]), _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), n, None))
+        return o
 
     # ---- parity probes
     def debug_stdrng_u32(self, seed, n):

@@ -52,13 +52,17 @@ class LearningLoop:
                  from that same global generator before the first randperm, so the permutations of a Rust run differ
     network_arithmetic  "f32" (default) | "f16x2": the arithmetic this rank's engine evaluates the network in during self-play
                  (include/synthesis_amd.h syn_set_network_arithmetic; both networks). The learner itself trains in `precision`.
+    replay       "host" (default: the replay buffer is a dict of numpy arrays on the learner's rank; self-play downloads its padded
+                 outputs) | "device": the buffer lives in the engine's device memory (Engine.replay_*; data.rs:107-235 on the GPU) —
+                 self-play downloads only `plies`, the positions are compacted on the device, trimmed to the last games_to_keep games
+                 and de-duplicated straight into the learner's data set. Same games, same buffer order, same bits as "host".
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", **hyper):
+                 network_arithmetic="f32", replay="host", **hyper):
         import torch
 
         self._torch = torch
@@ -91,6 +95,11 @@ class LearningLoop:
         self.iterations_done = 0
         if sampler not in ("numpy", "torch"):
             raise ValueError(f"sampler must be 'numpy' or 'torch', got {sampler!r}")
+        if replay not in ("host", "device"):
+            raise ValueError(f"replay must be 'host' or 'device', got {replay!r}")
+        self.replay = replay
+        self._device = int(device)
+        self._replay_reserved = 0
         self.sampler = sampler
         self._torch_gen = torch.Generator().manual_seed(self.seed) if sampler == "torch" else None
         self.logs_dir = logs_dir if self.rank == 0 else None
@@ -162,8 +171,144 @@ class LearningLoop:
                 off += cap * np.dtype(dt).itemsize * width
         return {k: np.concatenate(v) for k, v in out.items()}
 
+    def _sections(self, base, cap):
+        """Addresses of the five `_FIELDS` sections of a gather buffer of `cap` positions that starts at `base`"""
+        out, off = [], 0
+        for _, dt, width in self._FIELDS:
+            out.append(base + off)
+            off += cap * np.dtype(dt).itemsize * width
+        return out
+
+    def _gather_positions_device(self, n, first):
+        """replay="device" with several ranks: the same wire format as `_gather_positions` (counts, then one fixed-layout buffer per rank),
+        but a rank's buffer is filled on the device — Engine.selfplay_positions_device compacts the last launch into its sections — and
+        the learner's rank appends the parts to the engine's buffer in rank order: straight from the gathered device tensors under RCCL,
+        from the gathered host tensors (a download of the compact 72 B/position form on every rank) under gloo. The learner's own part
+        never leaves its engine."""
+        t = self._torch
+        on_gpu = self._wbuf.is_cuda
+        cnt = t.tensor([n], dtype=t.int64, device=self._wbuf.device)
+        counts = [t.zeros(1, dtype=t.int64, device=self._wbuf.device) for _ in range(self.world)]
+        t_w = time.perf_counter()
+        self.dist.all_gather(counts, cnt)
+        counts = [int(c.item()) for c in counts]
+        self._last_gather_wait = time.perf_counter() - t_w
+        cap = (max(max(counts), 1) + 32767) // 32768 * 32768
+        if getattr(self, "_gcap", 0) != cap:
+            self._gcap = cap
+            self._gdev = t.empty(cap * self._POS_BYTES, dtype=t.uint8, device=t.device(f"cuda:{self._device}"))
+            self._ghost = None if on_gpu else t.zeros(cap * self._POS_BYTES, dtype=t.uint8)
+            like = self._gdev if on_gpu else self._ghost
+            self._gparts = [t.zeros_like(like) for _ in range(self.world)] if self.rank == 0 else None
+        if self.rank == 0:
+            assert self.engine.replay_append_selfplay(first) == n
+        else:
+            got = self.engine.selfplay_positions_device(first, *self._sections(self._gdev.data_ptr(), cap), cap)
+            assert got == n, (got, n)
+        mine = self._gdev
+        if not on_gpu:
+            if self.rank != 0:
+                self._ghost.copy_(self._gdev)
+            mine = self._ghost
+        self.dist.gather(mine, self._gparts, dst=0)
+        if self.rank != 0:
+            return
+        if on_gpu:
+            t.cuda.synchronize(self._gdev.device)   # the parts were written on torch's stream, the appends run on the engine's
+        for r in range(1, self.world):
+            c, part = counts[r], self._gparts[r]
+            if c == 0:
+                continue
+            if on_gpu:
+                self.engine.replay_append_device(*self._sections(part.data_ptr(), cap), c)
+            else:
+                raw, off, secs = part.numpy(), 0, []
+                for _, dt, width in self._FIELDS:
+                    secs.append(raw[off: off + cap * np.dtype(dt).itemsize * width].view(dt)[: c * width])
+                    off += cap * np.dtype(dt).itemsize * width
+                self.engine.replay_append(*secs)
+
+    def _iteration_device(self, cfg, games_per_train, games_to_keep, epochs, batch_size):
+        """`iteration` with the replay buffer in the engine's device memory (replay="device"): same games, same record."""
+        it = self.iterations_done
+        t0 = time.perf_counter()
+        off, count = shard_games(games_per_train, self.rank, self.world)
+        first = it * games_per_train + off
+        if self.rank == 0:   # (grows, keeping the contents, when an iteration's shape changes)
+            want = (int(games_to_keep) + int(games_per_train)) * 63
+            if want > self._replay_reserved:
+                self.engine.replay_reserve(want)
+                self._replay_reserved = want
+        sp = self.engine.selfplay(cfg, base_seed=self.seed, n_games=count, first_game=first, outputs=False)
+        t_play = time.perf_counter() - t0
+        n = sp["plies"]
+        t1 = time.perf_counter()
+        self._last_gather_wait = 0.0
+        if self.dist is not None:
+            self._gather_positions_device(int(n.sum()), first)
+        else:
+            self.engine.replay_append_selfplay(first)
+        t_gather = time.perf_counter() - t1 - self._last_gather_wait
+        self.games_played += games_per_train
+        lr = _lr_at(self.lr_schedule, it)
+        rec = dict(iteration=it + 1, lr=lr, games=int(games_per_train), games_this_rank=int(count),
+                   plies_per_game=float(n.mean()) if count else 0.0)
+        t_dedup = t_train = 0.0
+        if self.rank == 0:
+            self.engine.replay_keep_games_from(self.games_played - games_to_keep)   # keep_last_n_games (data.rs:160-194)
+            steps_in_buffer = self.engine.replay_size()
+            # ---- deduplicate into the learner's data set (data.rs:196-235 + alpha_zero.rs:52-58), all on the device
+            t2 = time.perf_counter()
+            n_unique = self.engine.replay_deduplicate_to_trainer()
+            t_dedup = time.perf_counter() - t2
+            t3 = time.perf_counter()
+            steps, epoch_losses = 0, []
+            n_steps = n_unique // batch_size
+            for ep in range(epochs):
+                if self.sampler == "torch":
+                    perm = self._torch.randperm(n_unique, generator=self._torch_gen, dtype=self._torch.int64).numpy()
+                else:
+                    perm = np.random.default_rng([self.seed, it, ep]).permutation(n_unique)
+                if n_steps:
+                    sl = self.engine.train_epoch(perm[: n_steps * batch_size], batch_size, lr)
+                    epoch_losses.append((sl.astype(np.float64).sum(axis=0) * batch_size / n_unique).tolist())
+                steps += n_steps
+            t_train = time.perf_counter() - t3
+            self.weights = self.engine.trainer_state()["weights"]
+            rec.update(steps_in_buffer=steps_in_buffer, unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
+            if self.logs_dir:
+                import os
+
+                D = self.engine.train_get_data()
+                self._save_model(it + 1)
+                np.save(os.path.join(self.logs_dir, "latest_states.npy"),
+                        np.asarray(self.engine.features(D["my_bb"], D["op_bb"]), np.float32).reshape(-1, 1, 7, 9))
+                np.save(os.path.join(self.logs_dir, "latest_pis.npy"), D["pis"])
+                np.save(os.path.join(self.logs_dir, "latest_vs.npy"), D["vs"])
+        self._finish_iteration(rec, t0, t_play, t_gather, t_dedup, t_train)
+        return rec
+
+    def _finish_iteration(self, rec, t0, t_play, t_gather, t_dedup, t_train):
+        """model_{i+1} (alpha_zero.rs:97,194): the trained parameters become every rank's self-play network; the record's timings"""
+        t4 = time.perf_counter()
+        if self.dist is not None:
+            if self.rank == 0:
+                self._wbuf.copy_(self._torch.from_numpy(self.weights))
+            self.dist.broadcast(self._wbuf, src=0)
+            self.weights = self._wbuf.cpu().numpy().copy()
+            self._load(self.weights)
+        elif self.rank == 0:
+            self.engine.trainer_publish_weights()
+        t_bcast = time.perf_counter() - t4
+        self.iterations_done += 1
+        rec["seconds"] = dict(selfplay=round(t_play, 4), wait_for_ranks=round(self._last_gather_wait, 4), gather=round(t_gather, 4),
+                              dedup=round(t_dedup, 4), train=round(t_train, 4),
+                              broadcast=round(t_bcast, 4), total=round(time.perf_counter() - t0, 4))
+
     def iteration(self, cfg, games_per_train, games_to_keep, epochs, batch_size):
         """One pass of the loop body (alpha_zero.rs:42-100). Returns this rank's record of it (rank 0's has the learner's numbers)."""
+        if self.replay == "device":
+            return self._iteration_device(cfg, games_per_train, games_to_keep, epochs, batch_size)
         it = self.iterations_done
         t0 = time.perf_counter()
         # ---- gather_experience: this rank's share of the new games; global game index = seed offset, never reused
