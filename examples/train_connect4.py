@@ -75,6 +75,9 @@ def main():
     ap.add_argument("--replay", default="host", choices=["host", "device"], help="where the learning loop's replay buffer lives: host = "
                     "numpy arrays on rank 0 (self-play downloads its padded outputs); device = the engine's device memory (compaction, "
                     "keep-window and de-duplication on the GPU, same bits); learning loop only")
+    ap.add_argument("--symmetry", default="none", choices=["none", "mirror"], help="mirror = the de-duplication merges a position with "
+                    "its left-right mirror image and hands the learner both orientations (up to twice the data set per epoch; self-play "
+                    "and the network are unchanged)")
     args = ap.parse_args()
     if args.replay != "host" and args.data_parallel:
         raise SystemExit("--replay device belongs to the learning loop: --data-parallel keeps one replay buffer per rank on the host")
@@ -117,7 +120,7 @@ def main():
     else:
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
-                            network_arithmetic=args.network_arithmetic, replay=args.replay, **hyper)
+                            network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):
@@ -150,7 +153,7 @@ def main():
             R = {k: a[keep] for k, a in R.items()}
             # ---- deduplicate on the GPU (data.rs:196-235)
             t1 = time.perf_counter()
-            D = eng.replay_deduplicate(R["my"], R["op"], R["pi"], R["v"])
+            D = eng.replay_deduplicate(R["my"], R["op"], R["pi"], R["v"], symmetry=args.symmetry)
             t_dedup = time.perf_counter() - t1
             n_unique = D["num"].size
             lr = lr_at(lr_schedule, it)

@@ -482,6 +482,27 @@ int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique);
 int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity,
                        size_t* n);
 
+/* ---- Mirror symmetry of the 9x7 board (DESIGN.md "Mirror-symmetric de-duplication"; not in the reference). Bit index of a bitboard =
+ * row + 7 * col; mirror moves bit [row, col] to [row, 8 - col] and leaves bit 63 alone; reverse: pi[c] -> pi[8 - c]; v is unchanged.
+ * A record [my, op, pi, v] is FLIPPED when the pair [mirror my, mirror op] is strictly smaller than [my, op] as unsigned 64-bit
+ * numbers, my first; its canonical form is then [mirror my, mirror op, reverse pi, v], otherwise it is the record itself.
+ *
+ * syn_positions_mirror: the mirroring kernel on its own, host arrays in and out: out_my[i] = mirror of my_bb[i], likewise op, and
+ * out_pi[i][c] = pis[i][8 - c]. pis and out_pi may both be NULL (boards only). */
+int syn_positions_mirror(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis /*may be NULL*/, size_t n,
+                         uint64_t* out_my, uint64_t* out_op, float* out_pi /*may be NULL*/);
+/* syn_replay_deduplicate over the canonical forms, closed under mirroring: rows [0, U) are the unique canonical states in ascending
+ * order with their targets summed over the class in buffer order (a flipped member contributes its reversed pi) and divided by the
+ * count; rows [U, U+M) are the mirror images of those classes whose state is not its own mirror image, in the same order, with
+ * the reversed averaged pi and the same v and num. Outputs are sized for 2n rows; *out_canonical = U, *out_count = U + M. The sort
+ * runs over n keys. n is at most 2^30 - 1. */
+int syn_replay_deduplicate_symmetric(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis, const float* vs,
+                                     size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v, uint32_t* out_num,
+                                     size_t* out_canonical, size_t* out_count);
+/* syn_replay_deduplicate_to_trainer in that form: the U + M rows become the learner's data set, the buffer itself is unchanged.
+ * *n_canonical = U, *n_total = U + M, either may be NULL. Same error codes. */
+int syn_replay_deduplicate_to_trainer_symmetric(syn_engine* h, size_t* n_canonical, size_t* n_total);
+
 /* Timing of the last syn_selfplay_run / syn_mcts_search / *_device call on this handle, measured with HIP events on
  * the engine stream: kernel_ms = device time of the dominant kernel launch(es), n_launches = how many. */
 int syn_last_timing(const syn_engine* h, float* kernel_ms, int* n_launches);

@@ -296,6 +296,10 @@ private:
 };
 
 // ---- ReplayBuffer (data.rs:107-235) --------------------------------------------------------------------------------------
+// What deduplicate does with the board's left-right symmetry (not in the reference; include/synthesis_amd.h, "Mirror symmetry"):
+// None = today's de-duplication; Mirror = a position and its mirror image are one class, and the output is closed under mirroring.
+enum class Symmetry { None, Mirror };
+
 struct FlatBatch {
     std::vector<Connect4> games;
     std::vector<std::array<float, 63>> states;
@@ -345,19 +349,29 @@ public:
         vs.erase(vs.begin(), vs.begin() + (long)drop);
     }
     // average the targets of identical states — on the GPU (sort + segmented reduce, sums in buffer order); output in
-    // ascending (my_bb, op_bb) order (the reference's HashMap order is unspecified)
-    FlatBatch deduplicate(Engine& e) const {
-        const size_t n = games.size();
-        std::vector<uint64_t> my(n), op(n), umy(n), uop(n);
+    // ascending (my_bb, op_bb) order (the reference's HashMap order is unspecified). Symmetry::Mirror: the canonical states first
+    // (*n_canonical of them, if asked for), then the mirror images of those that are not self-symmetric — up to 2n entries.
+    FlatBatch deduplicate(Engine& e, Symmetry symmetry = Symmetry::None, size_t* n_canonical = nullptr) const {
+        const size_t n = games.size(), rows = symmetry == Symmetry::Mirror ? 2 * n : n;
+        std::vector<uint64_t> my(n), op(n), umy(rows), uop(rows);
         for (size_t i = 0; i < n; i++) { my[i] = games[i].my_bb(); op[i] = games[i].op_bb(); }
         FlatBatch out;
-        out.pis.resize(n);
-        out.vs.resize(n);
-        std::vector<uint32_t> num(n);
-        size_t count = 0;
-        e.check(syn_replay_deduplicate(e.handle(), my.data(), op.data(), n ? pis[0].data() : nullptr,
-                                       n ? vs[0].data() : nullptr, n, umy.data(), uop.data(),
-                                       n ? out.pis[0].data() : nullptr, n ? out.vs[0].data() : nullptr, num.data(), &count));
+        out.pis.resize(rows);
+        out.vs.resize(rows);
+        std::vector<uint32_t> num(rows);
+        size_t count = 0, canonical = 0;
+        if (symmetry == Symmetry::Mirror) {
+            e.check(syn_replay_deduplicate_symmetric(e.handle(), my.data(), op.data(), n ? pis[0].data() : nullptr,
+                                                     n ? vs[0].data() : nullptr, n, umy.data(), uop.data(),
+                                                     n ? out.pis[0].data() : nullptr, n ? out.vs[0].data() : nullptr, num.data(),
+                                                     &canonical, &count));
+        } else {
+            e.check(syn_replay_deduplicate(e.handle(), my.data(), op.data(), n ? pis[0].data() : nullptr,
+                                           n ? vs[0].data() : nullptr, n, umy.data(), uop.data(),
+                                           n ? out.pis[0].data() : nullptr, n ? out.vs[0].data() : nullptr, num.data(), &count));
+            canonical = count;
+        }
+        if (n_canonical) *n_canonical = canonical;
         out.pis.resize(count);
         out.vs.resize(count);
         for (size_t i = 0; i < count; i++) {
@@ -408,10 +422,17 @@ public:
         e_.check(syn_replay_keep_games_from(e_.handle(), (int64_t)(game_id_ - n)));
     }
     // deduplicate (data.rs:196-235) straight into the learner of this engine (Learner / syn_trainer_init first); returns the number
-    // of unique states syn_train_epoch then indexes
-    size_t deduplicate_to_trainer() {
-        size_t m = 0;
-        e_.check(syn_replay_deduplicate_to_trainer(e_.handle(), &m));
+    // of unique states syn_train_epoch then indexes. Symmetry::Mirror: the canonical states and their mirror images (the return value
+    // counts both; *n_canonical, if asked for, the canonical ones).
+    size_t deduplicate_to_trainer(Symmetry symmetry = Symmetry::None, size_t* n_canonical = nullptr) {
+        size_t m = 0, u = 0;
+        if (symmetry == Symmetry::Mirror) {
+            e_.check(syn_replay_deduplicate_to_trainer_symmetric(e_.handle(), &u, &m));
+        } else {
+            e_.check(syn_replay_deduplicate_to_trainer(e_.handle(), &m));
+            u = m;
+        }
+        if (n_canonical) *n_canonical = u;
         return m;
     }
 

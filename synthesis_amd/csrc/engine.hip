@@ -2717,10 +2717,11 @@ struct DedupOut {
     float* pi = nullptr;
     float* v = nullptr;
     unsigned* num = nullptr;
-    int m = 0;
+    int m = 0;       // unique (with mirror: canonical) states, rows [0, m)
+    int total = 0;   // rows in all: m, with mirror m + the mirror images of the classes that are not self-symmetric
 };
 static size_t dedup_align(size_t x) { return (x + 255) & ~(size_t)255; }
-static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total) {
+static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total, bool mirror = false) {
     const int ni = (int)n;
     size_t tmp_sort = 0, tmp_scan = 0;
     HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const unsigned long long*)nullptr,
@@ -2732,22 +2733,44 @@ static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* 
     // sort keys/values (double buffers) | heads | scan | seg_start | outputs | cub temp
     *total = 2 * dedup_align(n * 8) + 2 * dedup_align(n * 4) + 3 * dedup_align(n * 4) + 2 * dedup_align(n * 8) + dedup_align(n * 36) +
              dedup_align(n * 12) + dedup_align(n * 4) + dedup_align(*tmp_bytes);
+    if (mirror) {
+        // the symmetric form (replay_kernels.cuh): outputs of 2n rows instead of n | canonical keys | flip | expand flags | their scan
+        size_t tmp_excl = 0;
+        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_excl, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+        if (tmp_excl > *tmp_bytes) *tmp_bytes = tmp_excl;
+        const size_t r = 2 * n;
+        *total = 2 * dedup_align(n * 8) + 2 * dedup_align(n * 4) + 3 * dedup_align(n * 4) + 2 * dedup_align(r * 8) + dedup_align(r * 36) +
+                 dedup_align(r * 12) + dedup_align(r * 4) + dedup_align(*tmp_bytes) + 2 * dedup_align(n * 8) + 3 * dedup_align(n * 4);
+    }
     return SYN_OK;
 }
 static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsigned long long* d_my, const unsigned long long* d_op,
-                             const float* d_pi, const float* d_v, size_t n, DedupOut* out) {
+                             const float* d_pi, const float* d_v, size_t n, DedupOut* out, bool mirror = false) {
     const int ni = (int)n;
+    const size_t rows = mirror ? 2 * n : n;   // (dedup_work_bytes' layout)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
     size_t o_k0 = take(n * 8), o_k1 = take(n * 8), o_i0 = take(n * 4), o_i1 = take(n * 4);
     size_t o_head = take(n * 4), o_scan = take(n * 4), o_start = take(n * 4);
-    size_t o_omy = take(n * 8), o_oop = take(n * 8), o_opi = take(n * 36), o_ov = take(n * 12), o_on = take(n * 4);
+    size_t o_omy = take(rows * 8), o_oop = take(rows * 8), o_opi = take(rows * 36), o_ov = take(rows * 12), o_on = take(rows * 4);
     size_t o_tmp = take(tmp);
+    size_t o_cmy = 0, o_cop = 0, o_flip = 0, o_exp = 0, o_dst = 0;
+    if (mirror) { o_cmy = take(n * 8); o_cop = take(n * 8); o_flip = take(n * 4); o_exp = take(n * 4); o_dst = take(n * 4); }
     char* base = work;
     auto P8 = [&](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     auto P4 = [&](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
     auto PF = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
     const int blocks = (ni + 255) / 256;
+    const unsigned long long* in_my = d_my;
+    const unsigned long long* in_op = d_op;
+    if (mirror) {
+        // symmetric: every record in its canonical orientation first, so that the sort still runs over n keys; from here on the
+        // keys are the canonical boards and the records' own boards are not read again
+        hipLaunchKernelGGL(replay_canonicalise_kernel, dim3(blocks), dim3(256), 0, h->stream, in_my, in_op, ni, P8(o_cmy), P8(o_cop),
+                           P4(o_flip));
+        d_my = P8(o_cmy);
+        d_op = P8(o_cop);
+    }
     // stable LSD sort of the buffer indices by the 128-bit key: first by op_bb, then by my_bb
     hipLaunchKernelGGL(iota_kernel, dim3(blocks), dim3(256), 0, h->stream, P4(o_i0), ni);
     size_t t1 = tmp;
@@ -2768,31 +2791,58 @@ static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsign
     HIP_TRY(h, hipMemcpyAsync(&m_u, P4(o_scan) + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     const int m = (int)m_u;
-    hipLaunchKernelGGL(dedup_reduce_kernel, dim3((m * 16 + 255) / 256), dim3(256), 0, h->stream, P4(o_i0), P4(o_start),
-                       m, ni, d_my, d_op, d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
-    HIP_TRY(h, hipGetLastError());
+    int total = m;
+    if (!mirror) {
+        hipLaunchKernelGGL(dedup_reduce_kernel, dim3((m * 16 + 255) / 256), dim3(256), 0, h->stream, P4(o_i0), P4(o_start),
+                           m, ni, d_my, d_op, d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
+        HIP_TRY(h, hipGetLastError());
+    } else if (m > 0) {
+        const dim3 rows16((unsigned)(((size_t)m * 16 + 255) / 256));
+        hipLaunchKernelGGL(dedup_reduce_mirror_kernel, rows16, dim3(256), 0, h->stream, P4(o_i0), P4(o_start), m, ni, d_my, d_op,
+                           P4(o_flip), d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on), P4(o_exp));
+        HIP_TRY(h, hipGetLastError());
+        // rows [m, m + M): the mirror images of the classes that are not self-symmetric, in class order
+        t1 = tmp;
+        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, t1, P4(o_exp), P4(o_dst), m, h->stream));
+        unsigned last[2] = {0, 0};
+        HIP_TRY(h, hipMemcpyAsync(&last[0], P4(o_dst) + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(&last[1], P4(o_exp) + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        const size_t extra = (size_t)last[0] + last[1];
+        if (extra > (size_t)m) return fail(h, SYN_ERR_HIP, "%zu mirror images for %d canonical states", extra, m);
+        hipLaunchKernelGGL(dedup_expand_mirror_kernel, rows16, dim3(256), 0, h->stream, P4(o_exp), P4(o_dst), m, rows, P8(o_omy),
+                           P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
+        HIP_TRY(h, hipGetLastError());
+        total = m + (int)extra;
+    }
     out->my = P8(o_omy);
     out->op = P8(o_oop);
     out->pi = PF(o_opi);
     out->v = PF(o_ov);
     out->num = P4(o_on);
     out->m = m;
+    out->total = total;
     return SYN_OK;
 }
 
-int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis,
-                           const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v,
-                           uint32_t* out_num, size_t* out_count) {
+// the rows of the symmetric forms are counted in an int like the plain ones: 2n must fit
+constexpr size_t DEDUP_MIRROR_MAX_N = 0x3FFFFFFFu;
+
+// (the entry points have selected the engine's device)
+static int replay_deduplicate_host(syn_engine* h, const char* who, bool mirror, const uint64_t* my_bb, const uint64_t* op_bb,
+                                   const float* pis, const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi,
+                                   float* out_v, uint32_t* out_num, size_t* out_canonical, size_t* out_count) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (!out_count) return fail(h, SYN_ERR_INVALID_ARGUMENT, "out_count is NULL");
     *out_count = 0;
+    if (out_canonical) *out_canonical = 0;
     if (n == 0) return SYN_OK;
-    if (!my_bb || !op_bb || !pis || !vs || !out_my || !out_op || !out_pi || !out_v || !out_num || n > 0x7FFFFFFFu)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_replay_deduplicate");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (!my_bb || !op_bb || !pis || !vs || !out_my || !out_op || !out_pi || !out_v || !out_num ||
+        n > (mirror ? DEDUP_MIRROR_MAX_N : (size_t)0x7FFFFFFFu))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to %s", who);
     // device layout: inputs | the core's work area
     size_t tmp = 0, work = 0;
-    int rc = dedup_work_bytes(h, n, &tmp, &work);
+    int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
     if (rc != SYN_OK) return rc;
     const size_t o_my = 0, o_op = o_my + dedup_align(n * 8), o_pi = o_op + dedup_align(n * 8), o_v = o_pi + dedup_align(n * 36);
     const size_t o_work = o_v + dedup_align(n * 12);
@@ -2808,9 +2858,9 @@ int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t*
     HIP_TRY(h, hipMemcpyAsync(d_pi, pis, n * 36, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(d_v, vs, n * 12, hipMemcpyHostToDevice, h->stream));
     DedupOut o;
-    rc = dedup_device_core(h, base + o_work, tmp, d_my, d_op, d_pi, d_v, n, &o);
+    rc = dedup_device_core(h, base + o_work, tmp, d_my, d_op, d_pi, d_v, n, &o, mirror);
     if (rc != SYN_OK) return rc;
-    const size_t m = (size_t)o.m;
+    const size_t m = (size_t)o.total;
     HIP_TRY(h, hipMemcpyAsync(out_my, o.my, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(out_op, o.op, m * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(out_pi, o.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
@@ -2818,6 +2868,58 @@ int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t*
     HIP_TRY(h, hipMemcpyAsync(out_num, o.num, m * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *out_count = m;
+    if (out_canonical) *out_canonical = (size_t)o.m;
+    return SYN_OK;
+}
+
+int syn_replay_deduplicate(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis,
+                           const float* vs, size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v,
+                           uint32_t* out_num, size_t* out_count) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return replay_deduplicate_host(h, "syn_replay_deduplicate", false, my_bb, op_bb, pis, vs, n, out_my, out_op, out_pi, out_v, out_num,
+                                   nullptr, out_count);
+}
+
+int syn_replay_deduplicate_symmetric(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis, const float* vs,
+                                     size_t n, uint64_t* out_my, uint64_t* out_op, float* out_pi, float* out_v, uint32_t* out_num,
+                                     size_t* out_canonical, size_t* out_count) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!out_canonical) return fail(h, SYN_ERR_INVALID_ARGUMENT, "out_canonical is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return replay_deduplicate_host(h, "syn_replay_deduplicate_symmetric", true, my_bb, op_bb, pis, vs, n, out_my, out_op, out_pi, out_v,
+                                   out_num, out_canonical, out_count);
+}
+
+int syn_positions_mirror(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* pis, size_t n, uint64_t* out_my,
+                         uint64_t* out_op, float* out_pi) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n == 0) return SYN_OK;
+    if (!my_bb || !op_bb || !out_my || !out_op || (pis != nullptr) != (out_pi != nullptr) || n > 0x7FFFFFFFu)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_positions_mirror");
+    HIP_TRY(h, hipSetDevice(h->device));
+    // device layout: my | op | pi | mirrored my | op | pi
+    const size_t s8 = dedup_align(n * 8), s36 = pis ? dedup_align(n * 36) : 0;
+    int rc = ensure_scratch(h, 4 * s8 + 2 * s36 + 256);
+    if (rc != SYN_OK) return rc;
+    char* base = static_cast<char*>(h->d_scratch);
+    unsigned long long* d_my = reinterpret_cast<unsigned long long*>(base);
+    unsigned long long* d_op = reinterpret_cast<unsigned long long*>(base + s8);
+    float* d_pi = pis ? reinterpret_cast<float*>(base + 2 * s8) : nullptr;
+    unsigned long long* d_omy = reinterpret_cast<unsigned long long*>(base + 2 * s8 + s36);
+    unsigned long long* d_oop = reinterpret_cast<unsigned long long*>(base + 3 * s8 + s36);
+    float* d_opi = pis ? reinterpret_cast<float*>(base + 4 * s8 + s36) : nullptr;
+    HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
+    if (pis) HIP_TRY(h, hipMemcpyAsync(d_pi, pis, n * 36, hipMemcpyHostToDevice, h->stream));
+    const size_t threads = pis ? n * 9 : n;
+    hipLaunchKernelGGL(replay_mirror_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, d_my, d_op, d_pi, (int)n,
+                       d_omy, d_oop, d_opi);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out_my, d_omy, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(out_op, d_oop, n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (pis) HIP_TRY(h, hipMemcpyAsync(out_pi, d_opi, n * 36, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
 
@@ -3067,23 +3169,26 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
     return SYN_OK;
 }
 
-int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique) {
+// (the entry points have selected the engine's device)
+static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_canonical, size_t* n_unique) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (n_unique) *n_unique = 0;
+    if (n_canonical) *n_canonical = 0;
     if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
     const size_t n = h->replay_n;
     if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "the replay buffer is empty");
-    HIP_TRY(h, hipSetDevice(h->device));
+    if (mirror && n > DEDUP_MIRROR_MAX_N)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "the symmetric de-duplication takes at most %zu positions", DEDUP_MIRROR_MAX_N);
     size_t tmp = 0, work = 0;
-    int rc = dedup_work_bytes(h, n, &tmp, &work);
+    int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
     if (rc != SYN_OK) return rc;
     rc = ensure_scratch(h, work + 256);
     if (rc != SYN_OK) return rc;
     const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
     DedupOut o;
-    rc = dedup_device_core(h, static_cast<char*>(h->d_scratch), tmp, cur.my, cur.op, cur.pi, cur.v, n, &o);
+    rc = dedup_device_core(h, static_cast<char*>(h->d_scratch), tmp, cur.my, cur.op, cur.pi, cur.v, n, &o, mirror);
     if (rc != SYN_OK) return rc;
-    const size_t m = (size_t)o.m;
+    const size_t m = (size_t)o.total;   // (with mirror: the canonical rows and their mirror images, all of them the learner's)
     if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n);
     // the unique set becomes the learner's data set (the state syn_train_set_data leaves): syn_train_epoch stages in d_scratch too,
     // so it moves to d_train_data before this call returns
@@ -3104,7 +3209,20 @@ int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique) {
     HIP_TRY(h, hipMemcpyAsync(base + m * 52, o.v, m * 12, hipMemcpyDeviceToDevice, h->stream));
     h->train_data_n = m;
     if (n_unique) *n_unique = m;
+    if (n_canonical) *n_canonical = (size_t)o.m;
     return SYN_OK;
+}
+
+int syn_replay_deduplicate_to_trainer(syn_engine* h, size_t* n_unique) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return replay_deduplicate_to_trainer(h, false, nullptr, n_unique);
+}
+
+int syn_replay_deduplicate_to_trainer_symmetric(syn_engine* h, size_t* n_canonical, size_t* n_total) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return replay_deduplicate_to_trainer(h, true, n_canonical, n_total);
 }
 
 int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity,

@@ -66,4 +66,101 @@ __global__ void replay_keep_scatter_kernel(const unsigned* __restrict__ keep, co
     d[(size_t)dst[i] * W + c] = s[t];
 }
 
+// ---------------------------------------------------------------------------------------------- mirror symmetry
+// The 9x7 board is left-right symmetric: a record (my, op, pi, v) implies (mirror(my), mirror(op), reverse(pi), v). Bit index of a
+// bitboard = row + 7 * col (device_common.cuh), so a column is a group of 7 bits and mirroring exchanges the groups c and 8 - c: four
+// delta-swaps at distances 56 / 42 / 28 / 14; the middle column (bits 28..34) and bit 63 stay where they are.
+__device__ __forceinline__ unsigned long long mirror_bb(unsigned long long b) {
+    unsigned long long x;
+    x = ((b >> 56) ^ b) & 0x7Full;          b ^= x ^ (x << 56);
+    x = ((b >> 42) ^ b) & (0x7Full << 7);   b ^= x ^ (x << 42);
+    x = ((b >> 28) ^ b) & (0x7Full << 14);  b ^= x ^ (x << 28);
+    x = ((b >> 14) ^ b) & (0x7Full << 21);  b ^= x ^ (x << 14);
+    return b;
+}
+
+// syn_positions_mirror: a thread moves one dword of pi (out_pi[i][c] = pi[i][8 - c]; pi == nullptr: boards only, n threads), the first
+// n threads also mirror position i's two boards.
+__global__ void __launch_bounds__(256) replay_mirror_kernel(
+    const unsigned long long* __restrict__ my, const unsigned long long* __restrict__ op, const float* __restrict__ pi, int n,
+    unsigned long long* __restrict__ out_my, unsigned long long* __restrict__ out_op, float* __restrict__ out_pi) {
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t < (size_t)n) {
+        out_my[t] = mirror_bb(my[t]);
+        out_op[t] = mirror_bb(op[t]);
+    }
+    if (pi != nullptr && t < (size_t)n * 9) {
+        const size_t i = t / 9, c = t % 9;
+        out_pi[t] = pi[i * 9 + (8 - c)];
+    }
+}
+
+// Symmetric de-duplication, step 1: the canonical orientation of every record. (mirror(my), mirror(op)) < (my, op) as pairs of
+// unsigned numbers, my first (the order the de-duplication emits states in) -> the record is flipped and its keys are the mirrored
+// boards; otherwise the keys are its own. The sort then runs over these n keys: a position and its mirror image meet in one segment.
+__global__ void __launch_bounds__(256) replay_canonicalise_kernel(
+    const unsigned long long* __restrict__ my, const unsigned long long* __restrict__ op, int n,
+    unsigned long long* __restrict__ key_my, unsigned long long* __restrict__ key_op, unsigned* __restrict__ flip) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long a = my[i], b = op[i], ma = mirror_bb(a), mb = mirror_bb(b);
+    const bool f = ma < a || (ma == a && mb < b);
+    key_my[i] = f ? ma : a;
+    key_op[i] = f ? mb : b;
+    flip[i] = f ? 1u : 0u;
+}
+
+// ... step 2, after the stable sort by the canonical keys: dedup_reduce_kernel's shape (train_kernels.cuh: one 16-lane row per class,
+// lane j < 12 owns one target component and sums it over the members in buffer order, then divides by the count), except that the pi
+// lane j reads component 8 - j of a flipped member. Lane 12 writes the canonical state and the count, lane 13 whether the class has a
+// mirror image of its own (expand[row] = 0 for a self-symmetric state).
+__global__ void __launch_bounds__(256) dedup_reduce_mirror_kernel(
+    const unsigned* __restrict__ order, const unsigned* __restrict__ seg_start, int m, int n,
+    const unsigned long long* __restrict__ key_my, const unsigned long long* __restrict__ key_op, const unsigned* __restrict__ flip,
+    const float* __restrict__ pis, const float* __restrict__ vs, unsigned long long* __restrict__ out_my,
+    unsigned long long* __restrict__ out_op, float* __restrict__ out_pi, float* __restrict__ out_v, unsigned* __restrict__ out_num,
+    unsigned* __restrict__ expand) {
+    const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const int j = threadIdx.x & 15;
+    if (row >= m) return;
+    const unsigned s0 = seg_start[row], s1 = row + 1 < m ? seg_start[row + 1] : (unsigned)n;
+    if (j < 12) {
+        float acc = 0.0f;
+        for (unsigned p = s0; p < s1; p++) {
+            const unsigned i = order[p];
+            acc += j < 9 ? pis[(size_t)i * 9 + (flip[i] ? 8 - j : j)] : vs[(size_t)i * 3 + (j - 9)];
+        }
+        const float avg = acc / (float)(s1 - s0);
+        if (j < 9) out_pi[(size_t)row * 9 + j] = avg;
+        else out_v[(size_t)row * 3 + (j - 9)] = avg;
+    } else if (j == 12) {
+        const unsigned i = order[s0];
+        out_my[row] = key_my[i];
+        out_op[row] = key_op[i];
+        out_num[row] = s1 - s0;
+    } else if (j == 13) {
+        const unsigned i = order[s0];
+        const unsigned long long a = key_my[i], b = key_op[i];
+        expand[row] = (mirror_bb(a) != a || mirror_bb(b) != b) ? 1u : 0u;
+    }
+}
+
+// ... step 3, after the exclusive sum `dst` of the expand flags: class `row` with a mirror image writes it to row m + dst[row] —
+// (mirror(my), mirror(op), reverse(pi_avg), v_avg, num): a permutation of the averaged row, so the two rows agree bit for bit.
+// Rows [0, m) are only read, rows [m, rows_cap) only written (the arrays are the same: no __restrict__ on them).
+__global__ void __launch_bounds__(256) dedup_expand_mirror_kernel(
+    const unsigned* __restrict__ expand, const unsigned* __restrict__ dst, int m, size_t rows_cap, unsigned long long* out_my,
+    unsigned long long* out_op, float* out_pi, float* out_v, unsigned* out_num) {
+    const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+    const int j = threadIdx.x & 15;
+    if (row >= m || !expand[row]) return;
+    const size_t d = (size_t)m + dst[row];
+    if (d >= rows_cap) return;
+    if (j < 9) out_pi[d * 9 + j] = out_pi[(size_t)row * 9 + (8 - j)];
+    else if (j < 12) out_v[d * 3 + (j - 9)] = out_v[(size_t)row * 3 + (j - 9)];
+    else if (j == 12) out_my[d] = mirror_bb(out_my[row]);
+    else if (j == 13) out_op[d] = mirror_bb(out_op[row]);
+    else if (j == 14) out_num[d] = out_num[row];
+}
+
 }  // namespace syn

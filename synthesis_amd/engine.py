@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "syn_replay_reserve", "syn_replay_clear", "syn_replay_size", "syn_selfplay_positions_device", "syn_replay_append_selfplay",
     "syn_replay_append_device", "syn_replay_append", "syn_replay_keep_games_from", "syn_replay_read",
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
+    "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
 ]
 
 
@@ -176,12 +177,22 @@ def load_library():
     lib.syn_replay_read.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(C.c_size_t)]
     lib.syn_replay_deduplicate_to_trainer.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
     lib.syn_train_get_data.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(C.c_size_t)]
+    lib.syn_positions_mirror.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_size_t] + [C.c_void_p] * 3
+    lib.syn_replay_deduplicate_symmetric.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 5 + [
+        C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    lib.syn_replay_deduplicate_to_trainer_symmetric.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     _lib = lib
     return lib
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _is_mirror(symmetry):
+    if symmetry not in ("none", "mirror"):
+        raise ValueError(f"symmetry must be 'none' or 'mirror', got {symmetry!r}")
+    return symmetry == "mirror"
 
 
 def _network_of(n_params):
@@ -633,19 +644,46 @@ class Engine:
         self._check(self._lib.syn_trainer_publish_weights(self._h))
         self._net_params = self._trainer_params
 
-    def replay_deduplicate(self, my_bb, op_bb, pis, vs):
+    def replay_deduplicate(self, my_bb, op_bb, pis, vs, symmetry="none"):
+        """symmetry="mirror": the de-duplication over the canonical orientations, closed under the board's left-right mirror
+        (syn_replay_deduplicate_symmetric): up to 2n rows, and the dict gains `canonical` = U, the number of leading canonical rows."""
+        mirror = _is_mirror(symmetry)
         my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()
         op = np.ascontiguousarray(op_bb, dtype=np.uint64).ravel()
         n = int(my.size)
         pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, 9)
         vs = np.ascontiguousarray(vs, dtype=np.float32).reshape(n, 3)
-        o = dict(my_bb=np.zeros(n, np.uint64), op_bb=np.zeros(n, np.uint64), pis=np.zeros((n, 9), np.float32),
-                 vs=np.zeros((n, 3), np.float32), num=np.zeros(n, np.uint32))
+        r = 2 * n if mirror else n
+        o = dict(my_bb=np.zeros(r, np.uint64), op_bb=np.zeros(r, np.uint64), pis=np.zeros((r, 9), np.float32),
+                 vs=np.zeros((r, 3), np.float32), num=np.zeros(r, np.uint32))
         cnt = C.c_size_t()
+        if mirror:
+            canonical = C.c_size_t()
+            self._check(self._lib.syn_replay_deduplicate_symmetric(self._h, _p(my), _p(op), _p(pis), _p(vs), n, _p(o["my_bb"]),
+                                                                   _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), _p(o["num"]),
+                                                                   C.byref(canonical), C.byref(cnt)))
+            return dict({k: a[: cnt.value] for k, a in o.items()}, canonical=int(canonical.value))
         self._check(self._lib.syn_replay_deduplicate(self._h, _p(my), _p(op), _p(pis), _p(vs), n, _p(o["my_bb"]),
                                                      _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), _p(o["num"]),
                                                      C.byref(cnt)))
         return {k: a[: cnt.value] for k, a in o.items()}
+
+    def positions_mirror(self, my_bb, op_bb, pis=None):
+        """The left-right mirror images of n positions (syn_positions_mirror): (my, op) as uint64 arrays, and with `pis` [n, 9] also
+        the reversed policies: (my, op, pis)."""
+        my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(op_bb, dtype=np.uint64).ravel()
+        n = int(my.size)
+        if op.size != n:
+            raise ValueError("my_bb and op_bb must have the same length")
+        omy, oop = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        if pis is None:
+            self._check(self._lib.syn_positions_mirror(self._h, _p(my), _p(op), None, n, _p(omy), _p(oop), None))
+            return omy, oop
+        pis = np.ascontiguousarray(pis, dtype=np.float32).reshape(n, 9)
+        opi = np.zeros((n, 9), np.float32)
+        self._check(self._lib.syn_positions_mirror(self._h, _p(my), _p(op), _p(pis), n, _p(omy), _p(oop), _p(opi)))
+        return omy, oop, opi
 
     # ---- the replay buffer in device memory (data.rs:107-235; include/synthesis_amd.h syn_replay_*)
     def replay_reserve(self, capacity_positions):
@@ -704,10 +742,15 @@ class Engine:
         self._check(self._lib.syn_replay_read(self._h, _p(o["my"]), _p(o["op"]), _p(o["gid"]), _p(o["pi"]), _p(o["v"]), n, C.byref(got)))
         return o
 
-    def replay_deduplicate_to_trainer(self):
+    def replay_deduplicate_to_trainer(self, symmetry="none"):
         """De-duplicates the buffer on the device and makes the unique set the learner's data set (what replay_deduplicate +
-        train_set_data leave, without the host copies). Returns the number of unique states."""
+        train_set_data leave, without the host copies). Returns the number of unique states; with symmetry="mirror"
+        (syn_replay_deduplicate_to_trainer_symmetric) the pair (canonical states U, rows in the data set U + M)."""
         n = C.c_size_t()
+        if _is_mirror(symmetry):
+            u = C.c_size_t()
+            self._check(self._lib.syn_replay_deduplicate_to_trainer_symmetric(self._h, C.byref(u), C.byref(n)))
+            return int(u.value), int(n.value)
         self._check(self._lib.syn_replay_deduplicate_to_trainer(self._h, C.byref(n)))
         return int(n.value)
 

@@ -56,13 +56,18 @@ class LearningLoop:
                  outputs) | "device": the buffer lives in the engine's device memory (Engine.replay_*; data.rs:107-235 on the GPU) —
                  self-play downloads only `plies`, the positions are compacted on the device, trimmed to the last games_to_keep games
                  and de-duplicated straight into the learner's data set. Same games, same buffer order, same bits as "host".
+    symmetry     "none" (default) | "mirror": the de-duplication treats a position and its left-right mirror image as one class and
+                 hands the learner a data set closed under mirroring (Engine.replay_deduplicate(symmetry="mirror") /
+                 replay_deduplicate_to_trainer(symmetry="mirror"); DESIGN.md "Mirror-symmetric de-duplication"): `unique` counts the
+                 canonical states and their mirror images, the record gains `unique_canonical`, latest_*.npy hold the augmented set.
+                 Self-play, the buffer and the network are untouched. Both replay modes, same bits.
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", replay="host", **hyper):
+                 network_arithmetic="f32", replay="host", symmetry="none", **hyper):
         import torch
 
         self._torch = torch
@@ -97,7 +102,10 @@ class LearningLoop:
             raise ValueError(f"sampler must be 'numpy' or 'torch', got {sampler!r}")
         if replay not in ("host", "device"):
             raise ValueError(f"replay must be 'host' or 'device', got {replay!r}")
+        if symmetry not in ("none", "mirror"):
+            raise ValueError(f"symmetry must be 'none' or 'mirror', got {symmetry!r}")
         self.replay = replay
+        self.symmetry = symmetry
         self._device = int(device)
         self._replay_reserved = 0
         self.sampler = sampler
@@ -259,7 +267,10 @@ class LearningLoop:
             steps_in_buffer = self.engine.replay_size()
             # ---- deduplicate into the learner's data set (data.rs:196-235 + alpha_zero.rs:52-58), all on the device
             t2 = time.perf_counter()
-            n_unique = self.engine.replay_deduplicate_to_trainer()
+            if self.symmetry == "mirror":
+                n_canonical, n_unique = self.engine.replay_deduplicate_to_trainer(symmetry="mirror")
+            else:
+                n_unique = self.engine.replay_deduplicate_to_trainer()
             t_dedup = time.perf_counter() - t2
             t3 = time.perf_counter()
             steps, epoch_losses = 0, []
@@ -276,6 +287,8 @@ class LearningLoop:
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=steps_in_buffer, unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
+            if self.symmetry == "mirror":
+                rec["unique_canonical"] = n_canonical
             if self.logs_dir:
                 import os
 
@@ -336,7 +349,10 @@ class LearningLoop:
             self.R = {k: a[keep] for k, a in R.items()}
             # ---- deduplicate on the GPU (data.rs:196-235)
             t2 = time.perf_counter()
-            D = self.engine.replay_deduplicate(self.R["my"], self.R["op"], self.R["pi"], self.R["v"])
+            if self.symmetry == "mirror":
+                D = self.engine.replay_deduplicate(self.R["my"], self.R["op"], self.R["pi"], self.R["v"], symmetry="mirror")
+            else:
+                D = self.engine.replay_deduplicate(self.R["my"], self.R["op"], self.R["pi"], self.R["v"])
             t_dedup = time.perf_counter() - t2
             n_unique = int(D["num"].size)
             # ---- epochs of optimiser steps (alpha_zero.rs:72-94): one upload, one persistent kernel launch per epoch
@@ -356,6 +372,8 @@ class LearningLoop:
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=int(self.R["my"].size), unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
+            if self.symmetry == "mirror":
+                rec["unique_canonical"] = D["canonical"]
             if self.logs_dir:   # alpha_zero.rs:97-100
                 import os
 
