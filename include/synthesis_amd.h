@@ -167,7 +167,8 @@ typedef struct syn_f16x2_plan {
 int syn_get_network_arithmetic(syn_engine* h, int* arithmetic, syn_f16x2_plan* plan);
 /* The same plan for a parameter blob without an engine (pure host code, no GPU needed): what syn_set_network_arithmetic would choose for
  * these parameters; n_floats selects the network (30492: Connect4Net, 12412: Connect4ConvNet, else SYN_ERR_INVALID_ARGUMENT). SYN_OK
- * with plan->valid = 0 when the blob has no plan (non-finite parameters). */
+ * with plan->valid = 0 when the blob has no plan (non-finite parameters, a layer's scales outside the f32-safe window |s + t| <= 60, or a
+ * bias that is not a finite f32 at its layer's scale). */
 int syn_f16x2_plan_of_blob(const float* blob, size_t n_floats, syn_f16x2_plan* plan);
 
 /* ---- leaf evaluation ------------------------------------------------------------------------------------------- */

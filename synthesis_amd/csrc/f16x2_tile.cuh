@@ -309,7 +309,8 @@ inline uint16_t f16x2_bits(float x) { const _Float16 h = (_Float16)x; uint16_t u
 inline float f16x2_value(uint16_t u) { _Float16 h; std::memcpy(&h, &u, 2); return (float)h; }
 
 // blob order: l_k.weight[O][I] then l_k.bias[O], k = 1..5 (study-connect4/src/policies.rs:20-24).
-// Returns false when the checkpoint cannot be represented (non-finite parameters or scales outside the f32-safe window).
+// Returns false when the checkpoint cannot be represented (non-finite parameters, scales outside the f32-safe window, or a bias
+// that leaves f32 when multiplied by its layer's scale 2^(s+t)).
 inline bool build_f16x2_image(const float* blob, F16Image& im) {
     im.words.assign(F16Geom::IMG_WORDS, 0u);
     uint16_t* halfs = reinterpret_cast<uint16_t*>(im.words.data());
@@ -372,7 +373,9 @@ inline bool build_f16x2_image(const float* blob, F16Image& im) {
         for (int ob = 0; ob < NOB; ob++)
             for (int u = 0; u < 16; u++) {
                 const int unit = 16 * ob + u;
-                bimg[F16Geom::B_OFF[l] + ob * 16 + u] = unit < O ? std::ldexp(b[unit], e_acc) : 0.0f;
+                const float bs = unit < O ? std::ldexp(b[unit], e_acc) : 0.0f;
+                if (!std::isfinite(bs)) return false;   // a bias outside the window at its layer's scale (as build_conv_f16x2_image)
+                bimg[F16Geom::B_OFF[l] + ob * 16 + u] = bs;
             }
     }
     return true;

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from tests import f16x2_checkpoints as fc
+
 
 @pytest.fixture(scope="module")
 def model(tmp_path_factory):
@@ -54,6 +56,89 @@ def test_model_is_within_tolerance_of_the_slimnn_order(model, oracle, blobs):
     l, v = model.eval(trained, my, op)
     sl, sv = oracle.c4conv_eval(trained, my, op, mode=oracle.ACC_SLIMNN)
     assert np.abs(l - sl).max() / max(1.0, float(np.abs(sl).max())) < 2e-6 and np.abs(v - sv).max() < 1e-5
+
+
+# ---- the stress family (tests/f16x2_checkpoints.py) -----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def family(blobs):
+    return fc.conv_family(*blobs)
+
+
+@pytest.fixture(scope="module")
+def family_positions(oracle):
+    from tests.test_gpu_parity import random_positions
+
+    return random_positions(oracle, 1000, seed=2026)
+
+
+def test_f64_reference_is_the_conv_network(oracle, blobs, family_positions):
+    """The yardstick itself (fc.conv_f64, plain numpy float64) computes the function of the oracle's slimnn-order Connect4ConvNet."""
+    my, op = family_positions
+    my = np.concatenate([np.zeros(1, np.uint64), my[:300]]); op = np.concatenate([np.zeros(1, np.uint64), op[:300]])   # + the empty board
+    for w, tol in zip(blobs, (2e-6, 5e-5)):
+        raw, v = fc.conv_f64(w, my, op)
+        sl, sv, sraw = oracle.c4conv_eval(w, my, op, mode=oracle.ACC_SLIMNN, raw=True)
+        assert np.abs(raw - sraw).max() < tol and np.abs(v - sv).max() < 2e-6
+
+
+@pytest.mark.parametrize("name", fc.CONV_MEMBERS)
+def test_conv_f16x2_family_member_meets_the_f64_bars(model, oracle, family, family_positions, name):
+    """Every member, 1,000 reachable positions: the CPU model of the definition against float64 (fc.check_f64_bars)."""
+    my, op = family_positions
+    w = family[name]
+    l, v = model.eval(w, my, op)
+    fl, _ = oracle.c4conv_eval(w, my, op, mode=oracle.ACC_FMA)
+    raw, v64 = fc.conv_f64(w, my, op)
+    fc.check_f64_bars("conv " + name, l, v, fl, raw, v64)
+
+
+def test_conv_family_plans_agree_between_the_product_and_the_model(model, blobs, family):
+    """syn_f16x2_plan_of_blob against the model's plan on every member and on init x 2^k for every k in -30..30: the same verdict, the
+    same exponents and bounds. The family reaches both caps (tc and th at 40, s1 at 24), negative exponents and both signs of the
+    rescale exponent s1 - tc."""
+    from synthesis_amd.engine import f16x2_plan_of_blob
+
+    def same(w, ctx):
+        a, b = f16x2_plan_of_blob(w), model.plan(w)
+        assert (a is None) == (b is None), ctx
+        if a is not None:
+            assert a["activation_exp"] == b["activation_exp"] and a["weight_exp"] == b["weight_exp"] and a["out_exp"] == b["out_exp"], ctx
+            assert a["bound"] == b["bound"], ctx
+            assert abs(b["weight_exp"][0]) <= 60 and abs(b["activation_exp"][1] + b["weight_exp"][1]) <= 60, ctx
+            assert b["out_exp"] == -(b["activation_exp"][1] + b["weight_exp"][1]), ctx
+        return b
+
+    plans = {name: same(w, name) for name, w in family.items()}
+    assert all(p is not None for p in plans.values())
+    every = list(plans.values())
+    assert any(p["activation_exp"][1] == 24 for p in every)                                            # the s cap
+    assert any(p["weight_exp"][0] == 40 for p in every) and any(p["weight_exp"][1] == 40 for p in every)   # the t cap, conv and head
+    assert plans["zero"]["weight_exp"][:2] == [0, 0] and plans["init_convW_zero"]["weight_exp"][0] == 0
+    assert any(p["activation_exp"][1] < 0 for p in every) and any(min(p["weight_exp"][:2]) < 0 for p in every)
+    cexp = [p["activation_exp"][1] - p["weight_exp"][0] for p in every]
+    assert min(cexp) < 0 < max(cexp)
+    rand = blobs[0]
+    ok_p, edges = fc.accept_edges(lambda w: f16x2_plan_of_blob(w) is not None, rand)
+    ok_m, _ = fc.accept_edges(lambda w: model.plan(w) is not None, rand)
+    assert ok_p == ok_m
+    for k in ok_p:
+        same(rand * np.float32(2.0) ** np.float32(k), k)
+    print(f"Connect4ConvNet init x 2^k: accepted for k in [{edges['last_accepted_down']}, {edges['last_accepted_up']}], "
+          f"refused at {edges['first_refused_down']} and {edges['first_refused_up']}")
+    assert edges["first_refused_down"] == edges["last_accepted_down"] - 1   # (upwards every k of the sweep has a plan)
+    assert all(ok_p[k] for k in range(edges["last_accepted_down"], 31))
+
+
+def test_conv_f16x2_family_replays_device_bits_and_plans(model, golden_dir, family):
+    """What an MI355X computed for every member (64 positions; tests/golden/make_f16x2_family_golden.py): the model reproduces every
+    bit and the plan's exponents."""
+    g = np.load(os.path.join(golden_dir, "f16x2_family_device.npz"))
+    my, op = g["my_bb"], g["op_bb"]
+    for name, w in family.items():
+        l, v = model.eval(w, my, op)
+        assert fc.same_bits(l, g[f"conv.{name}.logits"]) and fc.same_bits(v, g[f"conv.{name}.value"]), name
+        plan = model.plan(w)
+        assert plan["activation_exp"] + plan["weight_exp"] + [plan["out_exp"]] == g[f"conv.{name}.plan"].tolist(), name
 
 
 def test_learning_loop_runs_self_play_in_the_chosen_arithmetic():
