@@ -35,6 +35,7 @@
 #include "train_conv.cuh"
 #include "train_conv_mfma.cuh"
 #include "lane_instances.h"
+#include "launch_plan.hpp"
 #include "free_kernel.cuh"
 #ifdef SYN_DEBUG_SHAPES
 #include "pool_kernel.cuh"   // round 6's measured dead end (trees unbound from the lanes): a debug shape like the two above
@@ -47,63 +48,30 @@
 
 using namespace syn;
 
-// The Connect4ConvNet instantiations of the lane-per-tree kernel are compiled in engine_conv.hip (a second translation unit, built in
-// parallel); here they are only declared.
+// The lane-per-tree, free-running, pool and two-trees-per-lane instantiations are compiled in the side translation units (engine_conv.hip,
+// engine_lanes_*.hip, engine_free.hip, ...: built in parallel); here they are only declared, from the lists those units define them
+// from (lane_instances.h).
+#define SYN_LANES_ALL_LISTS(X)                                                                                           \
+    SYN_LANES_FAST_LIST(X) SYN_LANES_GEN_LIST(X) SYN_LANES_REF_LIST(X) SYN_LANES_F16_LIST(X) SYN_LANES_F16_GEN_LIST(X) \
+    SYN_LANES_CONV_LIST(X) SYN_LANES_CONV_F16_LIST(X)
 namespace syn {
-#define SYN_CONV_LANES(MODE, COUNT)                                                                        \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 4, false, 2>(EngineParams);   \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 4, false, 2>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 8, false, 2>(EngineParams);   \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 8, false, 2>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 16, false, 2>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 16, false, 2>(EngineParams);
-SYN_CONV_LANES(MODE_SEARCH, false)
-SYN_CONV_LANES(MODE_SELFPLAY, false)
-SYN_CONV_LANES(MODE_SELFPLAY, true)
-#undef SYN_CONV_LANES
-// ... and (DEBUG_SHAPES=1 builds only) the two-trees-per-lane kernels in engine_lanes2.hip
-#ifdef SYN_DEBUG_SHAPES
-#define SYN_LANES2(MODE, COUNT)                                                                      \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 8, 0>(EngineParams);   \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 8, 0>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 8, 2>(EngineParams);   \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 8, 2>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 12, 0>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 12, 0>(EngineParams); \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 12, 2>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 12, 2>(EngineParams);
-extern template __global__ void selfplay_kernel_lanes2<MODE_SELFPLAY, false, true, 8, 0, 1>(EngineParams);
-SYN_LANES2(MODE_SEARCH, false)
-SYN_LANES2(MODE_SELFPLAY, false)
-SYN_LANES2(MODE_SELFPLAY, true)
-#undef SYN_LANES2
-#endif
-// ... and the Connect4Net / RolloutPolicy lane-per-tree kernels in engine_lanes_fast.hip and engine_lanes_gen.hip
 #define SYN_X(MODE, COUNT, FAST, NW, PROF, POLICY) \
     extern template __global__ void selfplay_kernel_lanes<MODE, COUNT, FAST, NW, PROF, POLICY>(EngineParams);
-SYN_LANES_FAST_LIST(SYN_X)
-SYN_LANES_GEN_LIST(SYN_X)
-SYN_LANES_REF_LIST(SYN_X)
-SYN_LANES_F16_LIST(SYN_X)
-SYN_LANES_F16_GEN_LIST(SYN_X)
-SYN_LANES_CONV_F16_LIST(SYN_X)
+SYN_LANES_ALL_LISTS(SYN_X)
 #undef SYN_X
-// ... and (DEBUG_SHAPES=1 builds only) the pool kernels (pool_kernel.cuh) in engine_pool.hip / engine_pool_f16.hip
-#ifdef SYN_DEBUG_SHAPES
+#define SYN_X(MODE, COUNT, FAST, PROF) extern template __global__ void selfplay_kernel_free<MODE, COUNT, FAST, PROF>(EngineParams);
+SYN_FREE_LIST(SYN_X)
+#undef SYN_X
+#ifdef SYN_DEBUG_SHAPES   // ... and (DEBUG_SHAPES=1 builds only) engine_lanes2.hip and engine_pool.hip / engine_pool_f16.hip
+#define SYN_X(MODE, COUNT, FAST, NW, POLICY, TILE) \
+    extern template __global__ void selfplay_kernel_lanes2<MODE, COUNT, FAST, NW, POLICY, TILE>(EngineParams);
+SYN_LANES2_LIST(SYN_X)
+#undef SYN_X
 #define SYN_X(MODE, COUNT, FAST, NW, POLICY) extern template __global__ void selfplay_kernel_pool<MODE, COUNT, FAST, NW, POLICY>(EngineParams);
 SYN_POOL_F32_LIST(SYN_X)
 SYN_POOL_F16_LIST(SYN_X)
 #undef SYN_X
 #endif
-// ... and the free-running four-trees-per-wave kernels (free_kernel.cuh) in engine_free.hip
-#define SYN_FREE(MODE, COUNT)                                                                      \
-    extern template __global__ void selfplay_kernel_free<MODE, COUNT, true, false>(EngineParams);  \
-    extern template __global__ void selfplay_kernel_free<MODE, COUNT, false, false>(EngineParams);
-SYN_FREE(MODE_SEARCH, false)
-SYN_FREE(MODE_SELFPLAY, false)
-SYN_FREE(MODE_SELFPLAY, true)
-#undef SYN_FREE
-extern template __global__ void selfplay_kernel_free<MODE_SELFPLAY, false, true, true>(EngineParams);
 }  // namespace syn
 
 static_assert(sizeof(DevSearchResult) == sizeof(syn_search_result), "search result layout must match the C ABI");
@@ -360,480 +328,142 @@ static int convert_mcts(syn_engine* h, const syn_mcts_config* c, DevMctsCfg& d) 
 }
 
 // ------------------------------------------------------------------------------------------------ launches
-template <int MODE, bool COUNT, bool PROF = false>
-static hipError_t launch_engine(syn_engine* h, const EngineParams& P, int jobs, int* out_grid = nullptr,
-                                int* out_nt = nullptr) {
-    // one 256-thread workgroup per 16 tree slots; the kernel needs ~17 KB of LDS and <= 256 VGPRs, so up to two
-    // workgroups are resident per CU (concurrency beyond 2 x 16 x CUs queues behind resident workgroups)
-    int want_slots = h->slots;
-    if (jobs < want_slots) want_slots = ((jobs + 15) / 16) * 16;
-    int grid = want_slots / 16;
-    if (grid < 1) grid = 1;
-    const bool fast = cfg_is_fast(P.mcts);  // compile-time-folded config family (mcts.cuh CfgView)
-#define SYN_LAUNCH(WPS, FAST)                                                                                      \
-    {                                                                                                              \
-        auto k = selfplay_kernel<MODE, COUNT, WPS, FAST, PROF>;                                                    \
-        size_t lds = WPS == 1 ? EngineLds::BYTES_WPS1 : EngineLds::BYTES_WPS2;                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, h->stream, P);                                           \
-    }
-    // Kernel choice by trees per CU: <= 16 -> one 16-tree workgroup per CU, weights in registers (latency-optimal);
-    // <= 32 -> two such workgroups per CU (hybrid register/LDS weights); more -> the quad-async kernel (NQ quads of 16
-    // trees per workgroup sharing one LDS weight image). SYN_DEBUG=1 SYN_QUADS=0..4 overrides (0 = never use the quad kernel).
-    // Lane-per-tree kernel (lane_kernel.cuh): one tree per lane, NW waves per workgroup, one workgroup per CU.
-    // SYN_DEBUG=1 SYN_LANES=<waves per workgroup: 4, 8, 12 or 16> forces it (0 = never); by default it takes over once every CU can
-    // be given 256 trees (4 waves; measured 41.9k games/s at 65,536 concurrent games against 31.8k for the queued
-    // row-per-tree workgroups), 8 waves up to 512 trees per CU, 12 up to 768, 16 beyond (selection below).
-    // Producer/consumer kernel (pc_kernel.cuh): 12 tree waves x NV virtual waves of 64 trees + 4 matrix waves per CU. Measured
-    // slower than the symmetric lane kernel (the f32 MFMA shares the SIMD's FP32 datapath with the VALU, so
-    // dedicating waves to the matrix pipe frees nothing), so it is never chosen automatically:
-    // SYN_DEBUG=1 SYN_PC=<NV 1..3> selects it (parity tests, profiling).
+// Which kernel plays a call and on what shape is decided in launch_plan.hpp (plan_launch: a pure function, tested on a CPU). Here:
+// the table of the instantiations the library ships, the lookup of a plan's kernel in it and the one place that launches.
+static_assert(PLAN_LANE_MAX_CAP == LANE_MAX_CAP && PLAN_PATH_ENTRIES == PATH_ENTRIES, "launch_plan.hpp restates lane_kernel.cuh");
+static_assert(MODE_SELFPLAY == 0 && MODE_SEARCH == 1, "launch_plan.hpp restates engine_kernels.cuh's MODE_*");
 #ifdef SYN_DEBUG_SHAPES
-    {
-        int nv = 0;
-        if (const char* ev = debug_env("SYN_PC")) nv = std::atoi(ev);
-        if (nv >= 1 && nv <= PcGeom::NV_MAX && h->cap <= LANE_MAX_CAP && h->net_kind == 0) {
-            const int per_wg = 64 * PcGeom::TREE_WAVES * nv;
-            const int pgrid = (want_slots + per_wg - 1) / per_wg;
-            const size_t nvw = (size_t)pgrid * PcGeom::TREE_WAVES * nv;
-            const size_t need_path = nvw * PATH_ENTRIES * sizeof(uint4);
-            if (need_path > h->path_bytes) {
-                if (h->d_path) (void)hipFree(h->d_path);
-                h->d_path = nullptr;
-                h->path_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_path, need_path);
-                if (pe != hipSuccess) return pe;
-                h->path_bytes = need_path;
-            }
-            const size_t need_vw = nvw * PcGeom::VW_BYTES;
-            if (need_vw > h->vw_bytes) {
-                if (h->d_vw) (void)hipFree(h->d_vw);
-                h->d_vw = nullptr;
-                h->vw_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_vw, need_vw);
-                if (pe != hipSuccess) return pe;
-                h->vw_bytes = need_vw;
-            }
-            EngineParams PL = P;
-            PL.path = h->d_path;
-            PL.vw_buf = h->d_vw;
-            PL.nv = nv;
-            PL.debug_prio = 2;
-            if (const char* ev = debug_env("SYN_PC_PRIO")) PL.debug_prio = std::atoi(ev);
-            PL.debug_stub = (PROF && debug_env("SYN_PC_STUB") != nullptr) ? 1 : 0;
-            PL.lane_thresh = 48;
-            if (const char* ev = debug_env("SYN_LANE_THRESH")) PL.lane_thresh = std::atoi(ev);
-            if (PL.lane_thresh < 16 || PL.lane_thresh > 64) PL.lane_thresh = 48;
-            PL.lane_thresh &= ~15;  // whole tiles
-#define SYN_LAUNCH_PC(FAST)                                                                                        \
-    {                                                                                                              \
-        auto k = selfplay_kernel_pc<MODE, COUNT, FAST, PROF>;                                                      \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)PcLds::BYTES);         \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(pgrid), dim3(PcGeom::NT), PcLds::BYTES, h->stream, PL);                         \
-    }
-            if (fast) SYN_LAUNCH_PC(true) else SYN_LAUNCH_PC(false)
-#undef SYN_LAUNCH_PC
-            h->last_shape = 5; h->last_grid = pgrid; h->last_threads = PcGeom::NT;
-            if (out_grid) *out_grid = pgrid;
-            if (out_nt) *out_nt = PcGeom::NT;
-            return hipGetLastError();
-        }
-    }
+static_assert(PLAN_PC_TREE_WAVES == PcGeom::TREE_WAVES && PLAN_PC_NT == PcGeom::NT && PLAN_PC_NV_MAX == PcGeom::NV_MAX &&
+              PLAN_PC_VW_BYTES == PcGeom::VW_BYTES, "launch_plan.hpp restates pc_kernel.cuh");
+static_assert(PLAN_POOL_M_MAX == PoolGeom::M_MAX && PLAN_POOL_WAVE_BYTES == PoolGeom::WAVE_BYTES, "launch_plan.hpp restates pool_kernel.cuh");
 #endif
-    // At most 16 trees per CU in the f16x2 arithmetic: four free-running waves of four trees, each evaluating its own leaves in a tile
-    // of its own (free_kernel.cuh). The draws of Fpu::Func / PolicyNoise::Dirichlet live in the lane-per-tree kernels only.
-    // SYN_DEBUG=1 SYN_FREE=0 switches it off (the lane kernel at 4 waves then plays these games).
-    if (h->net_kind == 0 && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16) &&
-        want_slots <= 16 * h->num_cus && P.mcts.fpu != 2 && P.mcts.noise != 2 && debug_env("SYN_LANES") == nullptr &&
-        !(debug_env("SYN_FREE") && std::atoi(debug_env("SYN_FREE")) == 0)
+
+struct KernelEntry {
+    int shape;   // LaunchPlan::shape
+    int mode, count, fast, n, prof, policy, tile;
+    void (*fn)(EngineParams);
+    size_t lds;
+};
+// the row-per-tree, quad and producer/consumer kernels are instantiated by this translation unit, for the four kinds of call
+#define SYN_CALL_LIST(X) X(MODE_SEARCH, false, false) X(MODE_SELFPLAY, false, false) X(MODE_SELFPLAY, true, false) X(MODE_SELFPLAY, false, true)
+#define SYN_ROW(MODE, COUNT, PROF, WPS, FAST) \
+    {WPS, MODE, COUNT, FAST, WPS, PROF, 0, 0, selfplay_kernel<MODE, COUNT, WPS, FAST, PROF>, WPS == 1 ? EngineLds::BYTES_WPS1 : EngineLds::BYTES_WPS2},
+#define SYN_QUAD(MODE, COUNT, PROF, NQ, FAST) {3, MODE, COUNT, FAST, NQ, PROF, 0, 0, selfplay_kernel_quads<MODE, COUNT, FAST, NQ, PROF>, QuadLds<NQ>::BYTES},
 #ifdef SYN_DEBUG_SHAPES
-        && !(debug_env("SYN_POOL") && std::atoi(debug_env("SYN_POOL")) > 64)
+#define SYN_PC(MODE, COUNT, PROF, FAST) {5, MODE, COUNT, FAST, 0, PROF, 0, 0, selfplay_kernel_pc<MODE, COUNT, FAST, PROF>, PcLds::BYTES},
+#else
+#define SYN_PC(MODE, COUNT, PROF, FAST)
 #endif
-        ) {
-        const int mgrid = (want_slots + 15) / 16;
-#define SYN_LAUNCH_FR(FAST, PROFV)                                                                                 \
-    {                                                                                                              \
-        auto k = selfplay_kernel_free<MODE, COUNT, FAST, PROFV>;                                                   \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)FreeLds::BYTES);       \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(mgrid), dim3(256), FreeLds::BYTES, h->stream, P);                               \
-    }
-        constexpr bool PROFFR = PROF && MODE == MODE_SELFPLAY && !COUNT;
-        if (fast) SYN_LAUNCH_FR(true, PROFFR) else SYN_LAUNCH_FR(false, false)
-#undef SYN_LAUNCH_FR
-        h->last_shape = 7; h->last_grid = mgrid; h->last_threads = 256;
-        if (out_grid) *out_grid = mgrid;
-        if (out_nt) *out_nt = 256;
-        return hipGetLastError();
-    }
+static const KernelEntry g_kernels[] = {
+#define SYN_X(MODE, COUNT, PROF)                                                                                                    \
+    SYN_ROW(MODE, COUNT, PROF, 1, false) SYN_ROW(MODE, COUNT, PROF, 1, true) SYN_ROW(MODE, COUNT, PROF, 2, false) SYN_ROW(MODE, COUNT, PROF, 2, true) \
+    SYN_QUAD(MODE, COUNT, PROF, 2, false) SYN_QUAD(MODE, COUNT, PROF, 2, true) SYN_QUAD(MODE, COUNT, PROF, 3, false)                \
+    SYN_QUAD(MODE, COUNT, PROF, 3, true) SYN_QUAD(MODE, COUNT, PROF, 4, false) SYN_QUAD(MODE, COUNT, PROF, 4, true)                 \
+    SYN_PC(MODE, COUNT, PROF, false) SYN_PC(MODE, COUNT, PROF, true)
+    SYN_CALL_LIST(SYN_X)
+#undef SYN_X
+#define SYN_X(MODE, COUNT, FAST, NW, PROF, POLICY) \
+    {4, MODE, COUNT, FAST, NW, PROF, POLICY, 0, selfplay_kernel_lanes<MODE, COUNT, FAST, NW, PROF, POLICY>, LaneLds<NW>::BYTES},
+    SYN_LANES_ALL_LISTS(SYN_X)
+#undef SYN_X
+#define SYN_X(MODE, COUNT, FAST, PROF) {7, MODE, COUNT, FAST, 0, PROF, 0, 0, selfplay_kernel_free<MODE, COUNT, FAST, PROF>, FreeLds::BYTES},
+    SYN_FREE_LIST(SYN_X)
+#undef SYN_X
 #ifdef SYN_DEBUG_SHAPES
-    // Two trees per lane (lane2_kernel.cuh): 8 waves per workgroup, 1,024 trees per CU. SYN_DEBUG=1 SYN_LANES2=8 forces it,
-    // SYN_LANES2=0 switches it off.
-    {
-        int nw2 = 0;
-        const bool needs_noise2 = P.mcts.fpu == 2 || P.mcts.noise == 2;
-        if (const char* ev = debug_env("SYN_LANES2")) nw2 = std::atoi(ev);
-        if (PROF) nw2 = 0;
-        if ((nw2 == 8 || nw2 == 12) && h->cap <= LANE_MAX_CAP && !(h->net_kind == 1 && h->net_arith == SYN_NET_ARITH_F16X2)) {
-            (void)needs_noise2;
-            const int per_wg = 128 * nw2;
-            const int lgrid = (want_slots + per_wg - 1) / per_wg;
-            const size_t need_path = (size_t)lgrid * nw2 * 2 * PATH_ENTRIES * sizeof(uint4);
-            if (need_path > h->path_bytes) {
-                if (h->d_path) (void)hipFree(h->d_path);
-                h->d_path = nullptr;
-                h->path_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_path, need_path);
-                if (pe != hipSuccess) return pe;
-                h->path_bytes = need_path;
-            }
-            EngineParams PL = P;
-            PL.path = h->d_path;
-            PL.lane_thresh = 48;
-            if (const char* ev = debug_env("SYN_LANE_THRESH")) PL.lane_thresh = std::atoi(ev);
-            if (PL.lane_thresh < 16 || PL.lane_thresh > 64) PL.lane_thresh = 48;
-            PL.lane_thresh &= ~15;  // whole tiles
-#define SYN_LAUNCH_L2(NW, FAST, POL)                                                                               \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes2<MODE, COUNT, FAST, NW, POL>;                                               \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lane2Lds<NW>::BYTES);  \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), Lane2Lds<NW>::BYTES, h->stream, PL);                     \
-    }
-            if (nw2 == 12) {
-                if (h->net_kind == 1) { if (fast) SYN_LAUNCH_L2(12, true, 2) else SYN_LAUNCH_L2(12, false, 2) }
-                else { if (fast) SYN_LAUNCH_L2(12, true, 0) else SYN_LAUNCH_L2(12, false, 0) }
-            }
-            else if (h->net_kind == 1) { if (fast) SYN_LAUNCH_L2(8, true, 2) else SYN_LAUNCH_L2(8, false, 2) }
-            else if (MODE == MODE_SELFPLAY && !COUNT && fast && debug_env("SYN_L2_TILE")) {
-                auto k = selfplay_kernel_lanes2<MODE_SELFPLAY, false, true, 8, 0, 1>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)Lane2Lds<8>::BYTES);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(k, dim3(lgrid), dim3(512), Lane2Lds<8>::BYTES, h->stream, PL);
-            }
-            else { if (fast) SYN_LAUNCH_L2(8, true, 0) else SYN_LAUNCH_L2(8, false, 0) }
-#undef SYN_LAUNCH_L2
-            h->last_shape = 6; h->last_grid = lgrid; h->last_threads = 64 * nw2;
-            if (out_grid) *out_grid = -lgrid;
-            if (out_nt) *out_nt = 64 * nw2;
-            return hipGetLastError();
-        }
-    }
+#define SYN_X(MODE, COUNT, FAST, NW, POLICY, TILE) \
+    {6, MODE, COUNT, FAST, NW, false, POLICY, TILE, selfplay_kernel_lanes2<MODE, COUNT, FAST, NW, POLICY, TILE>, Lane2Lds<NW>::BYTES},
+    SYN_LANES2_LIST(SYN_X)
+#undef SYN_X
+#define SYN_X(MODE, COUNT, FAST, NW, POLICY) \
+    {8, MODE, COUNT, FAST, NW, false, POLICY, 0, selfplay_kernel_pool<MODE, COUNT, FAST, NW, POLICY>, PoolLds<NW, FAST>::BYTES},
+    SYN_POOL_F32_LIST(SYN_X) SYN_POOL_F16_LIST(SYN_X)
+#undef SYN_X
 #endif
-#ifdef SYN_DEBUG_SHAPES
-    // The pool kernel (pool_kernel.cuh): a wave's 64 lanes work on a pool of M trees (64 < M <= 128) — a lane whose descent arrives
-    // binds the next READY tree in the same iteration, a round fires on 64 leaves — for the two compile-time-folded configuration
-    // families of Connect4Net (f32 and f16x2), 12 or 8 waves x M trees per CU. Measured slower than the lane kernel on every leg in
-    // three same-box A/B runs (profiles/r06_pool_unbinding_ab.txt, NOTES round 6), so it is never chosen automatically and ships only
-    // in DEBUG_SHAPES=1 builds: SYN_DEBUG=1 SYN_POOL=<M> selects it (parity tests, re-measurement).
-    {
-        int pm = h->pool_trees;
-        if (const char* ev = debug_env("SYN_POOL")) pm = std::atoi(ev);
-        // 1 = as many trees per wave as the engine's slots give 12 waves on every CU (at most 128)
-        if (pm == 1) pm = (want_slots + h->num_cus * 12 - 1) / (h->num_cus * 12) > PoolGeom::M_MAX ? PoolGeom::M_MAX
-                                                                                                   : (want_slots + h->num_cus * 12 - 1) / (h->num_cus * 12);
-        const int fam = cfg_family(P.mcts);
-        const bool f16 = h->net_kind == 0 && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
-        const bool lanes_forced = debug_env("SYN_LANES") != nullptr || debug_env("SYN_QUADS") != nullptr;
-        if (pm > 64 && pm <= PoolGeom::M_MAX && (fam == 1 || fam == 2) && h->net_kind == 0 && h->cap <= LANE_MAX_CAP && !PROF && !lanes_forced &&
-            (debug_env("SYN_POOL") != nullptr || want_slots >= h->num_cus * 768)) {
-            int nw = 12;   // waves per workgroup: 12 (three per SIMD, 168 registers) or 8 (two per SIMD, 256 registers)
-            if (const char* ev = debug_env("SYN_POOL_NW")) nw = std::atoi(ev) == 8 ? 8 : 12;
-            const int per_wg = nw * pm;
-            int pgrid = (want_slots + per_wg - 1) / per_wg;
-            if (pgrid > h->num_cus) pgrid = h->num_cus;   // one workgroup per CU: a larger engine only holds idle slabs
-            if (pgrid < 1) pgrid = 1;
-            const size_t nwv = (size_t)pgrid * nw;
-            const size_t need_path = nwv * 2 * PATH_ENTRIES * sizeof(uint4);
-            if (need_path > h->path_bytes) {
-                if (h->d_path) (void)hipFree(h->d_path);
-                h->d_path = nullptr;
-                h->path_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_path, need_path);
-                if (pe != hipSuccess) return pe;
-                h->path_bytes = need_path;
-            }
-            const size_t need_vw = nwv * PoolGeom::WAVE_BYTES;
-            if (need_vw > h->vw_bytes) {
-                if (h->d_vw) (void)hipFree(h->d_vw);
-                h->d_vw = nullptr;
-                h->vw_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_vw, need_vw);
-                if (pe != hipSuccess) return pe;
-                h->vw_bytes = need_vw;
-            }
-            EngineParams PL = P;
-            PL.path = h->d_path;
-            PL.vw_buf = h->d_vw;
-            PL.nv = pm;
-            PL.lane_thresh = 24;   // Fpu::Func: waiting lanes that trigger a scan iteration
-            if (const char* ev = debug_env("SYN_POOL_SCAN")) PL.lane_thresh = std::atoi(ev);
-            if (PL.lane_thresh < 1 || PL.lane_thresh > 64) PL.lane_thresh = 24;
-            PL.debug_prio = 64;    // leaves that fire a round
-            if (const char* ev = debug_env("SYN_POOL_FIRE")) PL.debug_prio = std::atoi(ev);
-            if (PL.debug_prio < 16 || PL.debug_prio > 64) PL.debug_prio = 64;
-#define SYN_LAUNCH_P(FASTV, POL) { if (nw == 8) SYN_LAUNCH_PN(FASTV, POL, 8) else SYN_LAUNCH_PN(FASTV, POL, 12) }
-#define SYN_LAUNCH_PN(FASTV, POL, NWV)                                                                             \
-    {                                                                                                              \
-        auto k = selfplay_kernel_pool<MODE, COUNT, FASTV, NWV, POL>;                                               \
-        using PLds = PoolLds<NWV, FASTV>;                                                                          \
-        const size_t plds = PLds::BYTES;                                                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);                 \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(pgrid), dim3(64 * NWV), plds, h->stream, PL);                                   \
-    }
-            if (f16) { if (fam == 1) SYN_LAUNCH_P(1, 3) else SYN_LAUNCH_P(2, 3) }
-            else { if (fam == 1) SYN_LAUNCH_P(1, 0) else SYN_LAUNCH_P(2, 0) }
-#undef SYN_LAUNCH_P
-#undef SYN_LAUNCH_PN
-            h->last_shape = 8; h->last_grid = pgrid; h->last_threads = 64 * nw;
-            h->last_pool_trees = pm;
-            if (out_grid) *out_grid = pgrid;
-            if (out_nt) *out_nt = 64 * nw;
-            return hipGetLastError();
-        }
-    }
-#endif
-    {
-        int nw = 0;
-        // 4 waves per workgroup up to 256 trees per CU, 8 up to 512, 12 up to 768, 16 (hand-pipelined network tile that fits
-        // the 128-VGPR budget: mlp_tile16_pipe) beyond
-        if (want_slots >= h->num_cus * 256)
-            nw = want_slots > h->num_cus * 768 ? 16 : (want_slots > h->num_cus * 512 ? 12 : (want_slots > h->num_cus * 256 ? 8 : 4));
-        // the random draws of Fpu::Func / PolicyNoise::Dirichlet (noise.cuh) exist in the lane-per-tree kernels only
-        const bool needs_noise = P.mcts.fpu == 2 || P.mcts.noise == 2;
-        if (needs_noise && nw == 0) nw = 4;
-        if (const char* ev = debug_env("SYN_LANES")) nw = std::atoi(ev);
-        if (needs_noise && !(nw == 4 || nw == 8 || nw == 12 || nw == 16)) nw = 4;
-        if (needs_noise && h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
-        // Connect4ConvNet (convnet.cuh) is evaluated by the lane-per-tree kernels only: 4 waves per workgroup up to 256 trees
-        // per CU, 8 up to 512, 16 beyond
-        const bool conv = h->net_kind == 1;
-        // Connect4Net in the f16x2 arithmetic (f16x2_tile.cuh) is evaluated by the lane-per-tree kernels only, at every size
-        const bool f16x2 = !conv && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
-        // ... and Connect4ConvNet in it (conv_f16x2_tile.cuh, POLICY 4)
-        const bool conv16 = conv && h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
-        if (f16x2) {
-            if (h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
-            if (debug_env("SYN_LANES") == nullptr || !(nw == 4 || nw == 8 || nw == 12 || nw == 16))
-                nw = want_slots > h->num_cus * 768 ? 16 : (want_slots > h->num_cus * 512 ? 12 : (want_slots > h->num_cus * 256 ? 8 : 4));
-        }
-        if (conv) {
-            if (h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
-            if (conv16) {
-                // the f16x2 tile ships where its instantiations keep their registers (profiles/r07_conv_f16x2_resource_usage.txt): the
-                // parity family at 4 and 8 waves (at most 512 trees per CU), the runtime-switched configurations at 4 (at most 256)
-                const bool forced = debug_env("SYN_LANES") != nullptr && (nw == 4 || nw == 8);
-                if (!forced) nw = want_slots > h->num_cus * 256 ? 8 : 4;
-                if (!fast) nw = 4;
-                if (want_slots > h->num_cus * 64 * nw) want_slots = h->num_cus * 64 * nw;
-            } else
-                nw = want_slots > h->num_cus * 512 ? 16 : (want_slots > h->num_cus * 256 ? 8 : 4);
-        }
-        // The runtime-switched (general) instantiations need 300-450 more registers than the 128 of a 16-wave workgroup and are
-        // bound by their own scratch traffic there (PMC: 8.8x the algorithmic bytes; Fpu::ParentQ 29.5k games/s against 42.4k,
-        // Fpu::Func 15.9k against 31.2k): they run 8 waves of 256 registers on at most 512 trees per CU, whatever the capacity.
-        if (!fast && cfg_family(P.mcts) != 2 && nw > 8 && debug_env("SYN_LANES") == nullptr) {
-            nw = 8;
-            if (want_slots > h->num_cus * 512) want_slots = h->num_cus * 512;
-        }
-        // Tree-bound regimes — PolicyWithCache on (most leaf evaluations are table hits) or the reference's own Fpu::Func
-        // configuration — run 12 waves of 168 registers (17 spilled) on at most 768 trees per CU rather than 16 x 128 (55 spilled):
-        // measured 90.5k against 84.8k games/s with the cache, 61.2k against 55.8k with the trained checkpoint and the cache,
-        // 51.2k against 47.7k for the reference configuration; without the cache the two shapes are equal (70.6k / 71.2k).
-        // The f16x2 arithmetic makes every regime tree-bound (its network tile is a quarter of the f32 one): 102k games/s at 16 x 1,024
-        // against 111k at 12 x 768 (random-init), 65.0k against 72.4k (trained checkpoint).
-        // Round 5: the headline (parity family, f32, no cache) takes the same shape — it measures the same or better there (75.9k against
-        // 74.6k at 1,048,576 games, 77.5k against 76.9k at a full step) and 12 x 164 registers spill nothing where 16 x 128 spills 35.
-        if (!conv && nw == 16 && (fast || cfg_family(P.mcts) == 2) &&
-            debug_env("SYN_LANES") == nullptr) {
-            nw = 12;
-            if (want_slots > h->num_cus * 768) want_slots = h->num_cus * 768;
-        }
-        if ((nw == 4 || nw == 8 || nw == 12 || nw == 16) && h->cap <= LANE_MAX_CAP) {
-            int lgrid = (want_slots + 64 * nw - 1) / (64 * nw);
-            // (slots are rounded up to whole workgroups; the pool was allocated for a multiple of 1024 slabs)
-            const size_t need_path = (size_t)lgrid * nw * PATH_ENTRIES * sizeof(uint4);
-            if (need_path > h->path_bytes) {
-                if (h->d_path) (void)hipFree(h->d_path);
-                h->d_path = nullptr;
-                h->path_bytes = 0;
-                hipError_t pe = hipMalloc(&h->d_path, need_path);
-                if (pe != hipSuccess) return pe;
-                h->path_bytes = need_path;
-            }
-            EngineParams PL = P;
-            PL.path = h->d_path;
-            // a round ends once this many lanes of a wave stand on a leaf: 48 with the f32 tile; with the f16x2 tile (a quarter of the cost) waiting
-            // for all 64 measures +1-2 % (same box: 107.5k -> 108.7k games/s random-init, 65.3k -> 66.7k trained; 32: 100.5k / 60.8k)
-            PL.lane_thresh = f16x2 ? 64 : 48;
-            if (const char* ev = debug_env("SYN_LANE_THRESH")) PL.lane_thresh = std::atoi(ev);
-            if (PL.lane_thresh < 16 || PL.lane_thresh > 64) PL.lane_thresh = f16x2 ? 64 : 48;
-            PL.lane_thresh &= ~15;  // whole tiles
-            PL.debug_stub = 0;
-            if (PROF) { if (const char* ev = debug_env("SYN_ABLATE")) PL.debug_stub = std::atoi(ev); }
-            // Fpu::Func: 0 = every level takes its draws on the spot (a scan is ~220 issue slots since round 6); 1..64 = scans are
-            // deferred until that many lanes wait for one or nobody can move without one (rounds 4-5, when a scan was ~600: 64)
-            PL.nv = 0;
-            if (const char* ev = debug_env("SYN_SCAN_MIN")) PL.nv = std::atoi(ev);
-            if (PL.nv < 0 || PL.nv > 64) PL.nv = 0;
-#define SYN_LAUNCH_L(NW, FAST)                                                                                     \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes<MODE, COUNT, FAST, NW, PROF>;                                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                       \
-    }
-#define SYN_LAUNCH_LR(NW)                                                                                          \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes<MODE, COUNT, 2, NW, PROF && MODE == MODE_SELFPLAY && !COUNT, 0>;                                              \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
-    }
-#define SYN_LAUNCH_LC(NW, FAST)                                                                                    \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes<MODE, COUNT, FAST, NW, false, 2>;                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
-    }
-#define SYN_LAUNCH_LC16(NW, FAST)                                                                                  \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes<MODE, COUNT, FAST, NW, false, 4>;                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
-    }
-            // the reference's own self-play configuration (Fpu::Func folded at compile time: mcts.cuh cfg_family) has instantiations of
-            // its own at 8 and 16 waves
-            const bool ref_family = !conv && (!PROF || (MODE == MODE_SELFPLAY && !COUNT)) && cfg_family(P.mcts) == 2 && (nw == 8 || nw == 12 || nw == 16);
-            if (f16x2) {
-                // family 1 / 2 at every wave count, the runtime-switched configurations at 4 and 8 waves (nw was capped above)
-                const int fam = cfg_family(P.mcts);
-#define SYN_LAUNCH_LH(NW, FAST, PROFV)                                                                             \
-    {                                                                                                              \
-        auto k = selfplay_kernel_lanes<MODE, COUNT, FAST, NW, PROFV, 3>;                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)LaneLds<NW>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * NW), LaneLds<NW>::BYTES, h->stream, PL);                      \
-    }
-                constexpr bool PROFH = PROF && MODE == MODE_SELFPLAY && !COUNT;
-                if (fam == 2) {
-                    if (nw == 4) SYN_LAUNCH_LH(4, 2, false) else if (nw == 8) SYN_LAUNCH_LH(8, 2, false)
-                    else if (nw == 12) SYN_LAUNCH_LH(12, 2, false) else SYN_LAUNCH_LH(16, 2, false)
-                } else if (fast) {
-                    if (nw == 4) SYN_LAUNCH_LH(4, true, false) else if (nw == 8) SYN_LAUNCH_LH(8, true, false)
-                    else if (nw == 12) SYN_LAUNCH_LH(12, true, PROFH) else SYN_LAUNCH_LH(16, true, PROFH)
-                } else {
-                    if (nw == 4) SYN_LAUNCH_LH(4, false, false) else SYN_LAUNCH_LH(8, false, false)
-                }
-#undef SYN_LAUNCH_LH
-            } else
-            if (ref_family) {
-                if (nw == 8) SYN_LAUNCH_LR(8) else if (nw == 12) SYN_LAUNCH_LR(12) else SYN_LAUNCH_LR(16)
-            } else
-            if (conv16) {
-                if (nw == 8 && fast) SYN_LAUNCH_LC16(8, true)
-                else if (fast) SYN_LAUNCH_LC16(4, true)
-                else SYN_LAUNCH_LC16(4, false)
-            } else
-            if (conv) {
-                if (nw == 4) { if (fast) SYN_LAUNCH_LC(4, true) else SYN_LAUNCH_LC(4, false) }
-                else if (nw == 8) { if (fast) SYN_LAUNCH_LC(8, true) else SYN_LAUNCH_LC(8, false) }
-                else { if (fast) SYN_LAUNCH_LC(16, true) else SYN_LAUNCH_LC(16, false) }
-            } else
-            if (nw == 4) { if (fast) SYN_LAUNCH_L(4, true) else SYN_LAUNCH_L(4, false) }
-            else if (nw == 8) { if (fast) SYN_LAUNCH_L(8, true) else SYN_LAUNCH_L(8, false) }
-            else if (nw == 12) { if (fast) SYN_LAUNCH_L(12, true) else SYN_LAUNCH_L(12, false) }
-            else { if (fast) SYN_LAUNCH_L(16, true) else SYN_LAUNCH_L(16, false) }
-#undef SYN_LAUNCH_L
-#undef SYN_LAUNCH_LC
-#undef SYN_LAUNCH_LC16
-#undef SYN_LAUNCH_LR
-            h->last_shape = 4; h->last_grid = lgrid; h->last_threads = 64 * nw;
-            if (out_grid) *out_grid = -lgrid;  // negative: lane kernel (profile layout differs)
-            if (out_nt) *out_nt = 64 * nw;
-            return hipGetLastError();
-        }
-    }
-    int nq = 0;
-    {
-        int per_cu = (grid + h->num_cus - 1) / h->num_cus;
-        nq = per_cu <= 2 ? 0 : (per_cu >= 4 ? 4 : 3);
-        if (const char* ev = debug_env("SYN_QUADS")) nq = std::atoi(ev);
-        if (nq < 0 || nq == 1 || nq > 4) nq = 0;
-    }
-    if (nq >= 2) {
-        int qgrid = (grid + nq - 1) / nq;
-#define SYN_LAUNCH_Q(NQ, FAST)                                                                                     \
-    {                                                                                                              \
-        auto k = selfplay_kernel_quads<MODE, COUNT, FAST, NQ, PROF>;                                                    \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),                                       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)QuadLds<NQ>::BYTES);   \
-        if (e != hipSuccess) return e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(qgrid), dim3(256 * NQ), QuadLds<NQ>::BYTES, h->stream, P);                      \
-    }
-        if (nq == 2) { if (fast) SYN_LAUNCH_Q(2, true) else SYN_LAUNCH_Q(2, false) }
-        else if (nq == 3) { if (fast) SYN_LAUNCH_Q(3, true) else SYN_LAUNCH_Q(3, false) }
-        else { if (fast) SYN_LAUNCH_Q(4, true) else SYN_LAUNCH_Q(4, false) }
-#undef SYN_LAUNCH_Q
-        h->last_shape = 3; h->last_grid = qgrid; h->last_threads = 256 * nq;
-        if (out_grid) *out_grid = qgrid;
-        if (out_nt) *out_nt = 256 * nq;
-        return hipGetLastError();
-    }
-    if (grid <= h->num_cus) {
-        if (fast) SYN_LAUNCH(1, true) else SYN_LAUNCH(1, false)
-    } else {
-        if (fast) SYN_LAUNCH(2, true) else SYN_LAUNCH(2, false)
-    }
-#undef SYN_LAUNCH
-    h->last_shape = grid <= h->num_cus ? 1 : 2; h->last_grid = grid; h->last_threads = 256;
-    if (out_grid) *out_grid = grid;
-    if (out_nt) *out_nt = 256;
-    return hipGetLastError();
+};
+#undef SYN_ROW
+#undef SYN_QUAD
+#undef SYN_PC
+#undef SYN_CALL_LIST
+
+// The plan's instantiation; where a profile is requested and no profiled instantiation ships, the plain one. nullptr: not in the library.
+static const KernelEntry* find_kernel(const LaunchPlan& p) {
+    for (int prof = p.prof ? 1 : 0; prof >= 0; prof--)
+        for (const KernelEntry& e : g_kernels)
+            if (e.shape == p.shape && e.mode == p.mode && e.count == (int)p.count && e.fast == p.fast && e.n == p.n && e.prof == prof &&
+                e.policy == p.policy && e.tile == p.tile)
+                return &e;
+    return nullptr;
 }
 
-// MCTS over RolloutPolicy: always the lane-per-tree kernel (8 waves per workgroup), RolloutPolicy instead of the network
-static hipError_t launch_rollout_search(syn_engine* h, const EngineParams& P, int jobs) {
-    if (h->cap > LANE_MAX_CAP) return hipErrorInvalidValue;
-    const int nw = 8;
-    int want_slots = h->slots < jobs ? h->slots : jobs;
-    int lgrid = (want_slots + 64 * nw - 1) / (64 * nw);
-    if (lgrid < 1) lgrid = 1;
-    const size_t need_path = (size_t)lgrid * nw * PATH_ENTRIES * sizeof(uint4);
-    if (need_path > h->path_bytes) {
-        if (h->d_path) (void)hipFree(h->d_path);
-        h->d_path = nullptr;
-        h->path_bytes = 0;
-        hipError_t pe = hipMalloc(&h->d_path, need_path);
-        if (pe != hipSuccess) return pe;
-        h->path_bytes = need_path;
-    }
-    EngineParams PL = P;
-    PL.path = h->d_path;
-    PL.lane_thresh = 64;
-    PL.cache = nullptr;
-    auto k = selfplay_kernel_lanes<MODE_SEARCH, false, false, 8, false, 1>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)LaneLds<8>::BYTES);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(lgrid), dim3(64 * nw), LaneLds<8>::BYTES, h->stream, PL);
-    h->last_shape = 4; h->last_grid = lgrid; h->last_threads = 64 * nw;
-    return hipGetLastError();
+// the developer knobs of the launch selection (honoured with SYN_DEBUG=1 only: debug_env)
+static LaunchKnobs read_launch_knobs() {
+    LaunchKnobs k;
+    const auto num = [](const char* name, int& v) { if (const char* ev = debug_env(name)) v = std::atoi(ev); };
+    num("SYN_LANES", k.lanes); num("SYN_FREE", k.free_run); num("SYN_QUADS", k.quads);
+    num("SYN_LANE_THRESH", k.lane_thresh); num("SYN_SCAN_MIN", k.scan_min); num("SYN_ABLATE", k.ablate);
+#ifdef SYN_DEBUG_SHAPES
+    const auto flag = [](const char* name, int& v) { if (debug_env(name)) v = 1; };
+    num("SYN_PC", k.pc); num("SYN_PC_PRIO", k.pc_prio); flag("SYN_PC_STUB", k.pc_stub);
+    num("SYN_LANES2", k.lanes2); flag("SYN_L2_TILE", k.l2_tile);
+    num("SYN_POOL", k.pool); num("SYN_POOL_NW", k.pool_nw); num("SYN_POOL_FIRE", k.pool_fire); num("SYN_POOL_SCAN", k.pool_scan);
+#endif
+    return k;
+}
+
+// a device buffer that only grows: at least `need` bytes behind buf
+template <class T>
+static hipError_t ensure_device_buffer(T*& buf, size_t& have, size_t need) {
+    if (need <= have) return hipSuccess;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    have = 0;
+    hipError_t e = hipMalloc(&buf, need);
+    if (e == hipSuccess) have = need;
+    return e;
+}
+
+// Grows the buffers the plan needs, fills the EngineParams fields it fixes, looks its kernel up and launches it.
+static int launch_planned(syn_engine* h, const LaunchPlan& plan, EngineParams P) {
+    if (plan.error)
+        return fail(h, SYN_ERR_HIP, "launch failed: %s (this configuration runs in the lane-per-tree kernels only: at most %u nodes per tree, this engine: %u)",
+                    hipGetErrorString(hipErrorInvalidValue), LANE_MAX_CAP, h->cap);
+    const KernelEntry* k = find_kernel(plan);
+    if (!k)
+        return fail(h, SYN_ERR_UNSUPPORTED, "this library ships no kernel for launch shape %d with (mode %d, count %d, fast %d, n %d, prof %d, policy %d, tile %d)",
+                    plan.shape, plan.mode, (int)plan.count, plan.fast, plan.n, (int)plan.prof, plan.policy, plan.tile);
+    HIP_TRY(h, ensure_device_buffer(h->d_path, h->path_bytes, plan.path_entries * sizeof(uint4)));
+    HIP_TRY(h, ensure_device_buffer(h->d_vw, h->vw_bytes, plan.vw_bytes));
+    P.path = h->d_path;
+    P.vw_buf = h->d_vw;
+    P.lane_thresh = plan.lane_thresh;
+    P.nv = plan.nv;
+    P.debug_prio = plan.debug_prio;
+    P.debug_stub = plan.debug_stub;
+    if (plan.no_cache) P.cache = nullptr;
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->lds));
+    hipLaunchKernelGGL(k->fn, dim3(plan.grid), dim3(plan.threads), k->lds, h->stream, P);
+    h->last_shape = plan.shape; h->last_grid = plan.grid; h->last_threads = plan.threads;
+    if (plan.shape == 8) h->last_pool_trees = plan.pool_trees;
+    HIP_TRY(h, hipGetLastError());
+    return SYN_OK;
+}
+
+static int launch_engine(syn_engine* h, const EngineParams& P, int jobs, int mode, bool count, bool prof) {
+    LaunchQuery q;
+    q.num_cus = h->num_cus;
+    q.slots = h->slots;
+    q.jobs = jobs;
+    q.cap = h->cap;
+    q.net_kind = h->net_kind;
+    q.f16 = h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
+    q.pool_trees = h->pool_trees;
+    q.mode = mode;
+    q.count = count;
+    q.prof = prof;
+    q.fpu = P.mcts.fpu;
+    q.noise = P.mcts.noise;
+    q.family = cfg_family(P.mcts);
+    return launch_planned(h, plan_launch(q, read_launch_knobs()), P);
 }
 
 extern "C" {
@@ -1698,8 +1328,8 @@ static int mcts_search_impl(syn_engine* h, const syn_mcts_config* cfg, const uin
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     P.base_seed = seed;
     P.first_game = 0;
-    if (rollout) HIP_TRY(h, launch_rollout_search(h, P, n));
-    else HIP_TRY(h, (launch_engine<MODE_SEARCH, false>(h, P, n)));
+    if (int rc = rollout ? launch_planned(h, plan_rollout_search(h->slots, n, h->cap), P) : launch_engine(h, P, n, MODE_SEARCH, false, false))
+        return rc;
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     HIP_TRY(h, hipMemcpyAsync(results, d_res, nb * sizeof(DevSearchResult), hipMemcpyDeviceToHost, h->stream));
     int kerr = 0;
@@ -1898,7 +1528,6 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
     HIP_TRY(h, hipMemsetAsync(h->d_plies, 0, (size_t)n_games * 4, h->stream));  // plies = 0: a game that never started (syn_cancel)
     // SYN_PROFILE=1: diagnostic build of the kernel with s_memtime stamps around each phase (never timed/benched)
     const bool prof = !counters && debug_env("SYN_PROFILE") != nullptr;
-    int pgrid = 0, pnt = 0;
     unsigned long long* d_prof = nullptr;
     if (prof) {
         HIP_TRY(h, hipMalloc(&d_prof, (size_t)4096 * 16 * 6 * 8));
@@ -1906,9 +1535,8 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
         P.prof = d_prof;
     }
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    if (prof) HIP_TRY(h, (launch_engine<MODE_SELFPLAY, false, true>(h, P, n_games, &pgrid, &pnt)));
-    else if (counters) HIP_TRY(h, (launch_engine<MODE_SELFPLAY, true>(h, P, n_games)));
-    else HIP_TRY(h, (launch_engine<MODE_SELFPLAY, false>(h, P, n_games)));
+    if (int rc = launch_engine(h, P, n_games, MODE_SELFPLAY, counters != nullptr, prof)) return rc;
+    const int pgrid = h->last_grid, pnt = h->last_threads;
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     if (prof) {
         HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -1943,8 +1571,8 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
                             "tree waves=%.0f: per visit: wait=%.0f C=%.0f A+submit=%.0f cycles, explores finished=%.2f, visits per wave=%.0f\n",
                     pgrid, nm, 100.0 * mb / (mb + mw + 1e-9), mb / (mt + 1e-9), mt / (nm + 1e-9), ntw, tw / (tr + 1e-9), tc / (tr + 1e-9),
                     ta / (tr + 1e-9), tf / (tr + 1e-9), tr / (ntw + 1e-9));
-        } else if (pgrid < 0) {  // lane kernel: per wave [A, B, C, move, rounds, tiles, active lanes, evals, then the LP_* fields]
-            int nwv = -pgrid * (pnt / 64);
+        } else if (h->last_shape == 4) {  // lane kernel: per wave [A, B, C, move, rounds, tiles, active lanes, evals, then the LP_* fields]
+            int nwv = pgrid * (pnt / 64);
             constexpr int F = LP_FIELDS;
             std::vector<unsigned long long> hp((size_t)nwv * F);
             HIP_TRY(h, hipMemcpy(hp.data(), d_prof, hp.size() * 8, hipMemcpyDeviceToHost));
@@ -1956,7 +1584,7 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
             fprintf(stderr, "[syn profile lanes] grid=%d nt=%d waves=%d rounds/wave=%.0f | cycles per round: A=%.0f B=%.0f C: children=%.0f "
                             "solver walk=%.0f sweep=%.0f move=%.0f total=%.0f | per round: tiles=%.3f explores finished=%.2f evals=%.2f "
                             "(%.2f per tile) | cycles per finished explore=%.0f\n",
-                    -pgrid, pnt, nwv, s[4] / nwv, s[0] / s[4], s[1] / s[4], s[6] / s[4], s[7] / s[4], s[2] / s[4], s[3] / s[4],
+                    pgrid, pnt, nwv, s[4] / nwv, s[0] / s[4], s[1] / s[4], s[6] / s[4], s[7] / s[4], s[2] / s[4], s[3] / s[4],
                     (s[0] + s[1] + s[2] + s[3] + s[6] + s[7]) / s[4], s[5] / s[4], s[8] / s[4], s[9] / s[4], s[9] / s[5],
                     (s[0] + s[1] + s[2] + s[3] + s[6] + s[7]) / s[8]);
             const double R = s[4];  // rounds (all waves)

@@ -8,17 +8,10 @@
 
 #include "../../include/synthesis_amd.h"
 #include "lane_kernel.cuh"
+#include "lane_instances.h"
 
 namespace syn {
-#define SYN_CONV_LANES(MODE, COUNT)                                                          \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 4, false, 2>(EngineParams);   \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 4, false, 2>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 8, false, 2>(EngineParams);   \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 8, false, 2>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, true, 16, false, 2>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes<MODE, COUNT, false, 16, false, 2>(EngineParams);
-SYN_CONV_LANES(MODE_SEARCH, false)
-SYN_CONV_LANES(MODE_SELFPLAY, false)
-SYN_CONV_LANES(MODE_SELFPLAY, true)
-#undef SYN_CONV_LANES
+#define SYN_X(MODE, COUNT, FAST, NW, PROF, POLICY) template __global__ void selfplay_kernel_lanes<MODE, COUNT, FAST, NW, PROF, POLICY>(EngineParams);
+SYN_LANES_CONV_LIST(SYN_X)
+#undef SYN_X
 }  // namespace syn

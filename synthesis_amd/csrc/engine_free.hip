@@ -6,14 +6,10 @@
 
 #include "../../include/synthesis_amd.h"
 #include "free_kernel.cuh"
+#include "lane_instances.h"
 
 namespace syn {
-#define SYN_FREE(MODE, COUNT)                                                               \
-    template __global__ void selfplay_kernel_free<MODE, COUNT, true, false>(EngineParams);  \
-    template __global__ void selfplay_kernel_free<MODE, COUNT, false, false>(EngineParams);
-SYN_FREE(MODE_SEARCH, false)
-SYN_FREE(MODE_SELFPLAY, false)
-SYN_FREE(MODE_SELFPLAY, true)
-#undef SYN_FREE
-template __global__ void selfplay_kernel_free<MODE_SELFPLAY, false, true, true>(EngineParams);
+#define SYN_X(MODE, COUNT, FAST, PROF) template __global__ void selfplay_kernel_free<MODE, COUNT, FAST, PROF>(EngineParams);
+SYN_FREE_LIST(SYN_X)
+#undef SYN_X
 }  // namespace syn

@@ -7,20 +7,10 @@
 
 #include "../../include/synthesis_amd.h"
 #include "lane2_kernel.cuh"
+#include "lane_instances.h"
 
 namespace syn {
-#define SYN_LANES2(MODE, COUNT)                                                               \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 8, 0>(EngineParams);   \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 8, 0>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 8, 2>(EngineParams);   \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 8, 2>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 12, 0>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 12, 0>(EngineParams); \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, true, 12, 2>(EngineParams);  \
-    template __global__ void selfplay_kernel_lanes2<MODE, COUNT, false, 12, 2>(EngineParams);
-template __global__ void selfplay_kernel_lanes2<MODE_SELFPLAY, false, true, 8, 0, 1>(EngineParams);
-SYN_LANES2(MODE_SEARCH, false)
-SYN_LANES2(MODE_SELFPLAY, false)
-SYN_LANES2(MODE_SELFPLAY, true)
-#undef SYN_LANES2
+#define SYN_X(MODE, COUNT, FAST, NW, POLICY, TILE) template __global__ void selfplay_kernel_lanes2<MODE, COUNT, FAST, NW, POLICY, TILE>(EngineParams);
+SYN_LANES2_LIST(SYN_X)
+#undef SYN_X
 }  // namespace syn

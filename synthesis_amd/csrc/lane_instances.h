@@ -1,7 +1,8 @@
-// synthesis_amd — which instantiations of selfplay_kernel_lanes (lane_kernel.cuh) for Connect4Net (POLICY 0) and RolloutPolicy
-// (POLICY 1) the library ships, as X-macro lists: engine.hip declares them `extern template`, engine_lanes_fast.hip (the compile-
-// time-folded parity configuration family) and engine_lanes_gen.hip (the runtime-switched one) define them. Separate translation
-// units only so that `make -j` builds them beside engine.hip.
+// synthesis_amd — which instantiations of the self-play kernels the library ships, as X-macro lists: the ONE table of what exists. The side
+// translation units define them (engine_lanes_fast.hip: the compile-time-folded parity configuration family, engine_lanes_gen.hip: the
+// runtime-switched one, ...; separate units only so that `make -j` builds them beside engine.hip); engine.hip declares them `extern
+// template` and expands the same lists into the table its launches are looked up in, so launching code cannot name an instantiation that is
+// not listed here. Which entry a call takes is decided in launch_plan.hpp; tests/test_launch_plan.py checks that every plan is listed.
 //   X(MODE, COUNT, FAST, NW, PROF, POLICY)      FAST: 0 runtime-switched, 1 parity family, 2 the reference's self-play configuration
 //                                                (mcts.cuh CfgView; engine_lanes_ref.hip holds the third list)
 #pragma once
@@ -73,3 +74,35 @@
     X(MODE_SELFPLAY, false, false, 4, false, 4)                                                                  \
     X(MODE_SELFPLAY, true, true, 4, false, 4) X(MODE_SELFPLAY, true, true, 8, false, 4)                          \
     X(MODE_SELFPLAY, true, false, 4, false, 4)
+// Connect4ConvNet in f32 (POLICY 2, convnet.cuh; engine_conv.hip): both runtime values of FAST at 4, 8 and 16 waves
+#define SYN_LANES_CONV_LIST(X) \
+    X(MODE_SEARCH, false, true, 4, false, 2) X(MODE_SEARCH, false, false, 4, false, 2) \
+    X(MODE_SEARCH, false, true, 8, false, 2) X(MODE_SEARCH, false, false, 8, false, 2) \
+    X(MODE_SEARCH, false, true, 16, false, 2) X(MODE_SEARCH, false, false, 16, false, 2) \
+    X(MODE_SELFPLAY, false, true, 4, false, 2) X(MODE_SELFPLAY, false, false, 4, false, 2) \
+    X(MODE_SELFPLAY, false, true, 8, false, 2) X(MODE_SELFPLAY, false, false, 8, false, 2) \
+    X(MODE_SELFPLAY, false, true, 16, false, 2) X(MODE_SELFPLAY, false, false, 16, false, 2) \
+    X(MODE_SELFPLAY, true, true, 4, false, 2) X(MODE_SELFPLAY, true, false, 4, false, 2) \
+    X(MODE_SELFPLAY, true, true, 8, false, 2) X(MODE_SELFPLAY, true, false, 8, false, 2) \
+    X(MODE_SELFPLAY, true, true, 16, false, 2) X(MODE_SELFPLAY, true, false, 16, false, 2)
+// The free-running four-trees-per-wave kernels (free_kernel.cuh; engine_free.hip):  X(MODE, COUNT, FAST, PROF)
+#define SYN_FREE_LIST(X) \
+    X(MODE_SEARCH, false, true, false) X(MODE_SEARCH, false, false, false) \
+    X(MODE_SELFPLAY, false, true, false) X(MODE_SELFPLAY, false, false, false) \
+    X(MODE_SELFPLAY, true, true, false) X(MODE_SELFPLAY, true, false, false) \
+    X(MODE_SELFPLAY, false, true, true)
+// (DEBUG_SHAPES=1 builds) the two-trees-per-lane kernels (lane2_kernel.cuh; engine_lanes2.hip):  X(MODE, COUNT, FAST, NW, POLICY, TILE)
+#define SYN_LANES2_LIST(X) \
+    X(MODE_SEARCH, false, true, 8, 0, 0) X(MODE_SEARCH, false, false, 8, 0, 0) \
+    X(MODE_SEARCH, false, true, 8, 2, 0) X(MODE_SEARCH, false, false, 8, 2, 0) \
+    X(MODE_SEARCH, false, true, 12, 0, 0) X(MODE_SEARCH, false, false, 12, 0, 0) \
+    X(MODE_SEARCH, false, true, 12, 2, 0) X(MODE_SEARCH, false, false, 12, 2, 0) \
+    X(MODE_SELFPLAY, false, true, 8, 0, 0) X(MODE_SELFPLAY, false, false, 8, 0, 0) \
+    X(MODE_SELFPLAY, false, true, 8, 2, 0) X(MODE_SELFPLAY, false, false, 8, 2, 0) \
+    X(MODE_SELFPLAY, false, true, 12, 0, 0) X(MODE_SELFPLAY, false, false, 12, 0, 0) \
+    X(MODE_SELFPLAY, false, true, 12, 2, 0) X(MODE_SELFPLAY, false, false, 12, 2, 0) \
+    X(MODE_SELFPLAY, true, true, 8, 0, 0) X(MODE_SELFPLAY, true, false, 8, 0, 0) \
+    X(MODE_SELFPLAY, true, true, 8, 2, 0) X(MODE_SELFPLAY, true, false, 8, 2, 0) \
+    X(MODE_SELFPLAY, true, true, 12, 0, 0) X(MODE_SELFPLAY, true, false, 12, 0, 0) \
+    X(MODE_SELFPLAY, true, true, 12, 2, 0) X(MODE_SELFPLAY, true, false, 12, 2, 0) \
+    X(MODE_SELFPLAY, false, true, 8, 0, 1)
