@@ -126,8 +126,6 @@ struct syn_engine {
     int cache_log2 = 0;
     unsigned long long* d_cache_stats = nullptr;
     unsigned long long last_cache_hits = 0, last_cache_misses = 0;
-    void* d_train_data = nullptr;  // syn_train_set_data: [my u64 n][op u64 n][pi 9 f32 n][v 3 f32 n]
-    size_t train_data_cap = 0, train_data_n = 0;
     // the device-resident replay buffer (syn_replay_*; replay_kernels.cuh): sections my | op | gid | pi | v of replay_cap positions each
     // in ONE allocation; d_replay_alt is the keep-window's second buffer (same size, allocated when a keep first drops something)
     unsigned char* d_replay = nullptr;
@@ -158,30 +156,53 @@ struct syn_engine {
     std::string err;
     float last_kernel_ms = 0.0f;
     int last_launches = 0;
-    // learner state (syn_trainer_init): parameters, Adam moments, gradient + loss scratch
-    float* d_tw = nullptr;
-    float* d_tm = nullptr;
-    float* d_tv = nullptr;
-    float* d_tgrad = nullptr;
-    float* d_tloss = nullptr;
-    float* d_twimg = nullptr;  // the trainer's weights in the inference fragment order (forward A operands; = the published image)
-    float* d_ttimg = nullptr;  // ... and transposed fragments for the activation gradients (train_mfma.cuh)
-    float* d_timg2 = nullptr;  // the second buffer of both images for the persistent epoch kernel (train_epoch.cuh): [fwd][transposed]
-    unsigned* d_tsync = nullptr;  // its arrival counter and status word
-    float* d_tsnap = nullptr;     // snapshot of [w][m][v][fwd image][transposed image] taken before an epoch launch (restored if it aborts)
-    long long train_step = 0;
-    bool epoch_barrier_checked = false;  // syn_trainer_init's self-check of the epoch kernel's one-XCD barrier has run on this engine
-    bool epoch_device_scope = false;     // ... and it failed (or is running its second half): the epoch kernel uses the device-scope barrier
-    long long epoch_fallbacks = 0;  // syn_train_epoch calls whose persistent kernel gave up and ran through the queued launches
-    float* d_cxbuf = nullptr;       // Connect4ConvNet learner on four workgroups: the exchange buffer (train_conv_mfma.cuh ConvMwGeom)
-    bool conv_mw_checked = false;   // syn_trainer_init_conv's self-check of that kernel against the one-workgroup kernel has run
-    bool conv_mw_disabled = false;  // ... and it failed: this engine keeps the one-workgroup epoch kernel
-    int conv_mw_force = -1;         // self-check only: 0 = one workgroup, 1 = four
-    DevTrainHyper train_hp{};
-    bool has_trainer = false;
-    int trainer_kind = 0;  // 0 = Connect4Net (train_mfma.cuh / train_epoch.cuh), 1 = Connect4ConvNet (train_conv_mfma.cuh)
-    int train_bf16 = 0;    // Connect4ConvNet learner: 1 = the bf16 matrix-core variant of the gradient step (syn_trainer_set_precision)
+    // The learner (syn_trainer_init / syn_trainer_init_conv). Both networks' trainers share it; the buffers are sized for Connect4Net, the
+    // larger one (learner_buffers).
+    struct Learner {
+        // parameters, Adam moments, gradient + loss scratch
+        float* d_tw = nullptr;
+        float* d_tm = nullptr;
+        float* d_tv = nullptr;
+        float* d_tgrad = nullptr;
+        float* d_tloss = nullptr;
+        float* d_twimg = nullptr;  // the trainer's weights in the inference fragment order (forward A operands; = the published image)
+        float* d_ttimg = nullptr;  // ... and transposed fragments for the activation gradients (train_mfma.cuh)
+        float* d_timg2 = nullptr;  // the second buffer of both images for the persistent epoch kernel (train_epoch.cuh): [fwd][transposed]
+        unsigned* d_tsync = nullptr;  // its arrival counter and status word
+        float* d_tsnap = nullptr;     // snapshot of [w][m][v][fwd image][transposed image] taken before an epoch launch (restored if it aborts)
+        float* d_cxbuf = nullptr;     // Connect4ConvNet learner on four workgroups: the exchange buffer (train_conv_mfma.cuh ConvMwGeom)
+        void* d_train_data = nullptr;  // syn_train_set_data: [my u64 n][op u64 n][pi 9 f32 n][v 3 f32 n] (TrainSections)
+        size_t train_data_cap = 0, train_data_n = 0;
+        long long train_step = 0;
+        DevTrainHyper train_hp{};
+        bool has_trainer = false;
+        int trainer_kind = 0;  // 0 = Connect4Net (train_mfma.cuh / train_epoch.cuh), 1 = Connect4ConvNet (train_conv_mfma.cuh)
+        int train_bf16 = 0;    // Connect4ConvNet learner: 1 = the bf16 matrix-core variant of the gradient step (syn_trainer_set_precision)
+        bool epoch_barrier_checked = false;  // syn_trainer_init's self-check of the epoch kernel's one-XCD barrier has run on this engine
+        bool epoch_device_scope = false;     // ... and it failed (or is running its second half): the epoch kernel uses the device-scope barrier
+        long long epoch_fallbacks = 0;  // syn_train_epoch calls whose persistent kernel gave up and ran through the queued launches
+        bool conv_mw_checked = false;   // syn_trainer_init_conv's self-check of the four-workgroup kernel against the one-workgroup kernel has run
+        bool conv_mw_disabled = false;  // ... and it failed: this engine keeps the one-workgroup epoch kernel
+        int conv_mw_force = -1;         // self-check only: 0 = one workgroup, 1 = four
+    } learner;
 };
+
+// The learner's eleven device buffers: the one description used to allocate them (alloc_trainer_buffers: all of them or none) and to
+// free them (syn_engine_destroy).
+struct LearnerBuffers {
+    struct {
+        void** p;
+        size_t bytes;
+    } all[11];
+};
+static LearnerBuffers learner_buffers(syn_engine::Learner& L) {
+    const size_t bytes = (size_t)TrainGeom::NUM_PARAMS * 4;
+    const size_t img = (size_t)MlpGeom::IMG_FLOATS * 4, timg = (size_t)TrainImg::T_FLOATS * 4;
+    const auto at = [](auto& field) { return reinterpret_cast<void**>(&field); };
+    return {{{at(L.d_tw), bytes}, {at(L.d_tm), bytes}, {at(L.d_tv), bytes}, {at(L.d_tgrad), bytes}, {at(L.d_tloss), 64},
+             {at(L.d_twimg), img}, {at(L.d_ttimg), timg}, {at(L.d_timg2), img + timg}, {at(L.d_tsync), 256},
+             {at(L.d_tsnap), 3 * bytes + img + timg}, {at(L.d_cxbuf), (size_t)ConvMwGeom::FLOATS * 4}}};
+}
 
 static int fail(syn_engine* h, int code, const char* fmt, ...) {
     char buf[512];
@@ -578,7 +599,7 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
-    hipFree(h->d_train_data);
+    hipFree(h->learner.d_train_data);
     hipFree(h->d_replay);
     hipFree(h->d_replay_alt);
     hipFree(h->d_cache);
@@ -592,17 +613,8 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_root_nodes);
     hipFree(h->d_final);
     hipFree(h->d_scratch);
-    hipFree(h->d_tw);
-    hipFree(h->d_tm);
-    hipFree(h->d_tv);
-    hipFree(h->d_tgrad);
-    hipFree(h->d_tloss);
-    hipFree(h->d_twimg);
-    hipFree(h->d_ttimg);
-    hipFree(h->d_timg2);
-    hipFree(h->d_tsync);
-    hipFree(h->d_tsnap);
-    hipFree(h->d_cxbuf);
+    const LearnerBuffers learner_bufs = learner_buffers(h->learner);
+    for (const auto& b : learner_bufs.all) hipFree(*b.p);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1705,46 +1717,135 @@ int syn_cancel(syn_engine* h) {
     return SYN_OK;
 }
 
-// The learner's device buffers (shared by both networks' trainers; sized for Connect4Net, the larger one): all of them or none —
-// a failed allocation frees what was taken, so that a retry starts from scratch instead of skipping the allocation block.
+// ------------------------------------------------------------------------------------------------ learner
+// Every learner entry point opens with this: the handle, then the learner. (Its own argument check and the selection of the engine's
+// device follow in the entry point, in the order its errors have always had.)
+static int learner_check(syn_engine* h) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!h->learner.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    return SYN_OK;
+}
+
+// the developer knobs of the learner (honoured with SYN_DEBUG=1 only: debug_env), read once per process where one is first needed: the
+// first syn_train_epoch or gradient launch, which is inside the first syn_trainer_init*'s self-check.
+// (SYN_TRAIN_FORCE_ABORT is not among them: epoch_force_abort)
+struct LearnerKnobs {
+    bool queued;        // SYN_TRAIN_QUEUED=1: syn_train_epoch keeps the two launches per step (A/B, same bits)
+    bool profile;       // SYN_TRAIN_PROFILE=1: diagnostic stamps of the kernels' phases, printed to stderr
+    bool device_scope;  // SYN_TRAIN_DEVICE_SCOPE=1: the epoch kernels use the device-scope barrier
+    bool conv_mw_off;   // SYN_TRAIN_CONV_MW=0: the conv epoch runs in the one-workgroup kernel
+};
+static const LearnerKnobs& learner_knobs() {
+    static const LearnerKnobs knobs = [] {
+        const char* mw = debug_env("SYN_TRAIN_CONV_MW");
+        return LearnerKnobs{debug_env("SYN_TRAIN_QUEUED") != nullptr, debug_env("SYN_TRAIN_PROFILE") != nullptr,
+                            debug_env("SYN_TRAIN_DEVICE_SCOPE") != nullptr, mw && std::atoi(mw) == 0};
+    }();
+    return knobs;
+}
+// test hook, read at every syn_train_epoch call: the persistent kernel's result is thrown away and the recovery path taken
+static bool epoch_force_abort() { return debug_env("SYN_TRAIN_FORCE_ABORT") != nullptr; }
+
+static size_t learner_param_bytes(int kind) { return (size_t)(kind == 1 ? ConvGeom::NUM_PARAMS : TrainGeom::NUM_PARAMS) * 4; }
+
+// All of the learner's device buffers or none: a failed allocation frees what was taken, so that a retry starts from scratch instead
+// of skipping the allocation block.
 static int alloc_trainer_buffers(syn_engine* h) {
-    if (h->d_tw) return SYN_OK;
-    const size_t bytes = (size_t)TrainGeom::NUM_PARAMS * 4;
-    const size_t img = (size_t)MlpGeom::IMG_FLOATS * 4, timg = (size_t)TrainImg::T_FLOATS * 4;
-    struct { void** p; size_t n; } want[] = {
-        {reinterpret_cast<void**>(&h->d_tw), bytes},      {reinterpret_cast<void**>(&h->d_tm), bytes},
-        {reinterpret_cast<void**>(&h->d_tv), bytes},      {reinterpret_cast<void**>(&h->d_tgrad), bytes},
-        {reinterpret_cast<void**>(&h->d_tloss), 64},      {reinterpret_cast<void**>(&h->d_twimg), img},
-        {reinterpret_cast<void**>(&h->d_ttimg), timg},    {reinterpret_cast<void**>(&h->d_timg2), img + timg},
-        {reinterpret_cast<void**>(&h->d_tsync), 256},     {reinterpret_cast<void**>(&h->d_tsnap), 3 * bytes + img + timg},
-        {reinterpret_cast<void**>(&h->d_cxbuf), (size_t)ConvMwGeom::FLOATS * 4},
-    };
-    for (auto& w : want) {
-        hipError_t e = hipMalloc(w.p, w.n);
+    static_assert(ConvGeom::NUM_PARAMS <= TrainGeom::NUM_PARAMS, "trainer buffers are sized for Connect4Net");
+    auto& L = h->learner;
+    if (L.d_tw) return SYN_OK;
+    const LearnerBuffers want = learner_buffers(L);
+    for (const auto& w : want.all) {
+        hipError_t e = hipMalloc(w.p, w.bytes);
         if (e != hipSuccess) {
-            for (auto& u : want) {
+            for (const auto& u : want.all) {
                 if (*u.p) (void)hipFree(*u.p);
                 *u.p = nullptr;
             }
-            h->has_trainer = false;
+            L.has_trainer = false;
             return fail(h, SYN_ERR_HIP, "hipMalloc(trainer buffers) failed: %s", hipGetErrorString(e));
         }
     }
     return SYN_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ learner step
-// (re)load the Connect4Net learner's state: parameters, zero moments, both fragment images, step counter
-static int trainer_load_state(syn_engine* h, const float* blob, const std::vector<float>& img, const std::vector<float>& timg) {
-    const size_t bytes = (size_t)TrainGeom::NUM_PARAMS * 4;
-    HIP_TRY(h, hipMemcpyAsync(h->d_twimg, img.data(), img.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_ttimg, timg.data(), timg.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_tw, blob, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_tm, 0, bytes, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_tv, 0, bytes, h->stream));
+// The learner of network `kind` at its start: (Connect4Net) both fragment images uploaded, then the parameters, zero moments and
+// gradients (all three over the buffers' whole size, whichever network used them before), step 0.
+struct LearnerStart {
+    int kind;
+    const float* blob;
+    const std::vector<float>* img;   // Connect4Net: the forward and the transposed fragment image of `blob`; else NULL
+    const std::vector<float>* timg;
+};
+static int learner_load_state(syn_engine* h, const LearnerStart& s) {
+    auto& L = h->learner;
+    const size_t cap_bytes = (size_t)TrainGeom::NUM_PARAMS * 4;
+    if (s.kind == 0) {
+        HIP_TRY(h, hipMemcpyAsync(L.d_twimg, s.img->data(), s.img->size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(L.d_ttimg, s.timg->data(), s.timg->size() * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(L.d_tw, s.blob, learner_param_bytes(s.kind), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(L.d_tm, 0, cap_bytes, h->stream));
+    HIP_TRY(h, hipMemsetAsync(L.d_tv, 0, cap_bytes, h->stream));
+    HIP_TRY(h, hipMemsetAsync(L.d_tgrad, 0, cap_bytes, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->train_step = 0;
+    L.train_step = 0;
     return SYN_OK;
+}
+
+// Optimiser step `step`'s (1-based) bias corrections folded into the two scalars the Adam kernels take, in double on the host like
+// libtorch.
+struct AdamScalars {
+    float step_size, inv_sqrt_bc2;
+};
+static AdamScalars adam_scalars(const DevTrainHyper& hp, float lr, long long step) {
+    const double bc1 = 1.0 - std::pow((double)hp.beta1, (double)step);
+    const double bc2 = 1.0 - std::pow((double)hp.beta2, (double)step);
+    return {(float)((double)lr / bc1), (float)(1.0 / std::sqrt(bc2))};
+}
+
+// The start-up self-checks of the two learners run eight steps of batch 8 over this synthetic data set of 64 positions.
+struct SelfCheckBatch {
+    static constexpr int N = 64, STEPS = 8, B = 8;
+    std::vector<uint64_t> my, op;
+    std::vector<float> tpi, tv;
+    std::vector<int32_t> perm;
+};
+static SelfCheckBatch self_check_batch() {
+    using S = SelfCheckBatch;
+    S b{std::vector<uint64_t>(S::N), std::vector<uint64_t>(S::N), std::vector<float>((size_t)S::N * 9, 1.0f / 9.0f),
+        std::vector<float>((size_t)S::N * 3, 0.0f), std::vector<int32_t>(S::STEPS * S::B)};
+    for (int i = 0; i < S::N; i++) {
+        b.my[i] = (0x0000040810204081ull * (uint64_t)(i % 7 + 1)) & 0x00003F7EFDFBF7EFull & ~(0x7Full << (7 * (i % 9)));
+        b.op[i] = (0x7Full << (7 * (i % 9))) & (0x0101010101010101ull * (uint64_t)(i % 5 + 1));
+        b.op[i] &= ~b.my[i];
+        b.tv[(size_t)i * 3 + i % 3] = 1.0f;
+    }
+    for (int i = 0; i < S::STEPS * S::B; i++) b.perm[i] = (i * 37) % S::N;
+    return b;
+}
+// The two-mode loop of a self-check: from the caller's state `start`, mode 0 then mode 1 run the synthetic epoch, the weights are
+// read and the caller's state is put back. A mode is the barrier for Connect4Net (1 = device scope) and the kernel for Connect4ConvNet
+// (0 = one workgroup, 1 = four). Returns whether all of it could run (h->err says what could not); *same_bits: it could, and the two
+// modes left the same weights bit for bit.
+static bool learner_self_check(syn_engine* h, const LearnerStart& start, bool* same_bits) {
+    auto& L = h->learner;
+    const SelfCheckBatch b = self_check_batch();
+    const size_t nw = learner_param_bytes(start.kind) / 4;
+    std::vector<float> w[2] = {std::vector<float>(nw), std::vector<float>(nw)};
+    bool ok = true;
+    for (int mode = 0; mode < 2 && ok; mode++) {
+        if (start.kind == 0) L.epoch_device_scope = mode == 1;
+        else L.conv_mw_force = mode;
+        ok = syn_train_set_data(h, b.my.data(), b.op.data(), b.tpi.data(), b.tv.data(), b.N) == SYN_OK &&
+             syn_train_epoch(h, b.perm.data(), b.STEPS, b.B, 1e-3f, nullptr) == SYN_OK &&
+             syn_trainer_get_state(h, w[mode].data(), nullptr, nullptr, nullptr, nullptr) == SYN_OK && learner_load_state(h, start) == SYN_OK;
+    }
+    L.conv_mw_force = -1;
+    L.train_step = 0;
+    L.train_data_n = 0;   // the synthetic batch replaced whatever syn_train_set_data had uploaded: the caller uploads again (once per engine)
+    *same_bits = ok && std::memcmp(w[0].data(), w[1].data(), nw * 4) == 0;
+    return ok;
 }
 
 int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const syn_train_config* cfg) {
@@ -1753,10 +1854,9 @@ int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const sy
     if (n_floats != (size_t)TrainGeom::NUM_PARAMS)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4Net has %d parameters, got %zu", TrainGeom::NUM_PARAMS, n_floats);
     HIP_TRY(h, hipSetDevice(h->device));
-    {
-        const int rc = alloc_trainer_buffers(h);
-        if (rc != SYN_OK) return rc;
-    }
+    int rc = alloc_trainer_buffers(h);
+    if (rc != SYN_OK) return rc;
+    auto& L = h->learner;
     // the two fragment-order images the matrix-core learner reads its A operands from (train_mfma.cuh); adam_image_kernel
     // keeps them in step with the canonical weights afterwards
     std::vector<float> img, timg((size_t)TrainImg::T_FLOATS, 0.0f);
@@ -1767,39 +1867,21 @@ int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const sy
         if (img[(size_t)fwd] != blob[p]) return fail(h, SYN_ERR_HIP, "internal: image slot table disagrees with build_weight_image at %d", p);
         if (tr >= 0) timg[(size_t)tr] = blob[p];
     }
-    int rc = trainer_load_state(h, blob, img, timg);
+    const LearnerStart start{0, blob, &img, &timg};
+    rc = learner_load_state(h, start);
     if (rc != SYN_OK) return rc;
-    h->train_hp = DevTrainHyper{cfg->weight_decay, cfg->policy_weight, cfg->value_weight, cfg->beta1, cfg->beta2, cfg->eps};
-    h->has_trainer = true;
-    h->trainer_kind = 0;
-    h->train_bf16 = 0;
+    L.train_hp = DevTrainHyper{cfg->weight_decay, cfg->policy_weight, cfg->value_weight, cfg->beta1, cfg->beta2, cfg->eps};
+    L.has_trainer = true;
+    L.trainer_kind = 0;
+    L.train_bf16 = 0;
     // ---- the epoch kernel's one-XCD step barrier rests on observed hardware behaviour (train_epoch.cuh: `buffer_inv sc0` empties
     //      the vector L1 outside threadgroup-split mode). Once per engine: eight steps on a synthetic batch through that barrier and
     //      through the device-scope barrier from the same state; any differing bit switches this engine to the device-scope barrier.
-    if (!h->epoch_barrier_checked) {
-        h->epoch_barrier_checked = true;
-        const int n = 64, steps = 8, B = 8;
-        std::vector<uint64_t> my(n), op(n);
-        std::vector<float> tpi((size_t)n * 9, 1.0f / 9.0f), tv((size_t)n * 3, 0.0f);
-        std::vector<int32_t> perm(steps * B);
-        for (int i = 0; i < n; i++) {
-            my[i] = (0x0000040810204081ull * (uint64_t)(i % 7 + 1)) & 0x00003F7EFDFBF7EFull & ~(0x7Full << (7 * (i % 9)));
-            op[i] = (0x7Full << (7 * (i % 9))) & (0x0101010101010101ull * (uint64_t)(i % 5 + 1));
-            op[i] &= ~my[i];
-            tv[(size_t)i * 3 + i % 3] = 1.0f;
-        }
-        for (int i = 0; i < steps * B; i++) perm[i] = (i * 37) % n;
-        std::vector<float> wa((size_t)TrainGeom::NUM_PARAMS), wb((size_t)TrainGeom::NUM_PARAMS);
-        bool ok = true;
-        for (int mode = 0; mode < 2 && ok; mode++) {
-            h->epoch_device_scope = mode == 1;
-            ok = syn_train_set_data(h, my.data(), op.data(), tpi.data(), tv.data(), n) == SYN_OK &&
-                 syn_train_epoch(h, perm.data(), steps, B, 1e-3f, nullptr) == SYN_OK &&
-                 syn_trainer_get_state(h, mode == 0 ? wa.data() : wb.data(), nullptr, nullptr, nullptr, nullptr) == SYN_OK &&
-                 trainer_load_state(h, blob, img, timg) == SYN_OK;
-        }
-        h->epoch_device_scope = !(ok && std::memcmp(wa.data(), wb.data(), wa.size() * 4) == 0);
-        h->train_data_n = 0;   // the synthetic batch replaced whatever syn_train_set_data had uploaded: the caller uploads again (once per engine)
+    if (!L.epoch_barrier_checked) {
+        L.epoch_barrier_checked = true;
+        bool same = false;
+        const bool ok = learner_self_check(h, start, &same);
+        L.epoch_device_scope = !same;
         if (!ok) return fail(h, SYN_ERR_HIP, "the learner's start-up self-check could not run: %s", h->err.c_str());
     }
     return SYN_OK;
@@ -1811,57 +1893,26 @@ int syn_trainer_init_conv(syn_engine* h, const float* blob, size_t n_floats, con
     if (n_floats != (size_t)ConvGeom::NUM_PARAMS)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4ConvNet has %d parameters, got %zu", ConvGeom::NUM_PARAMS, n_floats);
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t cap_bytes = (size_t)TrainGeom::NUM_PARAMS * 4;  // the buffers are shared with the Connect4Net trainer (larger)
-    static_assert(ConvGeom::NUM_PARAMS <= TrainGeom::NUM_PARAMS, "trainer buffers are sized for Connect4Net");
-    {
-        const int rc = alloc_trainer_buffers(h);
-        if (rc != SYN_OK) return rc;
-    }
-    const size_t bytes = (size_t)ConvGeom::NUM_PARAMS * 4;
-    HIP_TRY(h, hipMemcpyAsync(h->d_tw, blob, bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_tm, 0, cap_bytes, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_tv, 0, cap_bytes, h->stream));
-    HIP_TRY(h, hipMemsetAsync(h->d_tgrad, 0, cap_bytes, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->train_hp = DevTrainHyper{cfg->weight_decay, cfg->policy_weight, cfg->value_weight, cfg->beta1, cfg->beta2, cfg->eps};
-    h->train_step = 0;
-    h->has_trainer = true;
-    h->trainer_kind = 1;
-    h->train_bf16 = 0;
+    int rc = alloc_trainer_buffers(h);
+    if (rc != SYN_OK) return rc;
+    auto& L = h->learner;
+    const LearnerStart start{1, blob, nullptr, nullptr};
+    rc = learner_load_state(h, start);
+    if (rc != SYN_OK) return rc;
+    L.train_hp = DevTrainHyper{cfg->weight_decay, cfg->policy_weight, cfg->value_weight, cfg->beta1, cfg->beta2, cfg->eps};
+    L.has_trainer = true;
+    L.trainer_kind = 1;
+    L.train_bf16 = 0;
     // ---- the four-workgroup epoch kernel exchanges its intermediates through L2 behind the one-XCD barrier of train_epoch.cuh (observed
     //      hardware behaviour, see there). Once per engine: eight steps on a synthetic batch through it and through the one-workgroup
     //      kernel from the same state; any differing bit (or a launch that cannot run) keeps this engine on the one-workgroup kernel.
-    if (!h->conv_mw_checked) {
-        h->conv_mw_checked = true;
-        const int n = 64, steps = 8, B = 8;
-        std::vector<uint64_t> my(n), op(n);
-        std::vector<float> tpi((size_t)n * 9, 1.0f / 9.0f), tv((size_t)n * 3, 0.0f);
-        std::vector<int32_t> perm(steps * B);
-        for (int i = 0; i < n; i++) {
-            my[i] = (0x0000040810204081ull * (uint64_t)(i % 7 + 1)) & 0x00003F7EFDFBF7EFull & ~(0x7Full << (7 * (i % 9)));
-            op[i] = (0x7Full << (7 * (i % 9))) & (0x0101010101010101ull * (uint64_t)(i % 5 + 1));
-            op[i] &= ~my[i];
-            tv[(size_t)i * 3 + i % 3] = 1.0f;
-        }
-        for (int i = 0; i < steps * B; i++) perm[i] = (i * 37) % n;
-        std::vector<float> wa((size_t)ConvGeom::NUM_PARAMS), wb((size_t)ConvGeom::NUM_PARAMS);
-        const long long fallbacks0 = h->epoch_fallbacks;
-        bool ok = true;
-        for (int mode = 0; mode < 2 && ok; mode++) {
-            h->conv_mw_force = mode;   // 0: one workgroup, 1: four
-            ok = syn_train_set_data(h, my.data(), op.data(), tpi.data(), tv.data(), n) == SYN_OK &&
-                 syn_train_epoch(h, perm.data(), steps, B, 1e-3f, nullptr) == SYN_OK &&
-                 syn_trainer_get_state(h, mode == 0 ? wa.data() : wb.data(), nullptr, nullptr, nullptr, nullptr) == SYN_OK;
-            // back to the caller's state
-            ok = ok && hipMemcpyAsync(h->d_tw, blob, bytes, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
-                 hipMemsetAsync(h->d_tm, 0, cap_bytes, h->stream) == hipSuccess && hipMemsetAsync(h->d_tv, 0, cap_bytes, h->stream) == hipSuccess &&
-                 hipMemsetAsync(h->d_tgrad, 0, cap_bytes, h->stream) == hipSuccess && hipStreamSynchronize(h->stream) == hipSuccess;
-            h->train_step = 0;
-        }
-        h->conv_mw_force = -1;
-        h->conv_mw_disabled = !(ok && h->epoch_fallbacks == fallbacks0 && std::memcmp(wa.data(), wb.data(), wa.size() * 4) == 0);
-        h->epoch_fallbacks = fallbacks0;
-        h->train_data_n = 0;   // the synthetic batch replaced whatever syn_train_set_data had uploaded: the caller uploads again (once per engine)
+    if (!L.conv_mw_checked) {
+        L.conv_mw_checked = true;
+        const long long fallbacks0 = L.epoch_fallbacks;
+        bool same = false;
+        const bool ok = learner_self_check(h, start, &same);
+        L.conv_mw_disabled = !(same && L.epoch_fallbacks == fallbacks0);
+        L.epoch_fallbacks = fallbacks0;
         if (!ok) return fail(h, SYN_ERR_HIP, "the conv learner's start-up self-check could not run: %s", h->err.c_str());
     }
     return SYN_OK;
@@ -1869,55 +1920,94 @@ int syn_trainer_init_conv(syn_engine* h, const float* blob, size_t n_floats, con
 
 int syn_trainer_set_precision(syn_engine* h, int precision) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init_conv first");
+    auto& L = h->learner;
+    if (!L.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init_conv first");
     if (precision != SYN_TRAIN_F32 && precision != SYN_TRAIN_BF16) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown training precision %d", precision);
-    if (precision == SYN_TRAIN_BF16 && h->trainer_kind != 1)
+    if (precision == SYN_TRAIN_BF16 && L.trainer_kind != 1)
         return fail(h, SYN_ERR_UNSUPPORTED, "the bf16 training variant exists for Connect4ConvNet only (BASELINE configs[4]: \"bf16 conv\"); "
                                             "Connect4Net trains in f32, bit-exact with the oracle");
-    h->train_bf16 = precision == SYN_TRAIN_BF16 ? 1 : 0;
+    L.train_bf16 = precision == SYN_TRAIN_BF16 ? 1 : 0;
     return SYN_OK;
 }
 
-static int launch_grads(syn_engine* h, const unsigned long long* d_my, const unsigned long long* d_op,
-                        const float* d_tpi, const float* d_tv, int batch, float* d_grads, float* d_losses = nullptr,
-                        const int* d_idx = nullptr, bool on_callers_stream = false, hipStream_t callers = nullptr) {
-    // (the *_enqueue entry points run the step on the caller's stream — which may be the null stream: torch's default)
-    const hipStream_t st = on_callers_stream ? callers : h->stream;
-    if (h->trainer_kind == 1) {
+// ------------------------------------------------------------------------------------------------ learner step
+// The learner's data set (d_train_data) and every staged batch: sections my | op | pi | v of n positions each, 64 bytes a position.
+struct TrainSections {
+    unsigned long long* my;
+    unsigned long long* op;
+    float* pi;
+    float* v;
+};
+static TrainSections train_sections(void* base, size_t n) {
+    unsigned char* b = static_cast<unsigned char*>(base);
+    return {reinterpret_cast<unsigned long long*>(b), reinterpret_cast<unsigned long long*>(b + n * 8),
+            reinterpret_cast<float*>(b + n * 16), reinterpret_cast<float*>(b + n * 52)};
+}
+// the same four arrays read-only: a caller's batch, or sections that are only read
+struct TrainSource {
+    const unsigned long long* my;
+    const unsigned long long* op;
+    const float* pi;
+    const float* v;
+    TrainSource(const unsigned long long* my_, const unsigned long long* op_, const float* pi_, const float* v_) : my(my_), op(op_), pi(pi_), v(v_) {}
+    TrainSource(const TrainSections& s) : my(s.my), op(s.op), pi(s.pi), v(s.v) {}
+};
+static TrainSource train_source(const uint64_t* my, const uint64_t* op, const float* pi, const float* v) {
+    return {reinterpret_cast<const unsigned long long*>(my), reinterpret_cast<const unsigned long long*>(op), pi, v};
+}
+// n positions from `src` into the sections `dst` on h->stream
+static int train_copy(syn_engine* h, const TrainSections& dst, const TrainSource& src, size_t n, hipMemcpyKind kind) {
+    HIP_TRY(h, hipMemcpyAsync(dst.my, src.my, n * 8, kind, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst.op, src.op, n * 8, kind, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst.pi, src.pi, n * 36, kind, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(dst.v, src.v, n * 12, kind, h->stream));
+    return SYN_OK;
+}
+// Room for `need` positions in d_train_data. A buffer that has to grow is allocated for `grow_to` >= need positions (the caller's
+// growth policy) once the stream's work on the old one is done; the data set it held is gone then.
+static int ensure_train_data(syn_engine* h, size_t need, size_t grow_to) {
+    auto& L = h->learner;
+    if (need <= L.train_data_cap) return SYN_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(L.d_train_data);
+    L.d_train_data = nullptr;
+    L.train_data_cap = 0;
+    L.train_data_n = 0;
+    HIP_TRY(h, hipMalloc(&L.d_train_data, grow_to * 64));
+    L.train_data_cap = grow_to;
+    return SYN_OK;
+}
+
+// (the *_enqueue entry points run the step on the caller's stream `st` — which may be the null stream: torch's default)
+static int launch_grads(syn_engine* h, hipStream_t st, const TrainSource& b, int batch, float* d_grads, float* d_losses = nullptr) {
+    auto& L = h->learner;
+    if (!d_losses) d_losses = L.d_tloss;
+    if (L.trainer_kind == 1) {
         // Connect4ConvNet (train_conv_mfma.cuh): one workgroup, the minibatch's activations resident in LDS, every chain on the
         // f32 matrix cores
         if (batch > ConvTrainGeom::CHUNK)
             return fail(h, SYN_ERR_UNSUPPORTED, "the Connect4ConvNet learner takes minibatches of at most %d positions (got %d)",
                         ConvTrainGeom::CHUNK, batch);
         const size_t clds = (size_t)ConvMfmaGeom::LDS_FLOATS * 4;
-        auto kg = h->train_bf16 ? train_conv_grad_kernel_mfma<true> : train_conv_grad_kernel_mfma<false>;
+        auto kg = L.train_bf16 ? train_conv_grad_kernel_mfma<true> : train_conv_grad_kernel_mfma<false>;
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kg), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
-        hipLaunchKernelGGL(kg, dim3(1), dim3(CONV_TRAIN_THREADS), clds, st, h->d_tw, d_my, d_op, d_tpi, d_tv, batch,
-                           h->train_hp, d_grads, d_losses ? d_losses : h->d_tloss, d_idx);
+        hipLaunchKernelGGL(kg, dim3(1), dim3(CONV_TRAIN_THREADS), clds, st, L.d_tw, b.my, b.op, b.pi, b.v, batch, L.train_hp, d_grads,
+                           d_losses, (const int*)nullptr);
         HIP_TRY(h, hipGetLastError());
         return SYN_OK;
     }
-    // the matrix-core kernel (train_mfma.cuh); SYN_DEBUG=1 SYN_TRAIN_VALU=1 runs the VALU kernel it replaced (A/B, same bits)
-    static const bool valu = debug_env("SYN_TRAIN_VALU") != nullptr;
-    const size_t lds = valu ? (size_t)TrainGeom::LDS_FLOATS * 4 : (size_t)TrainGeom::WL_OFF * 4;
-    if (valu) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(train_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    } else {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(train_grad_kernel_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    // Connect4Net: the matrix-core kernel (train_mfma.cuh)
+    const size_t lds = (size_t)TrainGeom::WL_OFF * 4;
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(train_grad_kernel_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // SYN_TRAIN_PROFILE=1: diagnostic stamps of the kernel's phases (first chunk), printed to stderr
-    static const bool prof = debug_env("SYN_TRAIN_PROFILE") != nullptr;
+    const bool prof = learner_knobs().profile;
     unsigned long long* d_prof = nullptr;
     if (prof) {
         HIP_TRY(h, hipMalloc(&d_prof, 4096));
         HIP_TRY(h, hipMemsetAsync(d_prof, 0, 4096, st));
     }
-    if (valu)
-        hipLaunchKernelGGL(train_grad_kernel, dim3(1), dim3(1024), lds, st, h->d_tw, d_my, d_op, d_tpi, d_tv, batch, h->train_hp,
-                           d_grads, d_losses ? d_losses : h->d_tloss, d_idx, d_prof);
-    else
-        hipLaunchKernelGGL(train_grad_kernel_mfma, dim3(1), dim3(1024), lds, st, h->d_tw, h->d_twimg, h->d_ttimg, d_my, d_op,
-                           d_tpi, d_tv, batch, h->train_hp, d_grads, d_losses ? d_losses : h->d_tloss, d_idx, d_prof);
+    hipLaunchKernelGGL(train_grad_kernel_mfma, dim3(1), dim3(1024), lds, st, L.d_tw, L.d_twimg, L.d_ttimg, b.my, b.op, b.pi, b.v, batch,
+                       L.train_hp, d_grads, d_losses, (const int*)nullptr, d_prof);
     HIP_TRY(h, hipGetLastError());
     if (prof) {
         unsigned long long t[8] = {0};
@@ -1930,49 +2020,43 @@ static int launch_grads(syn_engine* h, const unsigned long long* d_my, const uns
     return SYN_OK;
 }
 
-static int launch_adam(syn_engine* h, const float* d_grads, float lr, float grad_scale, bool on_callers_stream = false,
-                       hipStream_t callers = nullptr) {
-    const hipStream_t st = on_callers_stream ? callers : h->stream;
-    h->train_step += 1;
-    const double bc1 = 1.0 - std::pow((double)h->train_hp.beta1, (double)h->train_step);
-    const double bc2 = 1.0 - std::pow((double)h->train_hp.beta2, (double)h->train_step);
-    const float step_size = (float)((double)lr / bc1);
-    const float inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
-    if (h->trainer_kind == 1) {
+static int launch_adam(syn_engine* h, hipStream_t st, const float* d_grads, float lr, float grad_scale) {
+    auto& L = h->learner;
+    L.train_step += 1;
+    const AdamScalars a = adam_scalars(L.train_hp, lr, L.train_step);
+    if (L.trainer_kind == 1) {
         const int nc = ConvGeom::NUM_PARAMS;
-        hipLaunchKernelGGL(adam_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, h->d_tw, h->d_tm, h->d_tv, d_grads, nc,
-                           h->train_hp, step_size, inv_sqrt_bc2, grad_scale);
-        HIP_TRY(h, hipGetLastError());
-        return SYN_OK;
+        hipLaunchKernelGGL(adam_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, L.d_tw, L.d_tm, L.d_tv, d_grads, nc, L.train_hp,
+                           a.step_size, a.inv_sqrt_bc2, grad_scale);
+    } else {
+        const int n = TrainGeom::NUM_PARAMS;
+        hipLaunchKernelGGL(adam_image_kernel, dim3((n + 255) / 256), dim3(256), 0, st, L.d_tw, L.d_tm, L.d_tv, d_grads, n, L.train_hp,
+                           a.step_size, a.inv_sqrt_bc2, grad_scale, L.d_twimg, L.d_ttimg);
     }
-    const int n = TrainGeom::NUM_PARAMS;
-    hipLaunchKernelGGL(adam_image_kernel, dim3((n + 255) / 256), dim3(256), 0, st, h->d_tw, h->d_tm, h->d_tv, d_grads,
-                       n, h->train_hp, step_size, inv_sqrt_bc2, grad_scale, h->d_twimg, h->d_ttimg);
     HIP_TRY(h, hipGetLastError());
     return SYN_OK;
 }
 
 int syn_train_gradients_device(syn_engine* h, const uint64_t* d_my_bb, const uint64_t* d_op_bb, const float* d_target_pi,
                                const float* d_target_v, int batch, float* d_grads, float* losses) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     if (batch < 1 || !d_my_bb || !d_op_bb || !d_target_pi || !d_target_v || !d_grads)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_gradients_device");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = launch_grads(h, reinterpret_cast<const unsigned long long*>(d_my_bb),
-                          reinterpret_cast<const unsigned long long*>(d_op_bb), d_target_pi, d_target_v, batch, d_grads);
+    rc = launch_grads(h, h->stream, train_source(d_my_bb, d_op_bb, d_target_pi, d_target_v), batch, d_grads);
     if (rc != SYN_OK) return rc;
-    if (losses) HIP_TRY(h, hipMemcpyAsync(losses, h->d_tloss, 8, hipMemcpyDeviceToHost, h->stream));
+    if (losses) HIP_TRY(h, hipMemcpyAsync(losses, h->learner.d_tloss, 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
 
 int syn_train_apply_device(syn_engine* h, const float* d_grads, float lr, float grad_scale) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     if (!d_grads) return fail(h, SYN_ERR_INVALID_ARGUMENT, "d_grads is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = launch_adam(h, d_grads, lr, grad_scale);
+    rc = launch_adam(h, h->stream, d_grads, lr, grad_scale);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
@@ -1983,46 +2067,40 @@ int syn_train_apply_device(syn_engine* h, const float* d_grads, float lr, float 
 // gradients -> all-reduce -> Adam in one stream order. The caller keeps other trainer calls of this engine off other streams meanwhile.
 int syn_train_gradients_enqueue(syn_engine* h, void* stream, const uint64_t* d_my_bb, const uint64_t* d_op_bb, const float* d_target_pi,
                                 const float* d_target_v, int batch, float* d_grads, float* d_losses) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     if (batch < 1 || !d_my_bb || !d_op_bb || !d_target_pi || !d_target_v || !d_grads)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_gradients_enqueue");
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_grads(h, reinterpret_cast<const unsigned long long*>(d_my_bb), reinterpret_cast<const unsigned long long*>(d_op_bb),
-                        d_target_pi, d_target_v, batch, d_grads, d_losses, nullptr, true, static_cast<hipStream_t>(stream));
+    return launch_grads(h, static_cast<hipStream_t>(stream), train_source(d_my_bb, d_op_bb, d_target_pi, d_target_v), batch, d_grads, d_losses);
 }
 
 int syn_train_apply_enqueue(syn_engine* h, void* stream, const float* d_grads, float lr, float grad_scale) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     if (!d_grads) return fail(h, SYN_ERR_INVALID_ARGUMENT, "d_grads is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_adam(h, d_grads, lr, grad_scale, true, static_cast<hipStream_t>(stream));
+    return launch_adam(h, static_cast<hipStream_t>(stream), d_grads, lr, grad_scale);
 }
 
 int syn_train_step(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* target_pi,
                    const float* target_v, int batch, float lr, float* losses) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
-    if (batch < 1 || !my_bb || !op_bb || !target_pi || !target_v)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_step");
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    if (batch < 1 || !my_bb || !op_bb || !target_pi || !target_v) return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_step");
     HIP_TRY(h, hipSetDevice(h->device));
-    size_t nb = (size_t)batch;
-    int rc = ensure_scratch(h, nb * (16 + 36 + 12) + 256);
+    auto& L = h->learner;
+    const size_t nb = (size_t)batch;
+    rc = ensure_scratch(h, nb * 64 + 256);
     if (rc != SYN_OK) return rc;
-    unsigned long long* d_my = static_cast<unsigned long long*>(h->d_scratch);
-    unsigned long long* d_op = d_my + nb;
-    float* d_tpi = reinterpret_cast<float*>(d_op + nb);
-    float* d_tv = d_tpi + nb * 9;
-    HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, nb * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, nb * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_tpi, target_pi, nb * 36, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_tv, target_v, nb * 12, hipMemcpyHostToDevice, h->stream));
-    rc = launch_grads(h, d_my, d_op, d_tpi, d_tv, batch, h->d_tgrad);
+    const TrainSections staged = train_sections(h->d_scratch, nb);
+    rc = train_copy(h, staged, train_source(my_bb, op_bb, target_pi, target_v), nb, hipMemcpyHostToDevice);
     if (rc != SYN_OK) return rc;
-    rc = launch_adam(h, h->d_tgrad, lr, 1.0f);
+    rc = launch_grads(h, h->stream, staged, batch, L.d_tgrad);
     if (rc != SYN_OK) return rc;
-    if (losses) HIP_TRY(h, hipMemcpyAsync(losses, h->d_tloss, 8, hipMemcpyDeviceToHost, h->stream));
+    rc = launch_adam(h, h->stream, L.d_tgrad, lr, 1.0f);
+    if (rc != SYN_OK) return rc;
+    if (losses) HIP_TRY(h, hipMemcpyAsync(losses, L.d_tloss, 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -2030,306 +2108,331 @@ int syn_train_step(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, 
 // ---- epochs without the host in the loop: the de-duplicated buffer is uploaded once per iteration, an epoch is one call
 int syn_train_set_data(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* target_pi,
                        const float* target_v, size_t n) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     if (n < 1 || n > 0x7FFFFFFFu || !my_bb || !op_bb || !target_pi || !target_v)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_set_data");
     HIP_TRY(h, hipSetDevice(h->device));
-    if (n > h->train_data_cap) {
-        (void)hipFree(h->d_train_data);
-        h->d_train_data = nullptr;
-        h->train_data_cap = 0;
-        HIP_TRY(h, hipMalloc(&h->d_train_data, n * 64));
-        h->train_data_cap = n;
-    }
-    unsigned char* base = static_cast<unsigned char*>(h->d_train_data);
-    HIP_TRY(h, hipMemcpyAsync(base, my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + n * 8, op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + n * 16, target_pi, n * 36, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + n * 52, target_v, n * 12, hipMemcpyHostToDevice, h->stream));
+    rc = ensure_train_data(h, n, n);
+    if (rc != SYN_OK) return rc;
+    rc = train_copy(h, train_sections(h->learner.d_train_data, n), train_source(my_bb, op_bb, target_pi, target_v), n, hipMemcpyHostToDevice);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->train_data_n = n;
+    h->learner.train_data_n = n;
     return SYN_OK;
 }
 
-int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
-    if (h->train_data_n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "call syn_train_set_data first");
-    if (batch < 1 || (n_steps > 0 && !perm) || n_steps * (size_t)batch > 0x7FFFFFFFu)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_epoch");
+// What syn_train_epoch's paths work on, all of it in d_scratch: the permutation, the per-step losses (2 per step), the epoch's batches
+// in step order, the per-step Adam scalars' slot ([step_size n_steps][inv_sqrt_bc2 n_steps]) and 4 KB for diagnostic stamps.
+struct EpochStage {
+    int* d_perm;
+    float* d_losses;
+    TrainSections batches;
+    float* d_adam;
+    unsigned long long* d_stamps;
+};
+// an epoch's arguments (n_steps == 0 is valid: the caller returns before it selects the device)
+static int check_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch) {
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    const size_t n = h->learner.train_data_n, ni = n_steps * (size_t)batch;
+    if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "call syn_train_set_data first");
+    if (batch < 1 || (n_steps > 0 && !perm) || ni > 0x7FFFFFFFu) return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_epoch");
     if (n_steps == 0) return SYN_OK;
-    for (size_t i = 0; i < n_steps * (size_t)batch; i++)
-        if (perm[i] < 0 || (size_t)perm[i] >= h->train_data_n)
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "perm[%zu] = %d is outside the %zu uploaded states", i, perm[i],
-                        h->train_data_n);
-    HIP_TRY(h, hipSetDevice(h->device));
-    const size_t n = h->train_data_n, ni = n_steps * (size_t)batch;
+    for (size_t i = 0; i < ni; i++)
+        if (perm[i] < 0 || (size_t)perm[i] >= n)
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "perm[%zu] = %d is outside the %zu uploaded states", i, perm[i], n);
+    return SYN_OK;
+}
+// lays the scratch out and gathers the epoch's batches
+static int stage_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, EpochStage* st) {
+    const size_t n = h->learner.train_data_n, ni = n_steps * (size_t)batch;
     // scratch: [perm ni x 4][losses n_steps x 8][step-ordered batches: my, op (8 B each), pi (36 B), v (12 B) per sample]
     //          [per-step Adam scalars n_steps x 8][diagnostic stamps 4 KB]
     const size_t perm_bytes = (ni * 4 + 255) & ~(size_t)255, loss_bytes = (n_steps * 8 + 255) & ~(size_t)255;
     const size_t batch_bytes = (ni * 64 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(h, perm_bytes + loss_bytes + batch_bytes + loss_bytes + 4096 + 256);
+    const int rc = ensure_scratch(h, perm_bytes + loss_bytes + batch_bytes + loss_bytes + 4096 + 256);
     if (rc != SYN_OK) return rc;
     unsigned char* sc = static_cast<unsigned char*>(h->d_scratch);
-    int* d_perm = reinterpret_cast<int*>(sc);
-    float* d_losses = reinterpret_cast<float*>(sc + perm_bytes);
-    unsigned long long* g_my = reinterpret_cast<unsigned long long*>(sc + perm_bytes + loss_bytes);
-    unsigned long long* g_op = g_my + ni;
-    float* g_tpi = reinterpret_cast<float*>(g_op + ni);
-    float* g_tv = g_tpi + ni * 9;
-    HIP_TRY(h, hipMemcpyAsync(d_perm, perm, ni * 4, hipMemcpyHostToDevice, h->stream));
-    const unsigned char* base = static_cast<const unsigned char*>(h->d_train_data);
+    st->d_perm = reinterpret_cast<int*>(sc);
+    st->d_losses = reinterpret_cast<float*>(sc + perm_bytes);
+    st->batches = train_sections(sc + perm_bytes + loss_bytes, ni);
+    st->d_adam = reinterpret_cast<float*>(sc + perm_bytes + loss_bytes + batch_bytes);
+    st->d_stamps = reinterpret_cast<unsigned long long*>(sc + perm_bytes + loss_bytes + batch_bytes + loss_bytes);
+    HIP_TRY(h, hipMemcpyAsync(st->d_perm, perm, ni * 4, hipMemcpyHostToDevice, h->stream));
     // one gather for the whole epoch (the sampler's index_select), so a step reads its batch from consecutive addresses
     // instead of chasing perm -> sample inside the latency-bound step kernel
-    hipLaunchKernelGGL(train_gather_kernel, dim3((unsigned)((ni * 16 + 255) / 256)), dim3(256), 0, h->stream, d_perm, (int)ni,
-                       reinterpret_cast<const unsigned long long*>(base),
-                       reinterpret_cast<const unsigned long long*>(base + n * 8),
-                       reinterpret_cast<const float*>(base + n * 16), reinterpret_cast<const float*>(base + n * 52), g_my,
-                       g_op, g_tpi, g_tv);
+    const TrainSource data = train_sections(h->learner.d_train_data, n);
+    const TrainSections g = st->batches;
+    hipLaunchKernelGGL(train_gather_kernel, dim3((unsigned)((ni * 16 + 255) / 256)), dim3(256), 0, h->stream, st->d_perm, (int)ni, data.my,
+                       data.op, data.pi, data.v, g.my, g.op, g.pi, g.v);
     HIP_TRY(h, hipGetLastError());
-    // One persistent launch for the whole epoch (train_epoch.cuh) when the batch fits one 32-sample chunk — the reference's
-    // batch_size. SYN_DEBUG=1 SYN_TRAIN_QUEUED=1 keeps the two launches per step below (A/B, same bits), as do larger batches.
-    static const bool queued = debug_env("SYN_TRAIN_QUEUED") != nullptr;
-    if (!queued && batch <= TrainGeom::CHUNK && h->trainer_kind == 0) {
-        // per-step Adam scalars, in double on the host like libtorch (launch_adam)
-        std::vector<float> adam_sc(2 * n_steps);
-        for (size_t s = 0; s < n_steps; s++) {
-            const double t = (double)(h->train_step + (long long)s + 1);
-            const double bc1 = 1.0 - std::pow((double)h->train_hp.beta1, t);
-            const double bc2 = 1.0 - std::pow((double)h->train_hp.beta2, t);
-            adam_sc[s] = (float)((double)lr / bc1);
-            adam_sc[n_steps + s] = (float)(1.0 / std::sqrt(bc2));
-        }
-        float* d_sc = reinterpret_cast<float*>(sc + perm_bytes + loss_bytes + batch_bytes);
-        unsigned long long* d_prof = reinterpret_cast<unsigned long long*>(sc + perm_bytes + loss_bytes + batch_bytes + loss_bytes);
-        static const bool prof = debug_env("SYN_TRAIN_PROFILE") != nullptr;
-        int rc2 = SYN_OK;
+    return SYN_OK;
+}
+
+// the Adam scalars of the epoch's steps, as the persistent kernels read them from EpochStage::d_adam
+static std::vector<float> epoch_adam_scalars(const syn_engine::Learner& L, float lr, size_t n_steps) {
+    std::vector<float> sc(2 * n_steps);
+    for (size_t s = 0; s < n_steps; s++) {
+        const AdamScalars a = adam_scalars(L.train_hp, lr, L.train_step + (long long)s + 1);
+        sc[s] = a.step_size;
+        sc[n_steps + s] = a.inv_sqrt_bc2;
+    }
+    return sc;
+}
+
+// d_tsnap holds the learner as it was before a persistent epoch launch that may give up: [w][m][v] of the current network, then
+// (Connect4Net only) its two fragment images.
+struct SnapshotLayout {
+    float* live[5];
+    size_t bytes[5];
+    int parts;
+};
+static SnapshotLayout snapshot_layout(const syn_engine::Learner& L) {
+    const size_t pb = learner_param_bytes(L.trainer_kind);
+    return {{L.d_tw, L.d_tm, L.d_tv, L.d_twimg, L.d_ttimg},
+            {pb, pb, pb, (size_t)MlpGeom::IMG_FLOATS * 4, (size_t)TrainImg::T_FLOATS * 4},
+            L.trainer_kind == 1 ? 3 : 5};
+}
+static int learner_snapshot(syn_engine* h) {
+    const SnapshotLayout s = snapshot_layout(h->learner);
+    unsigned char* sn = reinterpret_cast<unsigned char*>(h->learner.d_tsnap);
+    for (int i = 0; i < s.parts; sn += s.bytes[i++])
+        HIP_TRY(h, hipMemcpyAsync(sn, s.live[i], s.bytes[i], hipMemcpyDeviceToDevice, h->stream));
+    return SYN_OK;
+}
+// the persistent launch gave up: the learner is put back for the path that runs the epoch instead, and the fallback is counted
+static int learner_restore(syn_engine* h) {
+    const SnapshotLayout s = snapshot_layout(h->learner);
+    const unsigned char* sn = reinterpret_cast<const unsigned char*>(h->learner.d_tsnap);
+    for (int i = 0; i < s.parts; sn += s.bytes[i++])
+        HIP_TRY(h, hipMemcpyAsync(s.live[i], sn, s.bytes[i], hipMemcpyDeviceToDevice, h->stream));
+    h->learner.epoch_fallbacks++;
+    return SYN_OK;
+}
+
+// ---- SYN_TRAIN_PROFILE=1: the stamps of an epoch kernel's step 2, printed to stderr
+// Connect4Net, workgroup g at [16 g ..]: top, features, forward L0..L4, heads, act-grads L4..L1, parameter jobs, step barrier
+static void print_epoch_stamps(const unsigned long long* stamps, bool one_xcd) {
+    fprintf(stderr, "[syn train profile] epoch kernel (%s), step 2, cycles per phase\n", one_xcd ? "workers on one XCD" : "device-scope barrier");
+    for (int g = 0; g < EP_WGS; g++) {
+        fprintf(stderr, "  wg %d (start %+lld):", g, (long long)(stamps[16 * g] - stamps[0]));
+        for (int i = 1; i < 14; i++) fprintf(stderr, " %llu", stamps[16 * g + i] - stamps[16 * g + i - 1]);
+        fprintf(stderr, " | probe fresh line %llu, cold line %llu\n", stamps[16 * g + 14], stamps[16 * g + 15]);
+    }
+}
+static int print_conv_mw_stamps(syn_engine* h, const unsigned long long* d_stamps, bool one_xcd) {
+    unsigned long long t[16 * CONV_MW_WGS] = {0};
+    HIP_TRY(h, hipMemcpy(t, d_stamps, sizeof(t), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[syn train profile] conv epoch kernel on %d workgroups (%s), step 2, cycles: stage | F | barrier | H | G1 | G2 | Adam (own head weights, inside the barrier) | rest of the barrier | dY in | G3 | barrier | G4 + Adam (shared)\n",
+            CONV_MW_WGS, one_xcd ? "one XCD" : "device-scope barrier");
+    for (int g = 0; g < CONV_MW_WGS; g++) {
+        fprintf(stderr, "  wg %d (start %+lld):", g, (long long)(t[16 * g] - t[0]));
+        for (int i = 1; i < 13; i++) fprintf(stderr, " %llu", t[16 * g + i] - t[16 * g + i - 1]);
+        fprintf(stderr, " | total %llu\n", t[16 * g + 12] - t[16 * g]);
+    }
+    return SYN_OK;
+}
+static int print_conv_stamps(syn_engine* h, const unsigned long long* d_stamps) {
+    unsigned long long t[16] = {0};
+    HIP_TRY(h, hipMemcpy(t, d_stamps, sizeof(t), hipMemcpyDeviceToHost));
+    fprintf(stderr, "[syn train profile] conv epoch kernel, step 2, cycles: stage %llu | F %llu | H %llu | losses+G1 %llu | G2 %llu | G3 %llu | G4 %llu | Adam %llu | total %llu\n",
+            t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[15] - t[7], t[15] - t[0]);
+    return SYN_OK;
+}
+
+// Connect4Net, batch <= 32: ONE persistent launch for the whole epoch (train_epoch.cuh). *done = false: the kernel gave up, the learner
+// is as it was before the call and the epoch is still to run.
+static int epoch_persistent_mlp(syn_engine* h, const EpochStage& st, size_t n_steps, int batch, float lr, float* step_losses, bool* done) {
+    auto& L = h->learner;
+    *done = false;
+    const bool prof = learner_knobs().profile;
+    const std::vector<float> adam_sc = epoch_adam_scalars(L, lr, n_steps);
+    unsigned status[4] = {0u, 0u, 0u, 0u};
+    unsigned long long stamps[16 * EP_WGS] = {0};
+    HIP_TRY(h, hipMemcpyAsync(st.d_adam, adam_sc.data(), adam_sc.size() * 4, hipMemcpyHostToDevice, h->stream));
+    // snapshot of the learner (parameters, moments, both images: 0.85 MB of device copies): the launch below needs its 16
+    // workgroups resident together; if it gives up (another kernel holds the CUs) the state is put back and the epoch runs
+    // through the queued per-step launches instead — same bits, no co-residency requirement
+    int rc = learner_snapshot(h);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipMemsetAsync(st.d_stamps, 0, 2048, h->stream));
+    HIP_TRY(h, hipMemsetAsync(L.d_tsync, 0, 256, h->stream));
+    float* img2 = L.d_timg2;
+    float* timg2 = L.d_timg2 + MlpGeom::IMG_FLOATS;
+    // both buffers start as the current network: the kernel rewrites every parameter's slot, never the padding
+    HIP_TRY(h, hipMemcpyAsync(img2, L.d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(timg2, L.d_ttimg, (size_t)TrainImg::T_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
+    EpochParams ep{};
+    ep.w = L.d_tw; ep.m = L.d_tm; ep.v = L.d_tv;
+    ep.img[0] = L.d_twimg; ep.img[1] = img2;
+    ep.timg[0] = L.d_ttimg; ep.timg[1] = timg2;
+    ep.my_bb = st.batches.my; ep.op_bb = st.batches.op; ep.tpi = st.batches.pi; ep.tv = st.batches.v;
+    ep.step_size = st.d_adam; ep.inv_sqrt_bc2 = st.d_adam + n_steps;
+    ep.losses = st.d_losses; ep.grads = L.d_tgrad; ep.sync = L.d_tsync;
+    ep.prof = prof ? st.d_stamps : nullptr;
+    ep.n_steps = (int)n_steps; ep.batch = batch; ep.hp = L.train_hp;
+    ep.force_device_scope = (learner_knobs().device_scope || L.epoch_device_scope) ? 1 : 0;
+    const size_t lds = (size_t)TrainGeom::WL_OFF * 4;
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(train_epoch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(train_epoch_kernel, dim3(EP_WGS * EP_XCDS), dim3(EP_THREADS), lds, h->stream, ep);
+    HIP_TRY(h, hipGetLastError());
+    if (n_steps & 1) {  // the final network sits in the second buffer: bring the first one (the published image) up to date
+        HIP_TRY(h, hipMemcpyAsync(L.d_twimg, img2, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(L.d_ttimg, timg2, (size_t)TrainImg::T_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
+    if (step_losses) HIP_TRY(h, hipMemcpyAsync(step_losses, st.d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(status, L.d_tsync, 16, hipMemcpyDeviceToHost, h->stream));
+    if (prof) HIP_TRY(h, hipMemcpyAsync(stamps, st.d_stamps, sizeof(stamps), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    // the workers were not resident together: put the learner back, the caller runs the epoch through the queued launches
+    if (status[1] != 0u || epoch_force_abort()) return learner_restore(h);
+    if (prof) print_epoch_stamps(stamps, status[3] != 0u);
+    L.train_step += (long long)n_steps;
+    *done = true;
+    return SYN_OK;
+}
+
+// Connect4ConvNet, batch <= 32: gradients and Adam of every step in ONE launch (train_conv_mfma.cuh) — on four workgroups of one XCD
+// where that kernel may run and does not give up, else in the one-workgroup kernel, which has no co-residency requirement.
+static int epoch_persistent_conv(syn_engine* h, const EpochStage& st, size_t n_steps, int batch, float lr, float* step_losses) {
+    auto& L = h->learner;
+    const LearnerKnobs& knobs = learner_knobs();
+    const std::vector<float> adam_sc = epoch_adam_scalars(L, lr, n_steps);
+    HIP_TRY(h, hipMemcpyAsync(st.d_adam, adam_sc.data(), adam_sc.size() * 4, hipMemcpyHostToDevice, h->stream));
+    ConvEpochParams ep{};
+    ep.w = L.d_tw; ep.m = L.d_tm; ep.v = L.d_tv;
+    ep.my_bb = st.batches.my; ep.op_bb = st.batches.op; ep.tpi = st.batches.pi; ep.tv = st.batches.v;
+    ep.step_size = st.d_adam; ep.inv_sqrt_bc2 = st.d_adam + n_steps;
+    ep.losses = st.d_losses; ep.grads = L.d_tgrad;
+    ep.n_steps = (int)n_steps; ep.batch = batch; ep.hp = L.train_hp;
+    const bool prof = knobs.profile && n_steps > 2;
+    if (prof) HIP_TRY(h, hipMemsetAsync(st.d_stamps, 0, 128, h->stream));
+    ep.prof = prof ? st.d_stamps : nullptr;
+    // the step spread over four workgroups of one XCD (train_conv_epoch_kernel_mw: same chains, same bits, f32 and bf16). They must be
+    // resident together: the learner is snapshotted first, and a launch that gives up (or SYN_DEBUG=1 SYN_TRAIN_CONV_MW=0, or a
+    // failed start-up self-check) runs the one-workgroup kernel below instead.
+    const bool want_mw = L.conv_mw_force >= 0 ? L.conv_mw_force == 1 : (!knobs.conv_mw_off && !L.conv_mw_disabled);
+    if (want_mw) {
+        int rc = learner_snapshot(h);
+        if (rc != SYN_OK) return rc;
+        HIP_TRY(h, hipMemsetAsync(L.d_tsync, 0, 256, h->stream));
+        if (prof) HIP_TRY(h, hipMemsetAsync(st.d_stamps, 0, 512, h->stream));
+        ConvMwParams mp{};
+        mp.e = ep;
+        mp.xbuf = L.d_cxbuf;
+        mp.sync = L.d_tsync;
+        mp.force_device_scope = knobs.device_scope ? 1 : 0;
+        const size_t mlds = (size_t)ConvMwGeom::LDS_FLOATS * 4;
+        auto km = L.train_bf16 ? train_conv_epoch_kernel_mw<true> : train_conv_epoch_kernel_mw<false>;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(km), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
+        hipLaunchKernelGGL(km, dim3(CONV_MW_WGS * CONV_MW_XCDS), dim3(CONV_TRAIN_THREADS), mlds, h->stream, mp);
+        HIP_TRY(h, hipGetLastError());
         unsigned status[4] = {0u, 0u, 0u, 0u};
-        unsigned long long stamps[16 * EP_WGS] = {0};
-        do {
-            hipError_t e;
-#define EP_TRY(expr) if ((e = (expr)) != hipSuccess) { rc2 = fail(h, SYN_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e)); break; }
-            EP_TRY(hipMemcpyAsync(d_sc, adam_sc.data(), adam_sc.size() * 4, hipMemcpyHostToDevice, h->stream));
-            // snapshot of the learner (parameters, moments, both images: 0.85 MB of device copies): the launch below needs its 16
-            // workgroups resident together; if it gives up (another kernel holds the CUs) the state is put back and the epoch runs
-            // through the queued per-step launches instead — same bits, no co-residency requirement
-            {
-                const size_t pb = (size_t)TrainGeom::NUM_PARAMS * 4, ib = (size_t)MlpGeom::IMG_FLOATS * 4, tb = (size_t)TrainImg::T_FLOATS * 4;
-                unsigned char* sn = reinterpret_cast<unsigned char*>(h->d_tsnap);
-                EP_TRY(hipMemcpyAsync(sn, h->d_tw, pb, hipMemcpyDeviceToDevice, h->stream));
-                EP_TRY(hipMemcpyAsync(sn + pb, h->d_tm, pb, hipMemcpyDeviceToDevice, h->stream));
-                EP_TRY(hipMemcpyAsync(sn + 2 * pb, h->d_tv, pb, hipMemcpyDeviceToDevice, h->stream));
-                EP_TRY(hipMemcpyAsync(sn + 3 * pb, h->d_twimg, ib, hipMemcpyDeviceToDevice, h->stream));
-                EP_TRY(hipMemcpyAsync(sn + 3 * pb + ib, h->d_ttimg, tb, hipMemcpyDeviceToDevice, h->stream));
-            }
-            EP_TRY(hipMemsetAsync(d_prof, 0, 2048, h->stream));
-            EP_TRY(hipMemsetAsync(h->d_tsync, 0, 256, h->stream));
-            float* img2 = h->d_timg2;
-            float* timg2 = h->d_timg2 + MlpGeom::IMG_FLOATS;
-            // both buffers start as the current network: the kernel rewrites every parameter's slot, never the padding
-            EP_TRY(hipMemcpyAsync(img2, h->d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
-            EP_TRY(hipMemcpyAsync(timg2, h->d_ttimg, (size_t)TrainImg::T_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
-            EpochParams ep{};
-            ep.w = h->d_tw; ep.m = h->d_tm; ep.v = h->d_tv;
-            ep.img[0] = h->d_twimg; ep.img[1] = img2;
-            ep.timg[0] = h->d_ttimg; ep.timg[1] = timg2;
-            ep.my_bb = g_my; ep.op_bb = g_op; ep.tpi = g_tpi; ep.tv = g_tv;
-            ep.step_size = d_sc; ep.inv_sqrt_bc2 = d_sc + n_steps;
-            ep.losses = d_losses; ep.grads = h->d_tgrad; ep.sync = h->d_tsync;
-            ep.prof = prof ? d_prof : nullptr;
-            ep.n_steps = (int)n_steps; ep.batch = batch; ep.hp = h->train_hp;
-            static const bool device_scope = debug_env("SYN_TRAIN_DEVICE_SCOPE") != nullptr;
-            ep.force_device_scope = (device_scope || h->epoch_device_scope) ? 1 : 0;
-            const size_t lds = (size_t)TrainGeom::WL_OFF * 4;
-            EP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(train_epoch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(train_epoch_kernel, dim3(EP_WGS * EP_XCDS), dim3(EP_THREADS), lds, h->stream, ep);
-            EP_TRY(hipGetLastError());
-            if (n_steps & 1) {  // the final network sits in the second buffer: bring the first one (the published image) up to date
-                EP_TRY(hipMemcpyAsync(h->d_twimg, img2, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
-                EP_TRY(hipMemcpyAsync(h->d_ttimg, timg2, (size_t)TrainImg::T_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
-            }
-            if (step_losses) EP_TRY(hipMemcpyAsync(step_losses, d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
-            EP_TRY(hipMemcpyAsync(status, h->d_tsync, 16, hipMemcpyDeviceToHost, h->stream));
-            if (prof) EP_TRY(hipMemcpyAsync(stamps, d_prof, sizeof(stamps), hipMemcpyDeviceToHost, h->stream));
-            EP_TRY(hipStreamSynchronize(h->stream));
-#undef EP_TRY
-        } while (0);
-        if (rc2 != SYN_OK) return rc2;
-        const bool force_abort = debug_env("SYN_TRAIN_FORCE_ABORT") != nullptr;  // test hook: take the recovery path
-        bool aborted = status[1] != 0u || force_abort;
-        if (aborted) {
-            // the workers were not resident together: put the learner back and run the epoch through the queued launches below
-            const size_t pb = (size_t)TrainGeom::NUM_PARAMS * 4, ib = (size_t)MlpGeom::IMG_FLOATS * 4, tb = (size_t)TrainImg::T_FLOATS * 4;
-            const unsigned char* sn = reinterpret_cast<const unsigned char*>(h->d_tsnap);
-            HIP_TRY(h, hipMemcpyAsync(h->d_tw, sn, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_tm, sn + pb, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_tv, sn + 2 * pb, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_twimg, sn + 3 * pb, ib, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_ttimg, sn + 3 * pb + ib, tb, hipMemcpyDeviceToDevice, h->stream));
-            h->epoch_fallbacks++;
-        }
-        if (!aborted && prof) {
-            // stamps of step 2, workgroup g at [16 g ..]: top, features, forward L0..L4, heads, act-grads L4..L1, parameter jobs, step barrier
-            fprintf(stderr, "[syn train profile] epoch kernel (%s), step 2, cycles per phase\n", status[3] ? "workers on one XCD" : "device-scope barrier");
-            for (int g = 0; g < EP_WGS; g++) {
-                fprintf(stderr, "  wg %d (start %+lld):", g, (long long)(stamps[16 * g] - stamps[0]));
-                for (int i = 1; i < 14; i++) fprintf(stderr, " %llu", stamps[16 * g + i] - stamps[16 * g + i - 1]);
-                fprintf(stderr, " | probe fresh line %llu, cold line %llu\n", stamps[16 * g + 14], stamps[16 * g + 15]);
-            }
-        }
-        if (!aborted) {
-            h->train_step += (long long)n_steps;
+        HIP_TRY(h, hipMemcpyAsync(status, L.d_tsync, 16, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (status[1] == 0u && !epoch_force_abort()) {
+            if (step_losses) HIP_TRY(h, hipMemcpy(step_losses, st.d_losses, n_steps * 8, hipMemcpyDeviceToHost));
+            if (prof) rc = print_conv_mw_stamps(h, st.d_stamps, status[3] != 0u);
+            if (rc != SYN_OK) return rc;
+            L.train_step += (long long)n_steps;
             return SYN_OK;
         }
+        rc = learner_restore(h);
+        if (rc != SYN_OK) return rc;
+        if (prof) HIP_TRY(h, hipMemsetAsync(st.d_stamps, 0, 128, h->stream));
     }
-    if (!queued && batch <= ConvTrainGeom::CHUNK && h->trainer_kind == 1) {
-        // Connect4ConvNet: the persistent one-workgroup epoch kernel (train_conv_mfma.cuh) — gradients and Adam of every step in ONE
-        // launch, no co-residency requirement
-        std::vector<float> adam_sc(2 * n_steps);
-        for (size_t s = 0; s < n_steps; s++) {
-            const double t = (double)(h->train_step + (long long)s + 1);
-            const double bc1 = 1.0 - std::pow((double)h->train_hp.beta1, t);
-            const double bc2 = 1.0 - std::pow((double)h->train_hp.beta2, t);
-            adam_sc[s] = (float)((double)lr / bc1);
-            adam_sc[n_steps + s] = (float)(1.0 / std::sqrt(bc2));
-        }
-        float* d_sc = reinterpret_cast<float*>(sc + perm_bytes + loss_bytes + batch_bytes);
-        HIP_TRY(h, hipMemcpyAsync(d_sc, adam_sc.data(), adam_sc.size() * 4, hipMemcpyHostToDevice, h->stream));
-        ConvEpochParams ep{};
-        ep.w = h->d_tw; ep.m = h->d_tm; ep.v = h->d_tv;
-        ep.my_bb = g_my; ep.op_bb = g_op; ep.tpi = g_tpi; ep.tv = g_tv;
-        ep.step_size = d_sc; ep.inv_sqrt_bc2 = d_sc + n_steps;
-        ep.losses = d_losses; ep.grads = h->d_tgrad;
-        ep.n_steps = (int)n_steps; ep.batch = batch; ep.hp = h->train_hp;
-        unsigned long long* d_cprof = reinterpret_cast<unsigned long long*>(sc + perm_bytes + loss_bytes + batch_bytes + loss_bytes);
-        const bool cprof = debug_env("SYN_TRAIN_PROFILE") != nullptr && n_steps > 2;
-        if (cprof) HIP_TRY(h, hipMemsetAsync(d_cprof, 0, 128, h->stream));
-        ep.prof = cprof ? d_cprof : nullptr;
-        const size_t clds = (size_t)ConvMfmaGeom::LDS_FLOATS * 4;
-        // the step spread over four workgroups of one XCD (train_conv_epoch_kernel_mw: same chains, same bits, f32 and bf16). They must be
-        // resident together: the learner is snapshotted first, and a launch that gives up (or SYN_DEBUG=1 SYN_TRAIN_CONV_MW=0, or a
-        // failed start-up self-check) runs the one-workgroup kernel below instead.
-        static const bool mw_off = [] { const char* e = debug_env("SYN_TRAIN_CONV_MW"); return e && std::atoi(e) == 0; }();
-        const bool want_mw = h->conv_mw_force >= 0 ? h->conv_mw_force == 1 : (!mw_off && !h->conv_mw_disabled);
-        if (want_mw) {
-            const size_t pb = (size_t)ConvGeom::NUM_PARAMS * 4;
-            unsigned char* sn = reinterpret_cast<unsigned char*>(h->d_tsnap);
-            HIP_TRY(h, hipMemcpyAsync(sn, h->d_tw, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(sn + pb, h->d_tm, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(sn + 2 * pb, h->d_tv, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemsetAsync(h->d_tsync, 0, 256, h->stream));
-            if (cprof) HIP_TRY(h, hipMemsetAsync(d_cprof, 0, 512, h->stream));
-            ConvMwParams mp{};
-            mp.e = ep;
-            mp.xbuf = h->d_cxbuf;
-            mp.sync = h->d_tsync;
-            static const bool device_scope = debug_env("SYN_TRAIN_DEVICE_SCOPE") != nullptr;
-            mp.force_device_scope = device_scope ? 1 : 0;
-            const size_t mlds = (size_t)ConvMwGeom::LDS_FLOATS * 4;
-            auto km = h->train_bf16 ? train_conv_epoch_kernel_mw<true> : train_conv_epoch_kernel_mw<false>;
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(km), hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-            hipLaunchKernelGGL(km, dim3(CONV_MW_WGS * CONV_MW_XCDS), dim3(CONV_TRAIN_THREADS), mlds, h->stream, mp);
-            HIP_TRY(h, hipGetLastError());
-            unsigned status[4] = {0u, 0u, 0u, 0u};
-            HIP_TRY(h, hipMemcpyAsync(status, h->d_tsync, 16, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            const bool aborted = status[1] != 0u || debug_env("SYN_TRAIN_FORCE_ABORT") != nullptr;
-            if (!aborted) {
-                if (step_losses) HIP_TRY(h, hipMemcpy(step_losses, d_losses, n_steps * 8, hipMemcpyDeviceToHost));
-                if (cprof) {
-                    unsigned long long t[16 * CONV_MW_WGS] = {0};
-                    HIP_TRY(h, hipMemcpy(t, d_cprof, sizeof(t), hipMemcpyDeviceToHost));
-                    fprintf(stderr, "[syn train profile] conv epoch kernel on %d workgroups (%s), step 2, cycles: stage | F | barrier | H | G1 | G2 | Adam (own head weights, inside the barrier) | rest of the barrier | dY in | G3 | barrier | G4 + Adam (shared)\n",
-                            CONV_MW_WGS, status[3] ? "one XCD" : "device-scope barrier");
-                    for (int g = 0; g < CONV_MW_WGS; g++) {
-                        fprintf(stderr, "  wg %d (start %+lld):", g, (long long)(t[16 * g] - t[0]));
-                        for (int i = 1; i < 13; i++) fprintf(stderr, " %llu", t[16 * g + i] - t[16 * g + i - 1]);
-                        fprintf(stderr, " | total %llu\n", t[16 * g + 12] - t[16 * g]);
-                    }
-                }
-                h->train_step += (long long)n_steps;
-                return SYN_OK;
-            }
-            HIP_TRY(h, hipMemcpyAsync(h->d_tw, sn, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_tm, sn + pb, pb, hipMemcpyDeviceToDevice, h->stream));
-            HIP_TRY(h, hipMemcpyAsync(h->d_tv, sn + 2 * pb, pb, hipMemcpyDeviceToDevice, h->stream));
-            h->epoch_fallbacks++;
-            if (cprof) HIP_TRY(h, hipMemsetAsync(d_cprof, 0, 128, h->stream));
-        }
-        auto ke = h->train_bf16 ? train_conv_epoch_kernel<true> : train_conv_epoch_kernel<false>;
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ke), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
-        hipLaunchKernelGGL(ke, dim3(1), dim3(CONV_TRAIN_THREADS), clds, h->stream, ep);
-        HIP_TRY(h, hipGetLastError());
-        if (step_losses) HIP_TRY(h, hipMemcpyAsync(step_losses, d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        if (cprof && !h->train_bf16) {
-            unsigned long long t[16] = {0};
-            HIP_TRY(h, hipMemcpy(t, d_cprof, sizeof(t), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[syn train profile] conv epoch kernel, step 2, cycles: stage %llu | F %llu | H %llu | losses+G1 %llu | G2 %llu | G3 %llu | G4 %llu | Adam %llu | total %llu\n",
-                    t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3], t[5] - t[4], t[6] - t[5], t[7] - t[6], t[15] - t[7], t[15] - t[0]);
-        }
-        h->train_step += (long long)n_steps;
-        return SYN_OK;
+    const size_t clds = (size_t)ConvMfmaGeom::LDS_FLOATS * 4;
+    auto ke = L.train_bf16 ? train_conv_epoch_kernel<true> : train_conv_epoch_kernel<false>;
+    HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(ke), hipFuncAttributeMaxDynamicSharedMemorySize, (int)clds));
+    hipLaunchKernelGGL(ke, dim3(1), dim3(CONV_TRAIN_THREADS), clds, h->stream, ep);
+    HIP_TRY(h, hipGetLastError());
+    if (step_losses) HIP_TRY(h, hipMemcpyAsync(step_losses, st.d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (prof && !L.train_bf16) {
+        const int rc = print_conv_stamps(h, st.d_stamps);
+        if (rc != SYN_OK) return rc;
     }
-    for (size_t s = 0; s < n_steps; s++) {  // steps are dependent (weights of step s feed step s+1): queued, never synced
+    L.train_step += (long long)n_steps;
+    return SYN_OK;
+}
+
+// Two launches per step, queued and never synchronised in between (the weights of step s feed step s + 1): batches above 32 positions,
+// a persistent kernel that gave up, and SYN_DEBUG=1 SYN_TRAIN_QUEUED=1.
+static int epoch_queued(syn_engine* h, const EpochStage& st, size_t n_steps, int batch, float lr, float* step_losses) {
+    auto& L = h->learner;
+    for (size_t s = 0; s < n_steps; s++) {
         const size_t o = s * (size_t)batch;
-        rc = launch_grads(h, g_my + o, g_op + o, g_tpi + o * 9, g_tv + o * 3, batch, h->d_tgrad, d_losses + 2 * s);
+        const TrainSource b = {st.batches.my + o, st.batches.op + o, st.batches.pi + o * 9, st.batches.v + o * 3};
+        int rc = launch_grads(h, h->stream, b, batch, L.d_tgrad, st.d_losses + 2 * s);
         if (rc != SYN_OK) return rc;
-        rc = launch_adam(h, h->d_tgrad, lr, 1.0f);
+        rc = launch_adam(h, h->stream, L.d_tgrad, lr, 1.0f);
         if (rc != SYN_OK) return rc;
     }
-    if (step_losses) HIP_TRY(h, hipMemcpyAsync(step_losses, d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
+    if (step_losses) HIP_TRY(h, hipMemcpyAsync(step_losses, st.d_losses, n_steps * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
 
-int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses) {
+    int rc = check_epoch(h, perm, n_steps, batch);
+    if (rc != SYN_OK || n_steps == 0) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t bytes = (size_t)(h->trainer_kind == 1 ? ConvGeom::NUM_PARAMS : TrainGeom::NUM_PARAMS) * 4;
-    if (blob) HIP_TRY(h, hipMemcpyAsync(blob, h->d_tw, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (m) HIP_TRY(h, hipMemcpyAsync(m, h->d_tm, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (v) HIP_TRY(h, hipMemcpyAsync(v, h->d_tv, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (grads) HIP_TRY(h, hipMemcpyAsync(grads, h->d_tgrad, bytes, hipMemcpyDeviceToHost, h->stream));
+    EpochStage st{};
+    rc = stage_epoch(h, perm, n_steps, batch, &st);
+    if (rc != SYN_OK) return rc;
+    // One persistent launch for the whole epoch when the batch fits one 32-sample chunk — the reference's batch_size. Larger batches
+    // queue two launches per step, as does a Connect4Net epoch whose persistent kernel gave up.
+    const int kind = h->learner.trainer_kind;
+    if (!learner_knobs().queued && kind == 1 && batch <= ConvTrainGeom::CHUNK)
+        return epoch_persistent_conv(h, st, n_steps, batch, lr, step_losses);
+    if (!learner_knobs().queued && kind == 0 && batch <= TrainGeom::CHUNK) {
+        bool done = false;
+        rc = epoch_persistent_mlp(h, st, n_steps, batch, lr, step_losses, &done);
+        if (rc != SYN_OK || done) return rc;
+    }
+    return epoch_queued(h, st, n_steps, batch, lr, step_losses);
+}
+
+int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads) {
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    auto& L = h->learner;
+    const size_t bytes = learner_param_bytes(L.trainer_kind);
+    if (blob) HIP_TRY(h, hipMemcpyAsync(blob, L.d_tw, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (m) HIP_TRY(h, hipMemcpyAsync(m, L.d_tm, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (v) HIP_TRY(h, hipMemcpyAsync(v, L.d_tv, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (grads) HIP_TRY(h, hipMemcpyAsync(grads, L.d_tgrad, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (step) *step = h->train_step;
+    if (step) *step = L.train_step;
     return SYN_OK;
 }
 
 // weight hand-off learner -> self-play (the reference does it through models/model_i.ot, alpha_zero.rs:97,194)
 int syn_trainer_publish_weights(syn_engine* h) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (h->trainer_kind == 1) {
+    auto& L = h->learner;
+    if (L.trainer_kind == 1) {
         // Connect4ConvNet: the fragment image of convnet.cuh is rebuilt from the canonical parameters on the device
         if (h->cap > LANE_MAX_CAP) return fail(h, SYN_ERR_UNSUPPORTED, "Connect4ConvNet runs in the lane-per-tree kernels only");
-        hipLaunchKernelGGL(conv_image_kernel, dim3((ConvGeom::IMG_FLOATS + 255) / 256), dim3(256), 0, h->stream, h->d_tw, h->d_wimg);
+        hipLaunchKernelGGL(conv_image_kernel, dim3((ConvGeom::IMG_FLOATS + 255) / 256), dim3(256), 0, h->stream, L.d_tw, h->d_wimg);
         HIP_TRY(h, hipGetLastError());
-        if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        // the f16x2 image is built on the host from the canonical parameters (conv_f16x2_tile.cuh): keep a copy of what was
-        // published; an engine in the f16x2 arithmetic stays in it, as Connect4Net's publish below does
-        h->host_blob.resize((size_t)ConvGeom::NUM_PARAMS);
-        HIP_TRY(h, hipMemcpyAsync(h->host_blob.data(), h->d_tw, (size_t)ConvGeom::NUM_PARAMS * 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        h->has_weights = true;
-        h->net_kind = 1;
-        h->img16_current = false;
-        if (h->net_arith == SYN_NET_ARITH_F16X2) return ensure_f16x2_image(h);
-        return SYN_OK;
+    } else {
+        // Connect4Net: the trainer keeps its weights in the inference fragment order as well (train_mfma.cuh): publishing is one device copy
+        HIP_TRY(h, hipMemcpyAsync(h->d_wimg, L.d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    // the trainer keeps its weights in the inference fragment order as well (train_mfma.cuh): publishing is one device copy
-    HIP_TRY(h, hipMemcpyAsync(h->d_wimg, h->d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
     if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));  // new network: empty PolicyWithCache
-    // the f16x2 image is built on the host from the canonical parameters: keep a copy of what was published
-    h->host_blob.resize((size_t)MlpGeom::NUM_PARAMS);
-    HIP_TRY(h, hipMemcpyAsync(h->host_blob.data(), h->d_tw, (size_t)MlpGeom::NUM_PARAMS * 4, hipMemcpyDeviceToHost, h->stream));
+    // the f16x2 image is built on the host from the canonical parameters (f16x2_tile.cuh / conv_f16x2_tile.cuh): keep a copy of what
+    // was published; an engine in the f16x2 arithmetic stays in it
+    const size_t bytes = learner_param_bytes(L.trainer_kind);
+    h->host_blob.resize(bytes / 4);
+    HIP_TRY(h, hipMemcpyAsync(h->host_blob.data(), L.d_tw, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->has_weights = true;
-    h->net_kind = 0;
+    h->net_kind = L.trainer_kind;
     h->img16_current = false;
     if (h->net_arith == SYN_NET_ARITH_F16X2) return ensure_f16x2_image(h);
     return SYN_OK;
@@ -2802,7 +2905,7 @@ static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_c
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (n_unique) *n_unique = 0;
     if (n_canonical) *n_canonical = 0;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    if (!h->learner.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
     const size_t n = h->replay_n;
     if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "the replay buffer is empty");
     if (mirror && n > DEDUP_MIRROR_MAX_N)
@@ -2820,22 +2923,11 @@ static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_c
     if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n);
     // the unique set becomes the learner's data set (the state syn_train_set_data leaves): syn_train_epoch stages in d_scratch too,
     // so it moves to d_train_data before this call returns
-    if (m > h->train_data_cap) {
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_train_data);
-        h->d_train_data = nullptr;
-        h->train_data_cap = 0;
-        h->train_data_n = 0;
-        const size_t want = m + m / 4;   // (the unique count drifts from iteration to iteration: do not reallocate for every rise)
-        HIP_TRY(h, hipMalloc(&h->d_train_data, want * 64));
-        h->train_data_cap = want;
-    }
-    unsigned char* base = static_cast<unsigned char*>(h->d_train_data);
-    HIP_TRY(h, hipMemcpyAsync(base, o.my, m * 8, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + m * 8, o.op, m * 8, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + m * 16, o.pi, m * 36, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(base + m * 52, o.v, m * 12, hipMemcpyDeviceToDevice, h->stream));
-    h->train_data_n = m;
+    rc = ensure_train_data(h, m, m + m / 4);   // (the unique count drifts from iteration to iteration: do not reallocate for every rise)
+    if (rc != SYN_OK) return rc;
+    rc = train_copy(h, train_sections(h->learner.d_train_data, m), TrainSource{o.my, o.op, o.pi, o.v}, m, hipMemcpyDeviceToDevice);
+    if (rc != SYN_OK) return rc;
+    h->learner.train_data_n = m;
     if (n_unique) *n_unique = m;
     if (n_canonical) *n_canonical = (size_t)o.m;
     return SYN_OK;
@@ -2855,18 +2947,18 @@ int syn_replay_deduplicate_to_trainer_symmetric(syn_engine* h, size_t* n_canonic
 
 int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity,
                        size_t* n) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!h->has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
-    const size_t m = h->train_data_n;
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    const size_t m = h->learner.train_data_n;
     if (n) *n = m;
     if (m > capacity) return fail(h, SYN_ERR_CAPACITY, "the learner's data set has %zu states, the caller's arrays %zu", m, capacity);
     if (m == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const unsigned char* base = static_cast<const unsigned char*>(h->d_train_data);
-    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, base, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, base + m * 8, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, base + m * 16, m * 36, hipMemcpyDeviceToHost, h->stream));
-    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, base + m * 52, m * 12, hipMemcpyDeviceToHost, h->stream));
+    const TrainSections data = train_sections(h->learner.d_train_data, m);
+    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, data.my, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, data.op, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, data.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
+    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, data.v, m * 12, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }

@@ -1,7 +1,7 @@
-// synthesis_amd — the learner step on the f32 matrix cores (replaces the VALU tiles of train_kernels.cuh).
+// synthesis_amd — the learner step on the f32 matrix cores.
 //
-// Same arithmetic as train_grad_kernel / oracle/train.hpp — alpha_zero.rs:72-94: forward, log_softmax + kl_div, backward — and the
-// same fixed-order fused-multiply-add chains, but every chain runs as v_mfma_f32_16x16x4_f32 (a k-ordered chain of fmas with one
+// The arithmetic of oracle/train.hpp — alpha_zero.rs:72-94: forward, log_softmax + kl_div, backward — in its fixed-order
+// fused-multiply-add chains, where every chain runs as v_mfma_f32_16x16x4_f32 (a k-ordered chain of fmas with one
 // rounding per term, the property the inference kernels already rely on):
 //   forward   Z[b][o]  = fma(x[K-1], w[K-1], ... fma(x[0], w[0], bias))     rows = 16 outputs, cols = 16 samples, k = inputs
 //   dA        dA[b][k] = chain over o ascending of fma(dZ[b][o], W[o][k], .) rows = 16 inputs,  cols = 16 samples, k = outputs
@@ -262,7 +262,7 @@ SYN_DEV void tm_gradients(const float* wimg, const float* timg, const unsigned l
         TM_FWD(0) TM_FWD(1) TM_FWD(2) TM_FWD(3) TM_FWD(4)
 #undef TM_FWD
         SYN_TSTAMP();  // forward
-        // ---- heads: log_softmax + kl_div and their gradient; one thread per (sample, head) — as train_grad_kernel
+        // ---- heads: log_softmax + kl_div and their gradient; one thread per (sample, head)
         if (tid < 2 * G::CHUNK) {
             const int b = tid >> 1, head = tid & 1;
             const int off = head == 0 ? 0 : 9, n = head == 0 ? 9 : 3;

@@ -192,6 +192,23 @@ def test_conv_learner_matches_oracle_and_feeds_selfplay(oracle, cblob, golden_di
     blob = np.load(os.path.join(golden_dir, "c4net_blob_f32.npy"))
     eng.trainer_init(blob)
     assert eng.trainer_state()["weights"].size == 30492
+    # ... and computes Connect4Net's steps in the buffers the two learners share (sized for the larger one)
+    gm = np.load(os.path.join(golden_dir, "train_torch_goldens.npz"))
+    ls = np.stack([eng.train_step(gm["my_bb"][s], gm["op_bb"][s], gm["target_pi"][s], gm["target_v"][s], float(gm["lrs"][s]))
+                   for s in range(2)])
+    st = eng.trainer_state()
+    X = np.stack([oracle.c4_features(gm["my_bb"][s], gm["op_bb"][s]) for s in range(2)])
+    wo, mo, vo, _, lo = oracle.train_steps(blob, default_train_hyper(), X, gm["target_pi"][:2], gm["target_v"][:2], gm["lrs"][:2])
+    assert st["step"] == 2 and np.array_equal(ls, lo)
+    assert np.array_equal(st["weights"], wo) and np.array_equal(st["m"], mo) and np.array_equal(st["v"], vo)
+    # and back to Connect4ConvNet: nothing of the larger network's parameters or moments is left behind
+    eng.trainer_init_conv(cblob)
+    eng.train_set_data(my.reshape(-1), op.reshape(-1), tpi.reshape(-1, 9), tv.reshape(-1, 3))
+    le = eng.train_epoch(np.arange(64, dtype=np.int32), 32, 1e-3)
+    st = eng.trainer_state()
+    wo2, mo2, vo2, _, lo2 = oracle.convtrain_steps(cblob, default_train_hyper(), my[:2], op[:2], tpi[:2], tv[:2], [1e-3] * 2)
+    assert st["step"] == 2 and np.array_equal(le, lo2)
+    assert np.array_equal(st["weights"], wo2) and np.array_equal(st["m"], mo2) and np.array_equal(st["v"], vo2)
     eng.close()
 
 

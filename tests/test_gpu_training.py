@@ -101,11 +101,12 @@ def test_device_resident_epoch_equals_step_by_step(engine, oracle, blob, gold):
         engine.train_epoch(np.array([n] * B, np.int32), B, 1e-3)  # index outside the uploaded buffer
 
 
-@pytest.mark.parametrize("B,steps_per_epoch", [(32, (5, 4, 1)), (7, (3, 2)), (1, (2,))])
+@pytest.mark.parametrize("B,steps_per_epoch", [(32, (5, 4, 1)), (7, (3, 2)), (1, (2,)), (33, (2, 1))])
 def test_persistent_epoch_kernel_chains_epochs(engine, oracle, blob, gold, B, steps_per_epoch):
     """The one-launch epoch kernel (train_epoch.cuh): consecutive epochs of odd and even length (the final network ends in either
     image buffer), short batches, non-default hyper-parameters and a changing learning rate — weights, moments, losses and the
-    last step's gradients equal the oracle's, and the published network is the trained one."""
+    last step's gradients equal the oracle's, and the published network is the trained one. A batch above the 32-sample chunk
+    (33) runs the same epochs through the two queued launches per step."""
     from tests.oracle_lib import default_train_hyper
 
     my = gold["my_bb"].reshape(-1); op = gold["op_bb"].reshape(-1)
@@ -170,6 +171,39 @@ def test_epoch_kernel_recovery_keeps_the_learner(engine, oracle, blob, gold, mon
                                            np.concatenate([tv[idx], tv[idx[:3]]]), [1e-3] * (2 * steps) + [2e-3] * 3)
     assert np.array_equal(engine.trainer_state()["weights"], wo2) and np.array_equal(l2, lo2[-3:])
     engine.load_weights(blob)
+
+
+def test_data_set_survives_later_inits(oracle, blob, gold):
+    """The first syn_trainer_init on an engine discards an uploaded data set (its start-up self-check uploads a synthetic one):
+    syn_train_epoch then asks for syn_train_set_data. Later inits keep the data set."""
+    import synthesis_amd as sa
+    from tests.oracle_lib import default_train_hyper
+
+    my = gold["my_bb"].reshape(-1); op = gold["op_bb"].reshape(-1)
+    tpi = gold["target_pi"].reshape(-1, 9); tv = gold["target_v"].reshape(-1, 3)
+    B, steps = 7, 2
+    perm = np.random.default_rng(3).integers(0, my.size, size=steps * B).astype(np.int32)
+    eng = sa.Engine(concurrent_games=64, max_explores=64)
+    try:
+        eng.trainer_init(blob)
+        eng.train_set_data(my, op, tpi, tv)
+        eng.trainer_init(blob)
+        losses = eng.train_epoch(perm, B, 1e-3)
+        st = eng.trainer_state()
+    finally:
+        eng.close()
+    idx = perm.reshape(steps, B)
+    X = oracle.c4_features(my, op)
+    wo, mo, vo, _, lo = oracle.train_steps(blob, default_train_hyper(), X[idx], tpi[idx], tv[idx], [1e-3] * steps)
+    assert st["step"] == steps and np.array_equal(losses, lo)
+    assert np.array_equal(st["weights"], wo) and np.array_equal(st["m"], mo) and np.array_equal(st["v"], vo)
+    eng = sa.Engine(concurrent_games=64, max_explores=64)
+    try:
+        eng.trainer_init(blob)
+        with pytest.raises(sa.SynthesisAmdError, match="call syn_train_set_data first"):
+            eng.train_epoch(perm, B, 1e-3)
+    finally:
+        eng.close()
 
 
 def test_data_parallel_gradient_path(engine, oracle, blob, gold):
