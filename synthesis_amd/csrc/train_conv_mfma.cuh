@@ -292,8 +292,11 @@ SYN_DEV void conv_grad_step_mfma(const float* __restrict__ w, const unsigned lon
 // B[4 q + e][j], e = 0..3, f32 accumulation), master weights, Adam moments, the softmax / KL head and every accumulator in f32.
 // K = 16 per instruction: the conv is 2 MFMAs per cell (18 taps, padded to 32), the head ONE (its k = the 16 channels: a lane's
 // four ReLU outputs are exactly its four k elements), dWh 2 per column tile, dY 1, dWc 4 per sample and tap tile. NOT bit-exact
-// with anything and never used for inference (bf16 cannot hold the 1e-5 bar): tests hold its gradients and an 8-step run to the f32
-// learner within bf16's error. Tap inputs (0 / 1) are exact in bf16; what is rounded: weights, activations, dz, dY.
+// with anything and never used for inference (bf16 cannot hold the 1e-5 bar): tests hold its gradients to a float64 model of this step
+// with bf16-rounded operands (tests/conv_bf16_learner_model.py; tests/test_gpu_conv_bf16_learner.py) — on checkpoints whose forward
+// pass is exact in any order inside n * 2^-23 * sum|terms| of every chain (+ the bf16 ulps of the dY entries a rounding boundary could
+// flip), elsewhere inside 8 x the model's own f32 summation-order noise; DESIGN.md §6.4, profiles/conv_bf16_learner_bars.txt.
+// Tap inputs (0 / 1) are exact in bf16; what is rounded: weights, activations (head, dWh), dz, dY — not the conv bias, not dbh.
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 SYN_DEV bf16x4 pack_bf16(float a, float b, float c, float d) { return bf16x4{(__bf16)a, (__bf16)b, (__bf16)c, (__bf16)d}; }
 

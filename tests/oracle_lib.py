@@ -400,11 +400,16 @@ class Oracle:
         return blob, m, v, st.value, losses
 
     def train_adam(self, blob, hp, grad, lr, m, v, step):
-        blob = np.array(blob, np.float32).copy(); m = np.array(m, np.float32).copy(); v = np.array(v, np.float32).copy()
-        grad = np.ascontiguousarray(grad, np.float32)
+        """One Adam update (Trainer::adam = ConvTrainer::adam: the same expression per element). orc_train_adam works on Connect4Net's
+        30,492 floats: a shorter parameter vector (Connect4ConvNet's 12,412) is padded with zeros for the call — handing it over as it
+        is made the oracle read and write past the end of all four arrays."""
+        n, full = np.size(blob), 30492
+        assert n <= full and np.size(grad) == n and np.size(m) == n and np.size(v) == n
+        pad = lambda a: np.concatenate([np.asarray(a, np.float32).ravel(), np.zeros(full - n, np.float32)])
+        blob, m, v, grad = pad(blob), pad(m), pad(v), pad(grad)
         st = C.c_longlong(step)
         self.lib.orc_train_adam(_p(blob), C.byref(hp), _p(grad), C.c_float(lr), _p(m), _p(v), C.byref(st))
-        return blob, m, v, st.value
+        return blob[:n].copy(), m[:n].copy(), v[:n].copy(), st.value
 
     def dedup(self, my_bb, op_bb, pis, vs):
         my = np.ascontiguousarray(my_bb, np.uint64); op = np.ascontiguousarray(op_bb, np.uint64)
