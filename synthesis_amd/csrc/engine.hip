@@ -111,16 +111,25 @@ struct syn_engine {
     uint32_t cap = 0;
     float4* d_stat = nullptr;
     uint4* d_edge = nullptr;
-    float* d_wimg = nullptr;
-    int net_kind = 0;  // which network d_wimg holds: 0 = Connect4Net (mlp.cuh), 1 = Connect4ConvNet (convnet.cuh)
-    // The network in the f16x2 arithmetic (syn_set_network_arithmetic; Connect4Net: f16x2_tile.cuh, Connect4ConvNet:
-    // conv_f16x2_tile.cuh): its image, the parameters it is built from (host copy of the current network's blob, refreshed by
-    // syn_load_weights* / syn_trainer_publish_weights) and whether the image is current
-    int net_arith = SYN_NET_ARITH_F32;
-    uint32_t* d_wimg16 = nullptr;
-    std::vector<float> host_blob;
-    bool img16_current = false;
-    bool has_weights = false;
+    // The network the engine evaluates, in which arithmetic, and its images. Written by install_network (syn_load_weights*,
+    // syn_trainer_publish_weights) and syn_set_network_arithmetic only.
+    // Invariant: an engine with weights in the f16x2 arithmetic holds a current f16x2 image (img16_current, of host_blob, which is the
+    // network d_wimg holds). A load or a switch that is refused for want of an f16x2 plan returns before anything here, or the policy
+    // cache, changes. Two corners leave arith == F16X2 with img16_current == false, and every evaluation is then refused
+    // (require_f16x2_image, SYN_ERR_UNSUPPORTED) until a load, a publish or a switch succeeds: a publish of parameters that have no
+    // plan (the f32 image and host_blob are the new network's by then), and a HIP error in the middle of an image upload.
+    struct Network {
+        int kind = 0;   // which network d_wimg holds: 0 = Connect4Net (mlp.cuh), 1 = Connect4ConvNet (convnet.cuh); index of g_net_desc
+        int arith = SYN_NET_ARITH_F32;   // syn_set_network_arithmetic (Connect4Net: f16x2_tile.cuh, Connect4ConvNet: conv_f16x2_tile.cuh)
+        bool has_weights = false;
+        float* d_wimg = nullptr;         // the f32 image (allocated with the engine, sized for Connect4Net's, the larger one)
+        uint32_t* d_wimg16 = nullptr;    // the f16x2 image (allocated on first use, likewise)
+        std::vector<float> host_blob;    // the current network's parameters: what the f16x2 image and plan are built from
+        bool img16_current = false;      // d_wimg16 is the image of host_blob
+        bool f16x2() const { return arith == SYN_NET_ARITH_F16X2; }
+        // the image the current arithmetic evaluates
+        const float* image() const { return f16x2() ? reinterpret_cast<const float*>(d_wimg16) : d_wimg; }
+    } net;
     int* d_job_next = nullptr;
     uint4* d_cache = nullptr;      // PolicyWithCache table (policy_cache_log2 > 0)
     int cache_log2 = 0;
@@ -149,7 +158,7 @@ struct syn_engine {
     // scratch for host-pointer entry points
     void* d_scratch = nullptr;
     size_t scratch_bytes = 0;
-    std::atomic<bool> eval_attr_set[6] = {{false}, {false}, {false}, {false}, {false}, {false}};   // launch_policy_eval: the kernels' LDS attribute is set
+    std::atomic<bool> eval_attr_set[EVAL_KERNELS] = {};   // launch_eval: the kernel's LDS attribute is set (indexed by EvalKernel)
     size_t eval_poll_max = 1024;       // contexts: batches up to this size signal completion through pinned memory (SYN_DEBUG=1 SYN_EVAL_POLL_MAX)
     size_t eval_zero_copy_out = 4096;  // contexts: results of up to this many positions are written into the pinned buffer by the kernel itself
     struct syn_eval_ctx* eval_ctx = nullptr;   // syn_policy_eval_batch's own evaluation context (created on first use)
@@ -475,8 +484,8 @@ static int launch_engine(syn_engine* h, const EngineParams& P, int jobs, int mod
     q.slots = h->slots;
     q.jobs = jobs;
     q.cap = h->cap;
-    q.net_kind = h->net_kind;
-    q.f16 = h->net_arith == SYN_NET_ARITH_F16X2 && P.wimg == reinterpret_cast<const float*>(h->d_wimg16);
+    q.net_kind = h->net.kind;
+    q.f16 = h->net.f16x2() && P.wimg == h->net.image();
     q.pool_trees = h->pool_trees;
     q.mode = mode;
     q.count = count;
@@ -579,7 +588,7 @@ int syn_engine_create(const syn_engine_config* cfg, int device, syn_engine** out
         if ((e = hipMemsetAsync(h->d_cache, 0, bytes, h->stream)) != hipSuccess) return bail("hipMemsetAsync(policy cache)", e);
     }
     if ((e = hipMalloc(&h->d_cache_stats, 16)) != hipSuccess) return bail("hipMalloc(cache stats)", e);
-    if ((e = hipMalloc(&h->d_wimg, MlpGeom::IMG_FLOATS * sizeof(float))) != hipSuccess) return bail("hipMalloc(wimg)", e);
+    if ((e = hipMalloc(&h->net.d_wimg, MlpGeom::IMG_FLOATS * sizeof(float))) != hipSuccess) return bail("hipMalloc(wimg)", e);
     if ((e = hipMalloc(&h->d_job_next, 64)) != hipSuccess) return bail("hipMalloc(job)", e);
     if ((e = hipMemsetAsync(h->d_job_next, 0, 64, h->stream)) != hipSuccess) return bail("hipMemsetAsync(job)", e);  // syn_progress before the first launch reads zeros
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return bail("hipStreamSynchronize", e);
@@ -594,8 +603,8 @@ int syn_engine_destroy(syn_engine* h) {
     if (h->eval_ctx) syn_eval_ctx_destroy(h->eval_ctx);
     if (h->stream) hipStreamSynchronize(h->stream);
     hipFree(h->d_stat);
-    hipFree(h->d_wimg);
-    hipFree(h->d_wimg16);
+    hipFree(h->net.d_wimg);
+    hipFree(h->net.d_wimg16);
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
@@ -624,29 +633,79 @@ int syn_engine_destroy(syn_engine* h) {
     return SYN_OK;
 }
 
-// The f16x2 image of the engine's Connect4Net (f16x2_tile.cuh: build_f16x2_image). State is committed only after the image exists:
-// a blob without an f16x2 plan (non-finite values, scales outside the window) leaves the engine exactly as it was — arithmetic,
-// parameters, both images and the policy cache — so nothing can evaluate a stale or missing image afterwards.
-// (Connect4ConvNet's image, conv_f16x2_tile.cuh, lives in the same buffer: it is the smaller of the two)
-static int upload_f16x2_image(syn_engine* h, const std::vector<uint32_t>& words) {
-    HIP_TRY(h, hipSetDevice(h->device));   // (reached through common_params before the entry point's own hipSetDevice)
-    if (!h->d_wimg16) HIP_TRY(h, hipMalloc(&h->d_wimg16, (size_t)F16Geom::IMG_WORDS * 4));
-    HIP_TRY(h, hipMemcpyAsync(h->d_wimg16, words.data(), words.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return SYN_OK;
-}
-// the f16x2 image of a blob of network `kind` (0 = Connect4Net, 1 = Connect4ConvNet); false = the blob has no f16x2 plan
-static bool build_f16x2_words(int kind, const float* blob, std::vector<uint32_t>& words) {
-    if (kind == 1) {
-        ConvF16Image im;
-        if (!build_conv_f16x2_image(blob, im)) return false;
-        words.swap(im.words);
-        return true;
-    }
+// ------------------------------------------------------------------------------------------------ the engine's network
+// (state and invariant: syn_engine::Network)
+// What differs between the two networks on the host, indexed by Network::kind.
+struct NetDesc {
+    const char* name;   // as messages say it
+    int num_params;
+    bool lane_only;     // evaluated by the lane-per-tree kernels only: engines of more than LANE_MAX_CAP nodes per tree cannot hold it
+    void (*build_f32)(const float* blob, std::vector<float>& img);          // the f32 fragment image of a blob
+    bool (*build_f16x2)(const float* blob, std::vector<uint32_t>& words);   // its f16x2 image; false = the blob has no f16x2 plan
+    size_t param_bytes() const { return (size_t)num_params * 4; }
+};
+static bool build_mlp_f16x2_words(const float* blob, std::vector<uint32_t>& words) {
     F16Image im;
     if (!build_f16x2_image(blob, im)) return false;
     words.swap(im.words);
     return true;
+}
+static bool build_conv_f16x2_words(const float* blob, std::vector<uint32_t>& words) {
+    ConvF16Image im;
+    if (!build_conv_f16x2_image(blob, im)) return false;
+    words.swap(im.words);
+    return true;
+}
+static void build_conv_image_vec(const float* blob, std::vector<float>& img) {
+    img.resize((size_t)ConvGeom::IMG_FLOATS);
+    build_conv_image(blob, img.data());
+}
+static const NetDesc g_net_desc[2] = {
+    {"Connect4Net", MlpGeom::NUM_PARAMS, false, build_weight_image, build_mlp_f16x2_words},
+    {"Connect4ConvNet", ConvGeom::NUM_PARAMS, true, build_conv_image_vec, build_conv_f16x2_words},
+};
+static_assert(TrainGeom::NUM_PARAMS == MlpGeom::NUM_PARAMS, "the learner's Connect4Net is the engine's");
+static_assert(ConvGeom::IMG_FLOATS <= MlpGeom::IMG_FLOATS && ConvF16Geom::IMG_WORDS <= F16Geom::IMG_WORDS,
+              "both image buffers are sized for Connect4Net");
+
+// The one text and status of each refusal in this section; the evaluation contexts put the same texts into their own error slot.
+static const char* const MSG_NO_WEIGHTS = "call syn_load_weights first";
+static const char* const MSG_NO_F16X2_IMAGE = "the engine is in the f16x2 arithmetic but holds no f16x2 image of its parameters";
+static bool lacks_f16x2_image(const syn_engine* h) { return h->net.f16x2() && (!h->net.img16_current || !h->net.d_wimg16); }
+static int require_weights(syn_engine* h) { return h->net.has_weights ? SYN_OK : fail(h, SYN_ERR_NO_WEIGHTS, "%s", MSG_NO_WEIGHTS); }
+// every path that evaluates a network in the f16x2 arithmetic checks this first
+static int require_f16x2_image(syn_engine* h) { return lacks_f16x2_image(h) ? fail(h, SYN_ERR_UNSUPPORTED, "%s", MSG_NO_F16X2_IMAGE) : SYN_OK; }
+// Fpu::Func, PolicyNoise::Dirichlet, Connect4ConvNet and the f16x2 arithmetic exist in the lane-per-tree kernels only, whose block ids
+// are 14 bits: an engine created for more than 7,280 explores cannot run them. Said before anything is enqueued or changed.
+static int require_lane_cap(syn_engine* h, const char* what) {
+    if (h->cap <= LANE_MAX_CAP) return SYN_OK;
+    return fail(h, SYN_ERR_UNSUPPORTED, "%s runs in the lane-per-tree kernels only: max_explores must be <= %u (this engine: %d)", what,
+                (LANE_MAX_CAP - 1u) / 9u - 1u, h->max_explores);
+}
+static int require_lane_cap_of_network(syn_engine* h, int kind) {
+    return g_net_desc[kind].lane_only ? require_lane_cap(h, g_net_desc[kind].name) : SYN_OK;
+}
+// the f16x2 image of `blob`, parameters of network `kind`, or the one refusal of parameters that have no plan
+static int f16x2_image_of(syn_engine* h, int kind, const float* blob, std::vector<uint32_t>& words) {
+    if (g_net_desc[kind].build_f16x2(blob, words)) return SYN_OK;
+    return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values or scales outside the f32-safe window): a load "
+                                        "or a switch leaves the engine as it was, a publish leaves it without an f16x2 image");
+}
+// PolicyWithCache entries belong to the network and the arithmetic that produced them (the reference builds a fresh cache per
+// run_n_games, alpha_zero.rs:196-198; the two arithmetics differ in the last bits): an all-zero entry never verifies. Stream-ordered
+// before every launch that reads the table.
+static int empty_policy_cache(syn_engine* h) {
+    if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));
+    return SYN_OK;
+}
+
+// (Connect4ConvNet's f16x2 image, conv_f16x2_tile.cuh, lives in the same buffer as Connect4Net's: it is the smaller of the two)
+static int upload_f16x2_image(syn_engine* h, const std::vector<uint32_t>& words) {
+    HIP_TRY(h, hipSetDevice(h->device));   // (every caller has selected it by now; kept because this helper allocates: test_abi_and_host.py)
+    if (!h->net.d_wimg16) HIP_TRY(h, hipMalloc(&h->net.d_wimg16, (size_t)F16Geom::IMG_WORDS * 4));
+    HIP_TRY(h, hipMemcpyAsync(h->net.d_wimg16, words.data(), words.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
 }
 // the plan of a blob, selected by its size (30,492 floats: Connect4Net, five layers; 12,412: Connect4ConvNet, layer 0 = the conv
 // layer whose inputs enter unscaled, layer 1 = the head, entries 2..4 zero); plan->valid = 0 when it has none
@@ -669,95 +728,104 @@ static void fill_f16x2_plan(const float* blob, size_t n_floats, syn_f16x2_plan* 
         }
     }
 }
-static int no_f16x2_plan(syn_engine* h) {
-    return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values or scales outside the f32-safe window); "
-                                        "the engine keeps its previous network and arithmetic");
-}
-// (re)builds the image from the engine's own copy of the parameters when it is not current (after syn_trainer_publish_weights)
+// builds the f16x2 image from the engine's own copy of the parameters when it is not current (a switch into the arithmetic; a publish
+// while in it) and commits it; a refusal leaves everything as it was
 static int ensure_f16x2_image(syn_engine* h) {
-    if (h->img16_current) return SYN_OK;
-    if (h->host_blob.size() != (size_t)(h->net_kind == 1 ? ConvGeom::NUM_PARAMS : MlpGeom::NUM_PARAMS))
+    auto& N = h->net;
+    if (N.img16_current) return SYN_OK;
+    if (N.host_blob.size() != (size_t)g_net_desc[N.kind].num_params)
         return fail(h, SYN_ERR_UNSUPPORTED, "the engine holds no host copy of its parameters to build the f16x2 image from");
     std::vector<uint32_t> words;
-    if (!build_f16x2_words(h->net_kind, h->host_blob.data(), words))
-        return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values or scales outside the f32-safe window)");
-    const int rc = upload_f16x2_image(h, words);
+    int rc = f16x2_image_of(h, N.kind, N.host_blob.data(), words);
+    if (rc == SYN_OK) rc = upload_f16x2_image(h, words);
     if (rc != SYN_OK) return rc;
-    h->img16_current = true;
-    return SYN_OK;
-}
-// every path that evaluates a network in the f16x2 arithmetic checks this first
-static int require_f16x2_image(syn_engine* h) {
-    if (h->net_arith != SYN_NET_ARITH_F16X2) return SYN_OK;
-    if (!h->img16_current || !h->d_wimg16)
-        return fail(h, SYN_ERR_UNSUPPORTED, "the engine is in the f16x2 arithmetic but holds no f16x2 image of its parameters");
+    N.img16_current = true;
     return SYN_OK;
 }
 
-int syn_load_weights(syn_engine* h, const float* blob, size_t n_floats) {
+// The one way a network becomes the engine's (the caller has selected the engine's device and checked require_lane_cap_of_network): `blob` = its parameters on the host (syn_load_weights*), or NULL = the learner's, on the
+// device (syn_trainer_publish_weights). Order: (host parameters, f16x2 arithmetic) the f16x2 image is built first and a blob without a
+// plan is refused before anything of the engine changes; the images; the policy cache; then the state is committed. A publish cannot
+// know whether its parameters have a plan before it has read them back, by which time the f32 image is the new network's: it commits,
+// then builds the f16x2 image, and a refusal there is the corner Network's invariant names.
+static int install_network(syn_engine* h, int kind, const float* blob) {
+    auto& N = h->net;
+    const NetDesc& d = g_net_desc[kind];
+    const bool want16 = N.f16x2();
+    if (blob) {
+        std::vector<uint32_t> im16;
+        if (want16) { const int rc = f16x2_image_of(h, kind, blob, im16); if (rc != SYN_OK) return rc; }
+        std::vector<float> img;
+        d.build_f32(blob, img);
+        if (want16) {
+            N.img16_current = false;
+            const int rc = upload_f16x2_image(h, im16);
+            if (rc != SYN_OK) return rc;
+        }
+        HIP_TRY(h, hipMemcpyAsync(N.d_wimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    } else if (kind == 1) {
+        // Connect4ConvNet: the fragment image of convnet.cuh is rebuilt from the canonical parameters on the device
+        hipLaunchKernelGGL(conv_image_kernel, dim3((ConvGeom::IMG_FLOATS + 255) / 256), dim3(256), 0, h->stream, h->learner.d_tw, N.d_wimg);
+        HIP_TRY(h, hipGetLastError());
+    } else {
+        // Connect4Net: the trainer keeps its weights in the inference fragment order as well (train_mfma.cuh): publishing is one device copy
+        HIP_TRY(h, hipMemcpyAsync(N.d_wimg, h->learner.d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
+    }
+    { const int rc = empty_policy_cache(h); if (rc != SYN_OK) return rc; }
+    if (blob) {
+        N.host_blob.assign(blob, blob + d.num_params);
+    } else {
+        // the f16x2 image is built on the host from the canonical parameters: keep a copy of what was published
+        N.host_blob.resize((size_t)d.num_params);
+        HIP_TRY(h, hipMemcpyAsync(N.host_blob.data(), h->learner.d_tw, d.param_bytes(), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    N.has_weights = true;
+    N.kind = kind;
+    N.img16_current = blob && want16;
+    return !blob && want16 ? ensure_f16x2_image(h) : SYN_OK;   // an engine in the f16x2 arithmetic stays in it
+}
+
+static int check_blob(syn_engine* h, int kind, const float* blob, size_t n_floats) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (!blob) return fail(h, SYN_ERR_INVALID_ARGUMENT, "blob is NULL");
-    if (n_floats != (size_t)MlpGeom::NUM_PARAMS)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4Net has %d parameters, got %zu", MlpGeom::NUM_PARAMS, n_floats);
+    const NetDesc& d = g_net_desc[kind];
+    if (n_floats != (size_t)d.num_params) return fail(h, SYN_ERR_INVALID_ARGUMENT, "%s has %d parameters, got %zu", d.name, d.num_params, n_floats);
+    return require_lane_cap_of_network(h, kind);
+}
+int syn_load_weights(syn_engine* h, const float* blob, size_t n_floats) {
+    const int rc = check_blob(h, 0, blob, n_floats);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    std::vector<uint32_t> im16;
-    const bool want16 = h->net_arith == SYN_NET_ARITH_F16X2;
-    if (want16 && !build_f16x2_words(0, blob, im16)) return no_f16x2_plan(h);   // (before anything of the engine changes)
-    std::vector<float> img;
-    build_weight_image(blob, img);
-    if (want16) {
-        h->img16_current = false;
-        const int rc = upload_f16x2_image(h, im16);
-        if (rc != SYN_OK) return rc;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_wimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    // PolicyWithCache entries belong to the network that produced them (the reference builds a fresh cache per
-    // run_n_games, alpha_zero.rs:196-198): a new network starts with an empty table
-    if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));
-    h->has_weights = true;
-    h->net_kind = 0;
-    h->host_blob.assign(blob, blob + n_floats);
-    h->img16_current = want16;
-    return SYN_OK;
+    return install_network(h, 0, blob);
+}
+int syn_load_weights_conv(syn_engine* h, const float* blob, size_t n_floats) {
+    const int rc = check_blob(h, 1, blob, n_floats);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return install_network(h, 1, blob);
 }
 
 int syn_set_network_arithmetic(syn_engine* h, int arithmetic) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (arithmetic != SYN_NET_ARITH_F32 && arithmetic != SYN_NET_ARITH_F16X2)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown network arithmetic %d", arithmetic);
-    if (arithmetic == h->net_arith) return SYN_OK;
-    if (arithmetic == SYN_NET_ARITH_F16X2) {
-        if (h->cap > LANE_MAX_CAP)
-            return fail(h, SYN_ERR_UNSUPPORTED, "the f16x2 arithmetic runs in the lane-per-tree kernels: max_explores must be <= %u",
-                        (LANE_MAX_CAP - 1u) / 9u - 1u);
-    }
+    if (arithmetic == h->net.arith) return SYN_OK;
+    if (arithmetic == SYN_NET_ARITH_F16X2) { const int rc = require_lane_cap(h, "the f16x2 arithmetic"); if (rc != SYN_OK) return rc; }
     HIP_TRY(h, hipSetDevice(h->device));
-    if (arithmetic == SYN_NET_ARITH_F16X2 && h->has_weights && !h->img16_current) {
-        // the image first (of whichever network the engine holds); the switch is committed only when it exists
-        if (h->host_blob.size() != (size_t)(h->net_kind == 1 ? ConvGeom::NUM_PARAMS : MlpGeom::NUM_PARAMS))
-            return fail(h, SYN_ERR_UNSUPPORTED, "the engine holds no host copy of its parameters to build the f16x2 image from");
-        std::vector<uint32_t> words;
-        if (!build_f16x2_words(h->net_kind, h->host_blob.data(), words)) return no_f16x2_plan(h);
-        const int rc = upload_f16x2_image(h, words);
-        if (rc != SYN_OK) return rc;
-        h->img16_current = true;
-    }
-    h->net_arith = arithmetic;
-    // PolicyWithCache entries belong to the arithmetic that produced them: the two differ in the last bits
-    if (h->d_cache) {
-        HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    return SYN_OK;
+    // the image first (of whichever network the engine holds); the switch is committed only when it exists
+    if (arithmetic == SYN_NET_ARITH_F16X2 && h->net.has_weights) { const int rc = ensure_f16x2_image(h); if (rc != SYN_OK) return rc; }
+    h->net.arith = arithmetic;
+    return empty_policy_cache(h);
 }
 
 int syn_get_network_arithmetic(syn_engine* h, int* arithmetic, syn_f16x2_plan* plan) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (arithmetic) *arithmetic = h->net_arith;
+    if (arithmetic) *arithmetic = h->net.arith;
     if (plan) {
         std::memset(plan, 0, sizeof(*plan));
-        if (h->has_weights && !h->host_blob.empty()) fill_f16x2_plan(h->host_blob.data(), h->host_blob.size(), plan);
+        if (h->net.has_weights && !h->net.host_blob.empty()) fill_f16x2_plan(h->net.host_blob.data(), h->net.host_blob.size(), plan);
     }
     return SYN_OK;
 }
@@ -769,111 +837,66 @@ int syn_f16x2_plan_of_blob(const float* blob, size_t n_floats, syn_f16x2_plan* p
     return SYN_OK;
 }
 
-int syn_load_weights_conv(syn_engine* h, const float* blob, size_t n_floats) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (!blob) return fail(h, SYN_ERR_INVALID_ARGUMENT, "blob is NULL");
-    if (n_floats != (size_t)ConvGeom::NUM_PARAMS)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4ConvNet has %d parameters, got %zu", ConvGeom::NUM_PARAMS, n_floats);
-    if (h->cap > LANE_MAX_CAP)
-        return fail(h, SYN_ERR_UNSUPPORTED, "Connect4ConvNet runs in the lane-per-tree kernels: max_explores must be <= %d",
-                    (LANE_MAX_CAP - 1) / 9 - 1);
-    HIP_TRY(h, hipSetDevice(h->device));
-    // an engine in the f16x2 arithmetic evaluates the new network in it: its image first (conv_f16x2_tile.cuh), before anything of
-    // the engine changes
-    std::vector<uint32_t> im16;
-    const bool want16 = h->net_arith == SYN_NET_ARITH_F16X2;
-    if (want16 && !build_f16x2_words(1, blob, im16)) return no_f16x2_plan(h);
-    std::vector<float> img((size_t)ConvGeom::IMG_FLOATS);
-    build_conv_image(blob, img.data());
-    if (want16) {
-        h->img16_current = false;
-        const int rc = upload_f16x2_image(h, im16);
-        if (rc != SYN_OK) return rc;
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_wimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));  // a new network: empty cache
-    h->has_weights = true;
-    h->net_kind = 1;
-    h->host_blob.assign(blob, blob + n_floats);
-    h->img16_current = want16;
-    return SYN_OK;
+// ------------------------------------------------------------------------------------------------ policy evaluation
+// Which kernel evaluates a batch is decided in launch_plan.hpp (plan_eval: a pure function, tested on a CPU). Here: the table from its
+// kernel ids to the functions and the one place that launches them.
+using EvalFnF32 = void (*)(const float*, const unsigned long long*, const unsigned long long*, int, float*, float*);
+using EvalFnF16 = void (*)(const uint32_t*, const unsigned long long*, const unsigned long long*, int, float*, float*);
+using EvalFnTile = void (*)(const float*, const unsigned long long*, const unsigned long long*, int, float*, float*, unsigned*, unsigned*, unsigned);
+struct EvalKernelEntry {
+    EvalFnF32 f32;     // exactly one of the three is set: the kernel reads the f32 image,
+    EvalFnF16 f16;     // ... the f16x2 image,
+    EvalFnTile tile;   // ... or is the latency kernel (f32 image + the completion protocol's three arguments)
+};
+static const EvalKernelEntry g_eval_kernels[EVAL_KERNELS] = {
+    /* EVAL_TILE */ {nullptr, nullptr, policy_eval_tile_kernel},
+    /* EVAL_MLP_512 */ {policy_eval_kernel<512>, nullptr, nullptr},
+    /* EVAL_MLP_768 */ {policy_eval_kernel<768>, nullptr, nullptr},
+    /* EVAL_CONV_512 */ {policy_eval_conv_kernel<512>, nullptr, nullptr},
+    /* EVAL_F16_512 */ {nullptr, policy_eval_f16x2_kernel<512>, nullptr},
+    /* EVAL_F16_1024 */ {nullptr, policy_eval_f16x2_kernel<1024>, nullptr},
+    /* EVAL_CONV_F16_512 */ {nullptr, policy_eval_conv_f16x2_kernel<512>, nullptr},
+};
+static_assert(EVAL_TILE == 0 && EVAL_MLP_512 == 1 && EVAL_MLP_768 == 2 && EVAL_CONV_512 == 3 && EVAL_F16_512 == 4 && EVAL_F16_1024 == 5 &&
+              EVAL_CONV_F16_512 == 6 && EVAL_KERNELS == 7, "g_eval_kernels is in EvalKernel's order");
+static_assert(PLAN_MLP_IMG_BYTES == (size_t)MlpGeom::IMG_FLOATS * 4 && PLAN_CONV_IMG_BYTES == (size_t)ConvGeom::IMG_FLOATS * 4 &&
+              PLAN_F16_IMG_BYTES == (size_t)F16Geom::IMG_WORDS * 4 && PLAN_CONV_F16_IMG_BYTES == (size_t)ConvF16Geom::IMG_WORDS * 4,
+              "launch_plan.hpp restates mlp.cuh, convnet.cuh, f16x2_tile.cuh and conv_f16x2_tile.cuh");
+constexpr size_t EVAL_TILE_LDS = 14 * 64 * 16;   // policy_eval_tile_kernel (eval_small.cuh): exA 8 x 64 x 16 B + exB 6 x 64 x 16 B
+static_assert(PLAN_EVAL_TILE_LDS == EVAL_TILE_LDS && EVAL_TILE_LDS <= 64 * 1024, "launch_plan.hpp restates the tile kernel's LDS; it needs no attribute");
+
+// the completion protocol of a polled call (eval_small.cuh): workgroups finished, the pinned word, this call's number
+struct EvalCompletion {
+    unsigned* done_blocks = nullptr;
+    unsigned* host_flag = nullptr;
+    unsigned seq = 0u;
+};
+static EvalQuery eval_query(const syn_engine* h, int n) {
+    EvalQuery q;
+    q.net_kind = h->net.kind;
+    q.f16 = h->net.f16x2();
+    q.n = n;
+    q.num_cus = h->num_cus;
+    return q;
 }
-
-constexpr size_t EVAL_TILE_LDS = 14 * 64 * 16;   // policy_eval_tile_kernel: the two activation-exchange buffers
-constexpr size_t EVAL_TILE_MAX = 4096;           // ... is used up to this many positions (256 tiles: one per CU)
-
-// The evaluation kernel of the engine's network on `st` (any stream of the engine's device): n positions, pointers the device can
+// The plan's kernel over the engine's network on `st` (any stream of the engine's device): n positions, pointers the device can
 // read / write (device memory or pinned, device-mapped host memory).
-static hipError_t launch_policy_eval(syn_engine* h, hipStream_t st, const uint64_t* d_my, const uint64_t* d_op, int n,
-                                     float* d_logits, float* d_value) {
-    // Two waves per SIMD (512 threads): one wave's LDS reads / feature math overlap the other's MFMAs. Large batches (every
-    // wave gets several tiles) run three waves per SIMD, which also hides the loads and stores around the tiles.
-    const int ntiles = (n + 15) / 16;
-    hipError_t e;
-#define SYN_LAUNCH_EVAL(KERNEL, NT, LDS, SLOT)                                                                                 \
-    {                                                                                                                          \
-        auto k = KERNEL<NT>;                                                                                                   \
-        if (!h->eval_attr_set[SLOT].load(std::memory_order_acquire)) { /* once per engine: the call costs a microsecond */     \
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                         (int)(LDS))) != hipSuccess)                                                           \
-                return e;                                                                                                      \
-            h->eval_attr_set[SLOT].store(true, std::memory_order_release);                                                     \
-        }                                                                                                                      \
-        int grid = (ntiles + NT / 64 - 1) / (NT / 64);                                                                         \
-        if (grid > h->num_cus) grid = h->num_cus;                                                                              \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(NT), (LDS), st, h->d_wimg, reinterpret_cast<const unsigned long long*>(d_my),    \
-                           reinterpret_cast<const unsigned long long*>(d_op), n, d_logits, d_value);                           \
+static hipError_t launch_eval(syn_engine* h, const EvalPlan& p, hipStream_t st, const uint64_t* d_my, const uint64_t* d_op, int n,
+                              float* d_logits, float* d_value, const EvalCompletion& done = EvalCompletion()) {
+    const EvalKernelEntry& k = g_eval_kernels[p.kernel];
+    const void* fn = k.tile ? reinterpret_cast<const void*>(k.tile) : k.f16 ? reinterpret_cast<const void*>(k.f16) : reinterpret_cast<const void*>(k.f32);
+    // above the 64 KB a kernel gets unasked (all but the tile kernel), the function's attribute is set once per engine: the call costs a microsecond
+    if (p.lds > 64 * 1024 && !h->eval_attr_set[p.kernel].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+        if (e != hipSuccess) return e;
+        h->eval_attr_set[p.kernel].store(true, std::memory_order_release);
     }
-    if (h->net_kind == 1 && h->net_arith == SYN_NET_ARITH_F16X2) {
-        // Connect4ConvNet in the f16x2 arithmetic (conv_f16x2_tile.cuh): the throughput kernel at every size, two waves per SIMD
-        auto k = policy_eval_conv_f16x2_kernel<512>;
-        if (!h->eval_attr_set[5].load(std::memory_order_acquire)) {
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(ConvF16Geom::IMG_WORDS * 4))) != hipSuccess)
-                return e;
-            h->eval_attr_set[5].store(true, std::memory_order_release);
-        }
-        int grid = (ntiles + 512 / 64 - 1) / (512 / 64);
-        if (grid > h->num_cus) grid = h->num_cus;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), (size_t)ConvF16Geom::IMG_WORDS * 4, st, h->d_wimg16,
-                           reinterpret_cast<const unsigned long long*>(d_my), reinterpret_cast<const unsigned long long*>(d_op), n,
-                           d_logits, d_value);
-    } else
-    if (h->net_kind == 0 && h->net_arith == SYN_NET_ARITH_F16X2) {
-        // Connect4Net in the f16x2 arithmetic: the throughput kernel at every size (its tile is 3x shorter than the f32 one's)
-#define SYN_LAUNCH_EVAL16(NT, SLOT)                                                                                            \
-    {                                                                                                                          \
-        auto k = policy_eval_f16x2_kernel<NT>;                                                                                 \
-        if (!h->eval_attr_set[SLOT].load(std::memory_order_acquire)) {                                                         \
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,         \
-                                         (int)(F16Geom::IMG_WORDS * 4))) != hipSuccess)                                        \
-                return e;                                                                                                      \
-            h->eval_attr_set[SLOT].store(true, std::memory_order_release);                                                     \
-        }                                                                                                                      \
-        int grid = (ntiles + NT / 64 - 1) / (NT / 64);                                                                         \
-        if (grid > h->num_cus) grid = h->num_cus;                                                                              \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(NT), (size_t)F16Geom::IMG_WORDS * 4, st, h->d_wimg16,                           \
-                           reinterpret_cast<const unsigned long long*>(d_my), reinterpret_cast<const unsigned long long*>(d_op), n, \
-                           d_logits, d_value);                                                                                 \
-    }
-        if (ntiles >= h->num_cus * 16 * 4) SYN_LAUNCH_EVAL16(1024, 3) else SYN_LAUNCH_EVAL16(512, 4)
-#undef SYN_LAUNCH_EVAL16
-    } else
-    if (h->net_kind == 0 && (size_t)n <= EVAL_TILE_MAX) {
-        // at most a tile per CU: the latency kernel (eval_small.cuh), one workgroup per tile, no weight staging
-        hipLaunchKernelGGL(policy_eval_tile_kernel, dim3((unsigned)ntiles), dim3(256), EVAL_TILE_LDS, st, h->d_wimg,
-                           reinterpret_cast<const unsigned long long*>(d_my), reinterpret_cast<const unsigned long long*>(d_op), n, d_logits,
-                           d_value, nullptr, nullptr, 0u);
-    } else if (h->net_kind == 1) {
-        // (16 waves per CU measured the same 46 % of the MFMA peak as 8: the tile is issue-bound, not latency-bound)
-        SYN_LAUNCH_EVAL(policy_eval_conv_kernel, 512, (size_t)ConvGeom::IMG_FLOATS * 4, 0)
-    } else if (ntiles >= h->num_cus * 12 * 4) {
-        SYN_LAUNCH_EVAL(policy_eval_kernel, 768, (size_t)MlpGeom::IMG_FLOATS * 4, 1)
-    } else {
-        SYN_LAUNCH_EVAL(policy_eval_kernel, 512, (size_t)MlpGeom::IMG_FLOATS * 4, 2)
-    }
-#undef SYN_LAUNCH_EVAL
+    const unsigned long long* my = reinterpret_cast<const unsigned long long*>(d_my);
+    const unsigned long long* op = reinterpret_cast<const unsigned long long*>(d_op);
+    const dim3 grid((unsigned)p.grid), threads((unsigned)p.threads);
+    if (k.tile) hipLaunchKernelGGL(k.tile, grid, threads, p.lds, st, h->net.d_wimg, my, op, n, d_logits, d_value, done.done_blocks, done.host_flag, done.seq);
+    else if (p.f16_image) hipLaunchKernelGGL(k.f16, grid, threads, p.lds, st, h->net.d_wimg16, my, op, n, d_logits, d_value);
+    else hipLaunchKernelGGL(k.f32, grid, threads, p.lds, st, h->net.d_wimg, my, op, n, d_logits, d_value);
     return hipGetLastError();
 }
 
@@ -882,12 +905,12 @@ int syn_policy_eval_batch_device(syn_engine* h, const uint64_t* d_my, const uint
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (n < 0 || (n > 0 && (!d_my || !d_op || !d_logits || !d_value)))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_policy_eval_batch_device");
-    if (!h->has_weights) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_load_weights first");
+    { const int rc = require_weights(h); if (rc != SYN_OK) return rc; }
     if (n == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     { const int rc16 = require_f16x2_image(h); if (rc16 != SYN_OK) return rc16; }
-    HIP_TRY(h, launch_policy_eval(h, h->stream, d_my, d_op, n, d_logits, d_value));
+    HIP_TRY(h, launch_eval(h, plan_eval(eval_query(h, n)), h->stream, d_my, d_op, n, d_logits, d_value));
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->last_launches = 1;
     if (sync) {
@@ -983,9 +1006,8 @@ int syn_eval_ctx_submit(syn_eval_ctx* c, const uint64_t* my_bb, const uint64_t* 
     if (n < 0 || (n > 0 && (!my_bb || !op_bb))) return ctx_fail(c, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_eval_ctx_submit");
     if (c->pending != 0) return ctx_fail(c, SYN_ERR_INVALID_ARGUMENT, "syn_eval_ctx_submit: the previous batch has not been waited for");
     syn_engine* h = c->h;
-    if (!h->has_weights) return ctx_fail(c, SYN_ERR_NO_WEIGHTS, "call syn_load_weights first");
-    if (h->net_arith == SYN_NET_ARITH_F16X2 && (!h->img16_current || !h->d_wimg16))
-        return ctx_fail(c, SYN_ERR_UNSUPPORTED, "the engine is in the f16x2 arithmetic but holds no f16x2 image of its parameters");
+    if (!h->net.has_weights) return ctx_fail(c, SYN_ERR_NO_WEIGHTS, MSG_NO_WEIGHTS);
+    if (lacks_f16x2_image(h)) return ctx_fail(c, SYN_ERR_UNSUPPORTED, MSG_NO_F16X2_IMAGE);
     if (n == 0) return SYN_OK;
     CTX_TRY(c, hipSetDevice(h->device));
     const size_t nb = (size_t)n;
@@ -1005,23 +1027,18 @@ int syn_eval_ctx_submit(syn_eval_ctx* c, const uint64_t* my_bb, const uint64_t* 
     float* s_logits = reinterpret_cast<float*>(s_op + nb);
     std::memcpy(s_my, my_bb, nb * 8);
     std::memcpy(s_op, op_bb, nb * 8);
-    // the positions are read across the host link in place (16 B each); small results are written in place, larger ones come back
-    // with one DMA (syn_policy_eval_batch, measured)
-    c->out_in_place = nb <= h->eval_zero_copy_out;
+    EvalQuery q = eval_query(h, n);
+    q.poll_max = h->eval_poll_max;
+    q.zero_copy_out = h->eval_zero_copy_out;
+    q.poll_broken = c->poll_broken;
+    const EvalPlan plan = plan_eval(q);
+    c->out_in_place = plan.in_place;
+    c->polled = plan.polled;
     float* o_logits = c->out_in_place ? s_logits : static_cast<float*>(c->d_out);
-    c->polled = c->out_in_place && h->net_kind == 0 && h->net_arith == SYN_NET_ARITH_F32 && nb <= h->eval_poll_max && !c->poll_broken;
-    if (c->polled) {
-        // the latency kernels: their last workgroup stores this call's number into pinned memory, syn_eval_ctx_wait polls it
-        c->seq += 1u;
-        const unsigned long long* k_my = reinterpret_cast<const unsigned long long*>(s_my);
-        const unsigned long long* k_op = reinterpret_cast<const unsigned long long*>(s_op);
-        hipLaunchKernelGGL(policy_eval_tile_kernel, dim3((unsigned)((n + 15) / 16)), dim3(256), EVAL_TILE_LDS, c->stream, h->d_wimg, k_my, k_op,
-                           n, o_logits, o_logits + nb * 9, c->d_done, c->h_flag, c->seq);
-        CTX_TRY(c, hipGetLastError());
-    } else {
-        CTX_TRY(c, launch_policy_eval(h, c->stream, s_my, s_op, n, o_logits, o_logits + nb * 9));
-        if (!c->out_in_place) CTX_TRY(c, hipMemcpyAsync(s_logits, c->d_out, nb * 48, hipMemcpyDeviceToHost, c->stream));
-    }
+    EvalCompletion done;
+    if (c->polled) done = EvalCompletion{c->d_done, c->h_flag, c->seq += 1u};   // syn_eval_ctx_wait polls h_flag for this call's number
+    CTX_TRY(c, launch_eval(h, plan, c->stream, s_my, s_op, n, o_logits, o_logits + nb * 9, done));
+    if (!c->out_in_place) CTX_TRY(c, hipMemcpyAsync(s_logits, c->d_out, nb * 48, hipMemcpyDeviceToHost, c->stream));
     c->pending = n;
     return SYN_OK;
 }
@@ -1082,7 +1099,7 @@ int syn_policy_eval_batch(syn_engine* h, const uint64_t* my_bb, const uint64_t* 
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (n < 0 || (n > 0 && (!my_bb || !op_bb || !logits || !value)))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_policy_eval_batch");
-    if (!h->has_weights) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_load_weights first");
+    { const int rc = require_weights(h); if (rc != SYN_OK) return rc; }
     if (n == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nb = (size_t)n;
@@ -1268,13 +1285,16 @@ static bool valid_root(uint64_t my, uint64_t op) {
 }
 
 static int common_params(syn_engine* h, EngineParams& P, int explores, bool need_weights = true) {
-    if (need_weights && !h->has_weights) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_load_weights first");
-    if (need_weights && h->net_arith == SYN_NET_ARITH_F16X2) { int rc16 = ensure_f16x2_image(h); if (rc16 != SYN_OK) return rc16; }
+    if (need_weights) {
+        int rc = require_weights(h);
+        if (rc == SYN_OK) rc = require_f16x2_image(h);
+        if (rc != SYN_OK) return rc;
+    }
     if (explores < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "explores must be >= 0");
     if (explores > h->max_explores)
         return fail(h, SYN_ERR_CAPACITY, "explores %d exceeds the engine's max_explores %d", explores, h->max_explores);
     std::memset(&P, 0, sizeof(P));
-    P.wimg = h->net_arith == SYN_NET_ARITH_F16X2 ? reinterpret_cast<const float*>(h->d_wimg16) : h->d_wimg;
+    P.wimg = h->net.image();
     P.stat = h->d_stat;
     P.edge = h->d_edge;
     P.cap = h->cap;
@@ -1289,13 +1309,11 @@ static int common_params(syn_engine* h, EngineParams& P, int explores, bool need
     return SYN_OK;
 }
 
-// Fpu::Func, PolicyNoise::Dirichlet and Connect4ConvNet exist in the lane-per-tree kernels only, whose block ids are 14 bits: an
-// engine created for more than 7,280 explores cannot run them. Said before anything is enqueued.
+// a search or self-play call whose configuration or network lives in the lane-per-tree kernels only (require_lane_cap)
 static int check_lane_only(syn_engine* h, const DevMctsCfg& m) {
-    if ((m.fpu == 2 || m.noise == 2 || h->net_kind == 1) && h->cap > LANE_MAX_CAP)
-        return fail(h, SYN_ERR_UNSUPPORTED, "Fpu::Func / PolicyNoise::Dirichlet / Connect4ConvNet run in the lane-per-tree kernels only: "
-                    "max_explores must be <= %u for them (this engine: %d)", (LANE_MAX_CAP - 1u) / 9u - 1u, h->max_explores);
-    return SYN_OK;
+    if (m.fpu == 2) return require_lane_cap(h, "Fpu::Func");
+    if (m.noise == 2) return require_lane_cap(h, "PolicyNoise::Dirichlet");
+    return require_lane_cap_of_network(h, h->net.kind);
 }
 
 static int mcts_search_impl(syn_engine* h, const syn_mcts_config* cfg, const uint64_t* my_bb, const uint64_t* op_bb, int n,
@@ -1746,8 +1764,6 @@ static const LearnerKnobs& learner_knobs() {
 // test hook, read at every syn_train_epoch call: the persistent kernel's result is thrown away and the recovery path taken
 static bool epoch_force_abort() { return debug_env("SYN_TRAIN_FORCE_ABORT") != nullptr; }
 
-static size_t learner_param_bytes(int kind) { return (size_t)(kind == 1 ? ConvGeom::NUM_PARAMS : TrainGeom::NUM_PARAMS) * 4; }
-
 // All of the learner's device buffers or none: a failed allocation frees what was taken, so that a retry starts from scratch instead
 // of skipping the allocation block.
 static int alloc_trainer_buffers(syn_engine* h) {
@@ -1784,7 +1800,7 @@ static int learner_load_state(syn_engine* h, const LearnerStart& s) {
         HIP_TRY(h, hipMemcpyAsync(L.d_twimg, s.img->data(), s.img->size() * 4, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(h, hipMemcpyAsync(L.d_ttimg, s.timg->data(), s.timg->size() * 4, hipMemcpyHostToDevice, h->stream));
     }
-    HIP_TRY(h, hipMemcpyAsync(L.d_tw, s.blob, learner_param_bytes(s.kind), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(L.d_tw, s.blob, g_net_desc[s.kind].param_bytes(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemsetAsync(L.d_tm, 0, cap_bytes, h->stream));
     HIP_TRY(h, hipMemsetAsync(L.d_tv, 0, cap_bytes, h->stream));
     HIP_TRY(h, hipMemsetAsync(L.d_tgrad, 0, cap_bytes, h->stream));
@@ -1831,7 +1847,7 @@ static SelfCheckBatch self_check_batch() {
 static bool learner_self_check(syn_engine* h, const LearnerStart& start, bool* same_bits) {
     auto& L = h->learner;
     const SelfCheckBatch b = self_check_batch();
-    const size_t nw = learner_param_bytes(start.kind) / 4;
+    const size_t nw = (size_t)g_net_desc[start.kind].num_params;
     std::vector<float> w[2] = {std::vector<float>(nw), std::vector<float>(nw)};
     bool ok = true;
     for (int mode = 0; mode < 2 && ok; mode++) {
@@ -2189,7 +2205,7 @@ struct SnapshotLayout {
     int parts;
 };
 static SnapshotLayout snapshot_layout(const syn_engine::Learner& L) {
-    const size_t pb = learner_param_bytes(L.trainer_kind);
+    const size_t pb = g_net_desc[L.trainer_kind].param_bytes();
     return {{L.d_tw, L.d_tm, L.d_tv, L.d_twimg, L.d_ttimg},
             {pb, pb, pb, (size_t)MlpGeom::IMG_FLOATS * 4, (size_t)TrainImg::T_FLOATS * 4},
             L.trainer_kind == 1 ? 3 : 5};
@@ -2399,7 +2415,7 @@ int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long l
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     auto& L = h->learner;
-    const size_t bytes = learner_param_bytes(L.trainer_kind);
+    const size_t bytes = g_net_desc[L.trainer_kind].param_bytes();
     if (blob) HIP_TRY(h, hipMemcpyAsync(blob, L.d_tw, bytes, hipMemcpyDeviceToHost, h->stream));
     if (m) HIP_TRY(h, hipMemcpyAsync(m, L.d_tm, bytes, hipMemcpyDeviceToHost, h->stream));
     if (v) HIP_TRY(h, hipMemcpyAsync(v, L.d_tv, bytes, hipMemcpyDeviceToHost, h->stream));
@@ -2414,28 +2430,8 @@ int syn_trainer_publish_weights(syn_engine* h) {
     const int rc = learner_check(h);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
-    auto& L = h->learner;
-    if (L.trainer_kind == 1) {
-        // Connect4ConvNet: the fragment image of convnet.cuh is rebuilt from the canonical parameters on the device
-        if (h->cap > LANE_MAX_CAP) return fail(h, SYN_ERR_UNSUPPORTED, "Connect4ConvNet runs in the lane-per-tree kernels only");
-        hipLaunchKernelGGL(conv_image_kernel, dim3((ConvGeom::IMG_FLOATS + 255) / 256), dim3(256), 0, h->stream, L.d_tw, h->d_wimg);
-        HIP_TRY(h, hipGetLastError());
-    } else {
-        // Connect4Net: the trainer keeps its weights in the inference fragment order as well (train_mfma.cuh): publishing is one device copy
-        HIP_TRY(h, hipMemcpyAsync(h->d_wimg, L.d_twimg, (size_t)MlpGeom::IMG_FLOATS * 4, hipMemcpyDeviceToDevice, h->stream));
-    }
-    if (h->d_cache) HIP_TRY(h, hipMemsetAsync(h->d_cache, 0, (size_t)64 << h->cache_log2, h->stream));  // new network: empty PolicyWithCache
-    // the f16x2 image is built on the host from the canonical parameters (f16x2_tile.cuh / conv_f16x2_tile.cuh): keep a copy of what
-    // was published; an engine in the f16x2 arithmetic stays in it
-    const size_t bytes = learner_param_bytes(L.trainer_kind);
-    h->host_blob.resize(bytes / 4);
-    HIP_TRY(h, hipMemcpyAsync(h->host_blob.data(), L.d_tw, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->has_weights = true;
-    h->net_kind = L.trainer_kind;
-    h->img16_current = false;
-    if (h->net_arith == SYN_NET_ARITH_F16X2) return ensure_f16x2_image(h);
-    return SYN_OK;
+    const int cap_rc = require_lane_cap_of_network(h, h->learner.trainer_kind);
+    return cap_rc != SYN_OK ? cap_rc : install_network(h, h->learner.trainer_kind, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ deduplicate

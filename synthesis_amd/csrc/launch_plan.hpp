@@ -1,7 +1,7 @@
 // synthesis_amd — which kernel plays a self-play / search call, and on what launch shape: the decision alone, as a pure function of
 // plain numbers. Host-only C++17 without a HIP header, so the selection is read and tested on a CPU (tests/test_launch_plan.py).
 // engine.hip builds the query, grows the buffers the plan asks for, looks the plan's kernel up in the table of shipped
-// instantiations (lane_instances.h) and launches it.
+// instantiations (lane_instances.h) and launches it. plan_eval, at the end, is the same for a policy-evaluation call.
 #pragma once
 #include <climits>
 #include <cstddef>
@@ -301,6 +301,86 @@ inline LaunchPlan plan_rollout_search(int slots, int jobs, unsigned cap) {
     p.lane_thresh = 64;
     p.no_cache = true;
     p.path_entries = (size_t)lgrid * nw * PLAN_PATH_ENTRIES;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ policy evaluation
+// Which kernel evaluates a batch of n positions (syn_policy_eval_batch*, the evaluation contexts), by network, arithmetic and size.
+// engine.hip keeps the table from EvalKernel to the function (g_eval_kernels) and the one launch (launch_eval).
+enum EvalKernel {
+    EVAL_TILE = 0,        // policy_eval_tile_kernel (eval_small.cuh): the latency kernel, one workgroup per 16-position tile, no weight staging
+    EVAL_MLP_512,         // policy_eval_kernel<512> / <768> (engine_kernels.cuh): Connect4Net, the f32 image staged in LDS
+    EVAL_MLP_768,
+    EVAL_CONV_512,        // policy_eval_conv_kernel<512> (convnet.cuh)
+    EVAL_F16_512,         // policy_eval_f16x2_kernel<512> / <1024> (engine_kernels.cuh): Connect4Net, the f16x2 image
+    EVAL_F16_1024,
+    EVAL_CONV_F16_512,    // policy_eval_conv_f16x2_kernel<512> (conv_f16x2_tile.cuh)
+    EVAL_KERNELS
+};
+// dynamic LDS of each: the tile kernel's two activation-exchange buffers, else the network's image (engine.hip static_asserts them)
+constexpr size_t PLAN_EVAL_TILE_LDS = 14 * 64 * 16;
+constexpr size_t PLAN_MLP_IMG_BYTES = 30816 * 4;        // mlp.cuh MlpGeom::IMG_FLOATS
+constexpr size_t PLAN_CONV_IMG_BYTES = 16480 * 4;       // convnet.cuh ConvGeom::IMG_FLOATS
+constexpr size_t PLAN_F16_IMG_BYTES = 31080 * 4;        // f16x2_tile.cuh F16Geom::IMG_WORDS
+constexpr size_t PLAN_CONV_F16_IMG_BYTES = 16932 * 4;   // conv_f16x2_tile.cuh ConvF16Geom::IMG_WORDS
+constexpr size_t PLAN_EVAL_TILE_MAX = 4096;             // the tile kernel is chosen up to this many positions (256 tiles: one per CU of an MI355X)
+
+struct EvalQuery {
+    int net_kind = 0;     // 0 Connect4Net, 1 Connect4ConvNet
+    bool f16 = false;     // the engine is in the f16x2 arithmetic
+    int n = 0;            // positions, >= 1
+    int num_cus = 256;
+    // an evaluation context's call (the engine's own launches leave the defaults: nothing in place, nothing polled)
+    size_t poll_max = 0;        // batches up to this size signal completion through pinned memory
+    size_t zero_copy_out = 0;   // results of up to this many positions are written into the pinned buffer by the kernel itself
+    bool poll_broken = false;   // a completion word went missing once on this context
+};
+
+struct EvalPlan {
+    int kernel = EVAL_TILE;   // EvalKernel
+    int threads = 0, grid = 0;
+    size_t lds = 0;
+    bool f16_image = false;   // the kernel reads the f16x2 image (else the f32 one)
+    bool in_place = false;    // results are written across the host link into the caller's pinned buffer
+    bool polled = false;      // the kernel's last workgroup reports completion through pinned memory (tile kernel only)
+};
+
+inline EvalPlan plan_eval(const EvalQuery& q) {
+    EvalPlan p;
+    const int ntiles = (q.n + 15) / 16;
+    const size_t nb = (size_t)q.n;
+    // the positions are read across the host link in place (16 B each); small results are written in place, larger ones come back
+    // with one DMA (syn_policy_eval_batch, measured)
+    p.in_place = nb <= q.zero_copy_out;
+    // the latency kernel: its last workgroup stores the call's number into pinned memory, syn_eval_ctx_wait polls it.
+    // (A polled call uses it whatever its size: SYN_EVAL_POLL_MAX raised past PLAN_EVAL_TILE_MAX is not capped.)
+    p.polled = p.in_place && q.net_kind == 0 && !q.f16 && nb <= q.poll_max && !q.poll_broken;
+    if (p.polled || (q.net_kind == 0 && !q.f16 && nb <= PLAN_EVAL_TILE_MAX)) {
+        // at most a tile per CU: the latency kernel (eval_small.cuh), one workgroup per tile, no weight staging
+        p.kernel = EVAL_TILE; p.threads = 256; p.grid = ntiles; p.lds = PLAN_EVAL_TILE_LDS;
+        return p;
+    }
+    // The throughput kernels: a workgroup stages the image once and its waves take tiles in turn, at most one workgroup per CU.
+    // Two waves per SIMD (512 threads): one wave's LDS reads / feature math overlap the other's MFMAs. Large batches (every
+    // wave gets several tiles) run three waves per SIMD, which also hides the loads and stores around the tiles.
+    p.f16_image = q.f16;
+    if (q.net_kind == 1 && q.f16) {
+        // Connect4ConvNet in the f16x2 arithmetic (conv_f16x2_tile.cuh): the throughput kernel at every size, two waves per SIMD
+        p.kernel = EVAL_CONV_F16_512; p.threads = 512; p.lds = PLAN_CONV_F16_IMG_BYTES;
+    } else if (q.f16) {
+        // Connect4Net in the f16x2 arithmetic: the throughput kernel at every size (its tile is 3x shorter than the f32 one's)
+        const bool large = ntiles >= q.num_cus * 16 * 4;
+        p.kernel = large ? EVAL_F16_1024 : EVAL_F16_512; p.threads = large ? 1024 : 512; p.lds = PLAN_F16_IMG_BYTES;
+    } else if (q.net_kind == 1) {
+        // (16 waves per CU measured the same 46 % of the MFMA peak as 8: the tile is issue-bound, not latency-bound)
+        p.kernel = EVAL_CONV_512; p.threads = 512; p.lds = PLAN_CONV_IMG_BYTES;
+    } else {
+        const bool large = ntiles >= q.num_cus * 12 * 4;
+        p.kernel = large ? EVAL_MLP_768 : EVAL_MLP_512; p.threads = large ? 768 : 512; p.lds = PLAN_MLP_IMG_BYTES;
+    }
+    const int waves = p.threads / 64;
+    p.grid = (ntiles + waves - 1) / waves;
+    if (p.grid > q.num_cus) p.grid = q.num_cus;
     return p;
 }
 

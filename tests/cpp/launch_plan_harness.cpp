@@ -3,6 +3,8 @@
 //   knobs          SYN_LANES SYN_FREE SYN_QUADS SYN_LANE_THRESH SYN_SCAN_MIN SYN_ABLATE SYN_PC SYN_PC_PRIO SYN_PC_STUB SYN_LANES2 SYN_L2_TILE
 //                  SYN_POOL SYN_POOL_NW SYN_POOL_FIRE SYN_POOL_SCAN
 //   rollout=1      the RolloutPolicy search's plan for (slots, jobs, cap)
+//   eval=1         the policy-evaluation plan (plan_eval) for (net, f16, n, cus, poll_max, zc_out, poll_broken); its output line is
+//                  kernel threads grid lds f16_image in_place polled
 // Output per line: error shape grid threads fast n policy tile prof slots lane_thresh nv path_entries listed
 // listed: 1 = the plan's kernel is in lane_instances.h's lists (or is one of the kernels engine.hip instantiates itself for every call:
 // row-per-tree, quads, producer/consumer), 2 = only its unprofiled twin is, 0 = neither.
@@ -46,7 +48,8 @@ int main() {
     while (std::fgets(line, sizeof line, stdin)) {
         syn::LaunchQuery q;
         syn::LaunchKnobs k;
-        int rollout = 0;
+        int rollout = 0, eval = 0;
+        syn::EvalQuery ev;
         std::istringstream in(line);
         std::string tok;
         while (in >> tok) {
@@ -57,6 +60,7 @@ int main() {
             const struct { const char* name; int* p; } ints[] = {
                 {"cus", &q.num_cus}, {"slots", &q.slots}, {"jobs", &q.jobs}, {"net", &q.net_kind}, {"pool_trees", &q.pool_trees}, {"mode", &q.mode},
                 {"fpu", &q.fpu}, {"noise", &q.noise}, {"fam", &q.family}, {"rollout", &rollout},
+                {"eval", &eval}, {"n", &ev.n},
                 {"SYN_LANES", &k.lanes}, {"SYN_FREE", &k.free_run}, {"SYN_QUADS", &k.quads}, {"SYN_LANE_THRESH", &k.lane_thresh},
                 {"SYN_SCAN_MIN", &k.scan_min}, {"SYN_ABLATE", &k.ablate}, {"SYN_PC", &k.pc}, {"SYN_PC_PRIO", &k.pc_prio}, {"SYN_PC_STUB", &k.pc_stub},
                 {"SYN_LANES2", &k.lanes2}, {"SYN_L2_TILE", &k.l2_tile}, {"SYN_POOL", &k.pool}, {"SYN_POOL_NW", &k.pool_nw},
@@ -68,7 +72,16 @@ int main() {
             if (key == "f16") { q.f16 = v != 0; found = true; }
             if (key == "count") { q.count = v != 0; found = true; }
             if (key == "prof") { q.prof = v != 0; found = true; }
+            if (key == "poll_max") { ev.poll_max = (size_t)v; found = true; }
+            if (key == "zc_out") { ev.zero_copy_out = (size_t)v; found = true; }
+            if (key == "poll_broken") { ev.poll_broken = v != 0; found = true; }
             if (!found) { std::fprintf(stderr, "unknown key %s\n", key.c_str()); return 2; }
+        }
+        if (eval) {
+            ev.net_kind = q.net_kind; ev.f16 = q.f16; ev.num_cus = q.num_cus;
+            const syn::EvalPlan e = syn::plan_eval(ev);
+            std::printf("%d %d %d %zu %d %d %d\n", e.kernel, e.threads, e.grid, e.lds, (int)e.f16_image, (int)e.in_place, (int)e.polled);
+            continue;
         }
         const syn::LaunchPlan p = rollout ? syn::plan_rollout_search(q.slots, q.jobs, q.cap) : syn::plan_launch(q, k);
         int listed = 0;

@@ -1,7 +1,9 @@
 """The launch selection (synthesis_amd/csrc/launch_plan.hpp: plan_launch) on a CPU: tests/cpp/launch_plan_harness.cpp, built with g++,
 prints the plan for queries on stdin. The expected rows were derived by reading the launch code this selector replaced (the thresholds at
 256 / 512 / 768 trees per CU, the 8-wave cap of the runtime-switched family, the 12-wave cap of the folded ones, the conv f16x2 caps),
-and every plan of a sweep must name a kernel instantiation that lane_instances.h lists."""
+and every plan of a sweep must name a kernel instantiation that lane_instances.h lists. The policy-evaluation selection (plan_eval) is
+held the same way: rows read off the launch code it replaced (the tile kernel up to 4,096 positions, three waves per SIMD from 48 tiles
+per CU, the f16x2 kernel's four from 64), the evaluation contexts' in-place and polling rules, and a sweep over the sizes."""
 import itertools
 import os
 import subprocess
@@ -29,6 +31,7 @@ def harness(tmp_path_factory):
         assert len(out) == len(queries)
         return [Plan(*map(int, l.split())) for l in out]
 
+    plans.exe = exes["default"]
     return plans
 
 
@@ -169,3 +172,80 @@ def test_debug_shape_plans_name_shipped_instantiations(harness):
     assert (p.shape, p.grid, p.threads) == (6, 256, 512)
     # the same knobs mean nothing to the default library
     assert harness([query("mlp f32", 1, 262144, SYN_POOL=96, SYN_LANES2=8, SYN_PC=2)])[0].shape == 4
+
+
+# ---- plan_eval: which kernel evaluates a batch of n positions
+EvalPlan = namedtuple("EvalPlan", "kernel threads grid lds f16_image in_place polled")
+TILE, MLP_512, MLP_768, CONV_512, F16_512, F16_1024, CONV_F16_512 = range(7)
+LDS = {TILE: 14 * 64 * 16, MLP_512: 30816 * 4, MLP_768: 30816 * 4, CONV_512: 16480 * 4, F16_512: 31080 * 4, F16_1024: 31080 * 4,
+       CONV_F16_512: 16932 * 4}
+
+
+def eval_plans(harness, queries):
+    text = "".join(" ".join(f"{k}={int(v)}" for k, v in dict(q, eval=1).items()) + "\n" for q in queries)
+    out = subprocess.run([harness.exe], input=text, capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(queries)
+    return [EvalPlan(*map(int, l.split())) for l in out]
+
+
+# (net / arithmetic, CUs, n, kernel, threads, grid)
+EVAL_ROWS = [
+    ("mlp f32", 256, 1, TILE, 256, 1),
+    ("mlp f32", 256, 16, TILE, 256, 1),
+    ("mlp f32", 256, 17, TILE, 256, 2),
+    ("mlp f32", 256, 4096, TILE, 256, 256),
+    ("mlp f32", 256, 4097, MLP_512, 512, 33),          # 257 tiles over 8 waves
+    ("mlp f32", 256, 196592, MLP_512, 512, 256),       # 12,287 tiles: one short of 48 per CU
+    ("mlp f32", 256, 196593, MLP_768, 768, 256),
+    ("conv f32", 256, 1, CONV_512, 512, 1),
+    ("conv f32", 256, 1000000, CONV_512, 512, 256),
+    ("mlp f16x2", 256, 1, F16_512, 512, 1),
+    ("mlp f16x2", 256, 4096, F16_512, 512, 32),
+    ("mlp f16x2", 256, 262128, F16_512, 512, 256),     # 16,383 tiles: one short of 64 per CU
+    ("mlp f16x2", 256, 262129, F16_1024, 1024, 256),
+    ("conv f16x2", 256, 1, CONV_F16_512, 512, 1),
+    ("conv f16x2", 256, 1000000, CONV_F16_512, 512, 256),
+    # the two wave-count thresholds scale with the CU count; the tile kernel's 4,096 positions do not
+    ("mlp f32", 8, 4096, TILE, 256, 256),
+    ("mlp f32", 8, 6128, MLP_512, 512, 8),
+    ("mlp f32", 8, 6129, MLP_768, 768, 8),
+    ("mlp f16x2", 8, 8176, F16_512, 512, 8),
+    ("mlp f16x2", 8, 8177, F16_1024, 1024, 8),
+]
+
+
+def test_eval_plan_rows(harness):
+    got = eval_plans(harness, [dict(NETS[net], cus=cus, n=n) for net, cus, n, _, _, _ in EVAL_ROWS])
+    for (net, cus, n, kernel, threads, grid), p in zip(EVAL_ROWS, got):
+        what = f"{net}, {cus} CUs, n {n}: {p}"
+        assert (p.kernel, p.threads, p.grid) == (kernel, threads, grid), what
+        assert p.lds == LDS[kernel] and p.f16_image == NETS[net]["f16"], what
+        assert not p.in_place and not p.polled, what   # the engine's own launches: neither
+
+    # the evaluation contexts' flags
+    queries = [dict(net, n=n, poll_max=pm, zc_out=zc, poll_broken=br)
+               for net in NETS.values() for n in (1, 17, 1024, 1025, 4096, 4097, 5000, 8192, 8193)
+               for pm, zc in ((1024, 4096), (0, 4096), (1024, 0), (8192, 8192), (8192, 1024)) for br in (0, 1)]
+    for q, p in zip(queries, eval_plans(harness, queries)):
+        assert p.in_place == (q["n"] <= q["zc_out"]), (q, p)
+        assert p.polled == (p.in_place and q["net"] == 0 and not q["f16"] and q["n"] <= q["poll_max"] and not q["poll_broken"]), (q, p)
+        if p.polled:
+            assert (p.kernel, p.threads, p.grid, p.lds) == (TILE, 256, (q["n"] + 15) // 16, LDS[TILE]), (q, p)
+        else:   # the flags change nothing else
+            assert p[:5] == eval_plans(harness, [dict(net=q["net"], f16=q["f16"], n=q["n"])])[0][:5], (q, p)
+    # a polled call takes the tile kernel even past its 4,096 positions
+    p, = eval_plans(harness, [dict(NETS["mlp f32"], n=5000, poll_max=8192, zc_out=8192)])
+    assert p.polled and p.in_place and (p.kernel, p.grid) == (TILE, 313)
+    p, = eval_plans(harness, [dict(NETS["mlp f32"], n=5000, poll_max=1024, zc_out=8192)])
+    assert not p.polled and p.in_place and (p.kernel, p.grid) == (MLP_512, 40)
+
+    # every size: the grid covers the tiles or fills the device, and the LDS fits a CU
+    for cus, edges in ((256, (4096, 196592, 262128)), (8, (4096, 6128, 8176))):
+        ns = sorted(set(range(1, 300001, 997)) | {n for e in edges for n in range(e - 40, e + 41)})
+        for net in NETS.values():
+            kernels = {(0, 0): (TILE, MLP_512, MLP_768), (0, 1): (F16_512, F16_1024), (1, 0): (CONV_512,), (1, 1): (CONV_F16_512,)}[net["net"], net["f16"]]
+            for n, p in zip(ns, eval_plans(harness, [dict(net, cus=cus, n=n) for n in ns])):
+                tiles, waves = (n + 15) // 16, p.threads // 64
+                assert p.kernel in kernels and p.lds == LDS[p.kernel] <= 160 * 1024 and p.threads % 64 == 0, (net, cus, n, p)
+                assert p.grid >= 1 and (p.grid * waves >= min(tiles, cus * waves) or p.grid == cus), (net, cus, n, p)
+                assert p.kernel != TILE or p.grid == tiles, (net, cus, n, p)
