@@ -50,6 +50,10 @@ def main():
     ap.add_argument("--explores", type=int, default=200)            # main.rs:30: 1600
     ap.add_argument("--epochs", type=int, default=2)                # main.rs:21: 20
     ap.add_argument("--batch-size", type=int, default=32)           # main.rs:22
+    ap.add_argument("--batch-mode", default="chained", choices=["chained", "micro"], help="chained = the reference's step: one chain over the "
+                    "minibatch, one workgroup however large --batch-size is; micro = the batch as micro-batches of 32 spread over the GPU, their "
+                    "gradients averaged in a fixed order (syn_trainer_set_batch_mode; --batch-size, per rank under --data-parallel, must be a "
+                    "multiple of 32). No learning rate is rescaled; the strength of networks trained at large batches is not measured")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--concurrent", type=int, default=65536)
     ap.add_argument("--eval-games", type=int, default=0, help="after every iteration: this many games as each colour against "
@@ -96,6 +100,8 @@ def main():
     if args.data_parallel and args.batch_size % world != 0:
         raise SystemExit(f"--batch-size {args.batch_size} must be a multiple of the world size {world}: every global batch is "
                          f"split evenly over the ranks so that the effective batch stays the reference's")
+    if args.batch_mode == "micro" and (args.batch_size // (world if args.data_parallel else 1)) % 32 != 0:
+        raise SystemExit(f"--batch-mode micro takes batches that are a multiple of 32 positions on every rank (got --batch-size {args.batch_size})")
     lr_schedule = [(1, 1e-3), (20, 5e-4), (40, 1e-4), (60, 5e-5), (80, 1e-5)]  # main.rs:18
     cfg = sa.parity_rollout_config(args.explores)
     if args.reference_fpu:
@@ -110,7 +116,7 @@ def main():
     if args.data_parallel:
         (eng.load_weights_conv if conv else eng.load_weights)(blob)
         learner = DataParallelLearner(eng, blob, dist=dist, device=local_rank, net=args.net, network_arithmetic=args.network_arithmetic,
-                                      **hyper)
+                                      batch_mode=args.batch_mode, **hyper)
         if args.precision != "f32":
             eng.trainer_set_precision(args.precision)
         # replay buffer: positions as bitboards + targets + the game each step came from
@@ -120,7 +126,8 @@ def main():
     else:
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
-                            network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry, **hyper)
+                            network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
+                            batch_mode=args.batch_mode, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -398,6 +398,30 @@ int syn_train_apply_enqueue(syn_engine* h, void* stream, const float* d_grads, f
  * libtorch f32, alpha_zero.rs:28-37). */
 enum { SYN_TRAIN_F32 = 0, SYN_TRAIN_BF16 = 1 };
 int syn_trainer_set_precision(syn_engine* h, int precision);
+/* How a minibatch above the reference's batch_size of 32 is evaluated (LearningConfig::batch_size is a free parameter: config.rs:86;
+ * the minibatch loop: alpha_zero.rs:72-94). SYN_TRAIN_BATCH_CHAINED (default after every syn_trainer_init*) = the oracle's definition:
+ * every gradient entry is ONE chain over all samples in ascending order, which one workgroup walks (Connect4Net; the Connect4ConvNet
+ * learner refuses more than 32). SYN_TRAIN_BATCH_MICRO = a second, opt-in, deterministic definition that the whole GPU can work on:
+ *   a minibatch of B = 32 nb positions, in the order given, is nb micro-batches of 32 (sample 32 j + i = sample i of micro-batch j);
+ *   g_j[P], l_j[2] = exactly what the chained step computes for those 32 samples as a minibatch of their own (batch mean 1/32,
+ *     policy_weight and value_weight applied, the oracle's chains; in the conv learner's bf16 variant: that variant's step);
+ *   acc = g_0, then acc = acc + g_j for j = 1 .. nb-1: plain f32 additions in ascending j (nothing is added to g_0: for nb = 1 every
+ *     bit, the sign of a zero included, is the chained step's);
+ *   G = acc * inv, inv = 1.0f / (float)nb (an IEEE f32 division; one rounding, fused with nothing); the two losses alike;
+ *   Adam is unchanged: the same expression on G, same weight decay, step counter and scalars.
+ * G is the gradient of the mean loss over the B samples (a mean of equal-size block means) — gradient averaging over micro-batches of
+ * the reference's own batch size — and does not depend on how many workgroups computed it. Every gradient path honours the mode:
+ * syn_train_step, syn_train_gradients_device, syn_train_gradients_enqueue (on the caller's stream) and syn_train_epoch, which then
+ * queues three launches per step (micro-batch gradients on min(nb, cap) workgroups, the reduction, Adam) with one synchronisation at
+ * the end and never uses the persistent kernels; no workgroup waits for another one, so the step also runs beside a self-play launch.
+ * max_workgroups caps the gradient launch (0 = one workgroup per CU): a caller who trains beside self-play can leave CUs to it.
+ * In this mode batch % 32 != 0 is SYN_ERR_INVALID_ARGUMENT and batch > 32 * 1024 SYN_ERR_UNSUPPORTED, at every entry point above,
+ * with the learner left as it was. An unknown mode or a negative cap is SYN_ERR_INVALID_ARGUMENT; before syn_trainer_init*,
+ * SYN_ERR_NO_WEIGHTS. No learning rate is rescaled for the larger batch; what large batches do to the trained player is not measured. */
+enum { SYN_TRAIN_BATCH_CHAINED = 0, SYN_TRAIN_BATCH_MICRO = 1 };
+int syn_trainer_set_batch_mode(syn_engine* h, int mode, int max_workgroups);
+/* Any pointer may be NULL. *last_grid = workgroups of the last micro-batch gradient launch on this engine, 0 if there has been none. */
+int syn_trainer_get_batch_mode(syn_engine* h, int* mode, int* max_workgroups, int* last_grid);
 /* Copies out parameters / Adam moments / last gradient (each may be NULL) and the optimiser step count. */
 int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads);
 /* Replaces: vs.save(model_{i+1}.ot) + the workers' vs.load (alpha_zero.rs:97,194): the trained parameters become the

@@ -623,6 +623,9 @@ public:
                                 (int)games.size(), lr, losses.data()));
         return losses;
     }
+    // SYN_TRAIN_BATCH_CHAINED (default) | SYN_TRAIN_BATCH_MICRO: a batch of 32 nb positions as nb micro-batches of 32 spread over up
+    // to max_workgroups workgroups (0 = one per CU), their gradients averaged in ascending order (synthesis_amd.h)
+    void set_batch_mode(int mode, int max_workgroups = 0) { e_.check(syn_trainer_set_batch_mode(e_.handle(), mode, max_workgroups)); }
     // vs.save + reload in the workers (alpha_zero.rs:97,194): the engine's self-play network becomes the trained one
     void publish() { e_.check(syn_trainer_publish_weights(e_.handle())); }
 

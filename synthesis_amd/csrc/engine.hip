@@ -34,6 +34,7 @@
 #include "layer_kernels.cuh"
 #include "train_conv.cuh"
 #include "train_conv_mfma.cuh"
+#include "train_micro.cuh"
 #include "lane_instances.h"
 #include "launch_plan.hpp"
 #include "free_kernel.cuh"
@@ -193,6 +194,12 @@ struct syn_engine {
         bool conv_mw_checked = false;   // syn_trainer_init_conv's self-check of the four-workgroup kernel against the one-workgroup kernel has run
         bool conv_mw_disabled = false;  // ... and it failed: this engine keeps the one-workgroup epoch kernel
         int conv_mw_force = -1;         // self-check only: 0 = one workgroup, 1 = four
+        // syn_trainer_set_batch_mode (train_micro.cuh); every syn_trainer_init* puts the first two back to chained / 0
+        int batch_mode = SYN_TRAIN_BATCH_CHAINED;
+        int micro_max_wgs = 0;          // cap on the blocks launch's workgroups; 0 = the device's CU count
+        int micro_last_grid = 0;        // grid of the last blocks launch (0: none yet)
+        float* d_micro_rows = nullptr;  // the block buffer: row j = [g_j][l_j] of micro-batch j (MicroPlan::row_stride); grown on demand
+        size_t micro_rows_bytes = 0;
     } learner;
 };
 
@@ -609,6 +616,7 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_path);
     hipFree(h->d_vw);
     hipFree(h->learner.d_train_data);
+    hipFree(h->learner.d_micro_rows);
     hipFree(h->d_replay);
     hipFree(h->d_replay_alt);
     hipFree(h->d_cache);
@@ -1890,6 +1898,8 @@ int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const sy
     L.has_trainer = true;
     L.trainer_kind = 0;
     L.train_bf16 = 0;
+    L.batch_mode = SYN_TRAIN_BATCH_CHAINED;
+    L.micro_max_wgs = 0;
     // ---- the epoch kernel's one-XCD step barrier rests on observed hardware behaviour (train_epoch.cuh: `buffer_inv sc0` empties
     //      the vector L1 outside threadgroup-split mode). Once per engine: eight steps on a synthetic batch through that barrier and
     //      through the device-scope barrier from the same state; any differing bit switches this engine to the device-scope barrier.
@@ -1919,6 +1929,8 @@ int syn_trainer_init_conv(syn_engine* h, const float* blob, size_t n_floats, con
     L.has_trainer = true;
     L.trainer_kind = 1;
     L.train_bf16 = 0;
+    L.batch_mode = SYN_TRAIN_BATCH_CHAINED;
+    L.micro_max_wgs = 0;
     // ---- the four-workgroup epoch kernel exchanges its intermediates through L2 behind the one-XCD barrier of train_epoch.cuh (observed
     //      hardware behaviour, see there). Once per engine: eight steps on a synthetic batch through it and through the one-workgroup
     //      kernel from the same state; any differing bit (or a launch that cannot run) keeps this engine on the one-workgroup kernel.
@@ -1943,6 +1955,27 @@ int syn_trainer_set_precision(syn_engine* h, int precision) {
         return fail(h, SYN_ERR_UNSUPPORTED, "the bf16 training variant exists for Connect4ConvNet only (BASELINE configs[4]: \"bf16 conv\"); "
                                             "Connect4Net trains in f32, bit-exact with the oracle");
     L.train_bf16 = precision == SYN_TRAIN_BF16 ? 1 : 0;
+    return SYN_OK;
+}
+
+int syn_trainer_set_batch_mode(syn_engine* h, int mode, int max_workgroups) {
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    if (mode != SYN_TRAIN_BATCH_CHAINED && mode != SYN_TRAIN_BATCH_MICRO) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown batch mode %d", mode);
+    if (max_workgroups < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "max_workgroups is negative (%d); 0 means one workgroup per CU", max_workgroups);
+    HIP_TRY(h, hipSetDevice(h->device));
+    h->learner.batch_mode = mode;
+    h->learner.micro_max_wgs = max_workgroups;
+    return SYN_OK;
+}
+
+int syn_trainer_get_batch_mode(syn_engine* h, int* mode, int* max_workgroups, int* last_grid) {
+    const int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (mode) *mode = h->learner.batch_mode;
+    if (max_workgroups) *max_workgroups = h->learner.micro_max_wgs;
+    if (last_grid) *last_grid = h->learner.micro_last_grid;
     return SYN_OK;
 }
 
@@ -1994,10 +2027,62 @@ static int ensure_train_data(syn_engine* h, size_t need, size_t grow_to) {
     return SYN_OK;
 }
 
+// SYN_TRAIN_BATCH_MICRO's refusals, before anything is staged or launched: the learner is left as it was
+static_assert(PLAN_MICRO_BLOCK == MICRO_BLOCK && PLAN_MICRO_MAX_BLOCKS == MICRO_MAX_BLOCKS && PLAN_MLP_NUM_PARAMS == TrainGeom::NUM_PARAMS &&
+                  PLAN_CONV_NUM_PARAMS == ConvGeom::NUM_PARAMS && PLAN_MICRO_MLP_LDS == (size_t)TrainGeom::WL_OFF * 4 &&
+                  PLAN_MICRO_CONV_LDS == (size_t)ConvMfmaGeom::LDS_FLOATS * 4,
+              "launch_plan.hpp restates train_micro.cuh and the learners' geometry");
+static int check_micro_batch(syn_engine* h, int batch) {
+    if (h->learner.batch_mode != SYN_TRAIN_BATCH_MICRO) return SYN_OK;
+    if (batch < MICRO_BLOCK || batch % MICRO_BLOCK != 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "SYN_TRAIN_BATCH_MICRO takes minibatches that are a multiple of %d positions (got %d)", MICRO_BLOCK, batch);
+    if (batch / MICRO_BLOCK > MICRO_MAX_BLOCKS)
+        return fail(h, SYN_ERR_UNSUPPORTED, "SYN_TRAIN_BATCH_MICRO takes at most %d micro-batches of %d positions (got %d positions)",
+                    MICRO_MAX_BLOCKS, MICRO_BLOCK, batch);
+    return SYN_OK;
+}
+
+// The micro-batch gradient (train_micro.cuh): the blocks kernel over plan_micro_grads' grid, then the reduce, both on `st`.
+static int launch_grads_micro(syn_engine* h, hipStream_t st, const TrainSource& b, int batch, float* d_grads, float* d_losses) {
+    auto& L = h->learner;
+    const int rc = check_micro_batch(h, batch);
+    if (rc != SYN_OK) return rc;
+    MicroQuery q;
+    q.net_kind = L.trainer_kind; q.nb = batch / MICRO_BLOCK; q.max_workgroups = L.micro_max_wgs; q.num_cus = h->num_cus;
+    const MicroPlan p = plan_micro_grads(q);
+    if (p.buffer_bytes > L.micro_rows_bytes) {
+        // (hipFree waits for the device: nothing still reads the old rows)
+        if (L.d_micro_rows) HIP_TRY(h, hipFree(L.d_micro_rows));
+        L.d_micro_rows = nullptr;
+        L.micro_rows_bytes = 0;
+        HIP_TRY(h, hipMalloc(&L.d_micro_rows, p.buffer_bytes));
+        L.micro_rows_bytes = p.buffer_bytes;
+    }
+    int num_params;
+    if (L.trainer_kind == 1) {
+        auto kb = L.train_bf16 ? train_micro_blocks_conv_kernel<true> : train_micro_blocks_conv_kernel<false>;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kb), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+        hipLaunchKernelGGL(kb, dim3(p.grid), dim3(p.threads), p.lds, st, L.d_tw, b.my, b.op, b.pi, b.v, q.nb, L.train_hp, L.d_micro_rows);
+        num_params = ConvGeom::NUM_PARAMS;
+    } else {
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(train_micro_blocks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+        hipLaunchKernelGGL(train_micro_blocks_kernel, dim3(p.grid), dim3(p.threads), p.lds, st, L.d_twimg, L.d_ttimg, b.my, b.op, b.pi, b.v, q.nb,
+                           L.train_hp, L.d_micro_rows);
+        num_params = TrainGeom::NUM_PARAMS;
+    }
+    HIP_TRY(h, hipGetLastError());
+    L.micro_last_grid = p.grid;
+    hipLaunchKernelGGL(train_micro_reduce_kernel, dim3(p.reduce_grid), dim3(p.reduce_threads), 0, st, L.d_micro_rows, q.nb, num_params, p.row_stride,
+                       1.0f / (float)q.nb, d_grads, d_losses);
+    HIP_TRY(h, hipGetLastError());
+    return SYN_OK;
+}
+
 // (the *_enqueue entry points run the step on the caller's stream `st` — which may be the null stream: torch's default)
 static int launch_grads(syn_engine* h, hipStream_t st, const TrainSource& b, int batch, float* d_grads, float* d_losses = nullptr) {
     auto& L = h->learner;
     if (!d_losses) d_losses = L.d_tloss;
+    if (L.batch_mode == SYN_TRAIN_BATCH_MICRO) return launch_grads_micro(h, st, b, batch, d_grads, d_losses);
     if (L.trainer_kind == 1) {
         // Connect4ConvNet (train_conv_mfma.cuh): one workgroup, the minibatch's activations resident in LDS, every chain on the
         // f32 matrix cores
@@ -2104,6 +2189,8 @@ int syn_train_step(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, 
     int rc = learner_check(h);
     if (rc != SYN_OK) return rc;
     if (batch < 1 || !my_bb || !op_bb || !target_pi || !target_v) return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_step");
+    rc = check_micro_batch(h, batch);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     auto& L = h->learner;
     const size_t nb = (size_t)batch;
@@ -2373,8 +2460,9 @@ static int epoch_persistent_conv(syn_engine* h, const EpochStage& st, size_t n_s
     return SYN_OK;
 }
 
-// Two launches per step, queued and never synchronised in between (the weights of step s feed step s + 1): batches above 32 positions,
-// a persistent kernel that gave up, and SYN_DEBUG=1 SYN_TRAIN_QUEUED=1.
+// Two launches per step (three in SYN_TRAIN_BATCH_MICRO: launch_grads is then blocks + reduce), queued and never synchronised in
+// between (the weights of step s feed step s + 1): batches above 32 positions, a persistent kernel that gave up, the micro-batch
+// mode, and SYN_DEBUG=1 SYN_TRAIN_QUEUED=1.
 static int epoch_queued(syn_engine* h, const EpochStage& st, size_t n_steps, int batch, float lr, float* step_losses) {
     auto& L = h->learner;
     for (size_t s = 0; s < n_steps; s++) {
@@ -2393,10 +2481,15 @@ static int epoch_queued(syn_engine* h, const EpochStage& st, size_t n_steps, int
 int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses) {
     int rc = check_epoch(h, perm, n_steps, batch);
     if (rc != SYN_OK || n_steps == 0) return rc;
+    rc = check_micro_batch(h, batch);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     EpochStage st{};
     rc = stage_epoch(h, perm, n_steps, batch, &st);
     if (rc != SYN_OK) return rc;
+    // SYN_TRAIN_BATCH_MICRO: three queued launches per step (blocks, reduce, Adam) whatever the batch, one synchronisation at the end;
+    // no workgroup waits for another, so there is no snapshot and never a persistent kernel
+    if (h->learner.batch_mode == SYN_TRAIN_BATCH_MICRO) return epoch_queued(h, st, n_steps, batch, lr, step_losses);
     // One persistent launch for the whole epoch when the batch fits one 32-sample chunk — the reference's batch_size. Larger batches
     // queue two launches per step, as does a Connect4Net epoch whose persistent kernel gave up.
     const int kind = h->learner.trainer_kind;

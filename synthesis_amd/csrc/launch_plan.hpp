@@ -1,7 +1,8 @@
 // synthesis_amd — which kernel plays a self-play / search call, and on what launch shape: the decision alone, as a pure function of
 // plain numbers. Host-only C++17 without a HIP header, so the selection is read and tested on a CPU (tests/test_launch_plan.py).
 // engine.hip builds the query, grows the buffers the plan asks for, looks the plan's kernel up in the table of shipped
-// instantiations (lane_instances.h) and launches it. plan_eval, at the end, is the same for a policy-evaluation call.
+// instantiations (lane_instances.h) and launches it. plan_eval, further down, is the same for a policy-evaluation call, and
+// plan_micro_grads, at the end, for the learner's micro-batch gradient launch.
 #pragma once
 #include <climits>
 #include <cstddef>
@@ -381,6 +382,46 @@ inline EvalPlan plan_eval(const EvalQuery& q) {
     const int waves = p.threads / 64;
     p.grid = (ntiles + waves - 1) / waves;
     if (p.grid > q.num_cus) p.grid = q.num_cus;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ micro-batch learner step
+// The blocks launch of a SYN_TRAIN_BATCH_MICRO gradient (train_micro.cuh): nb micro-batches of 32 positions over min(nb, cap)
+// workgroups, cap = the caller's max_workgroups or, when that is 0, one workgroup per CU (the conv kernels' LDS admits no more, and a
+// Connect4Net workgroup is 16 waves). A workgroup walks its micro-batches j = b, b + grid, ...; the result does not depend on the grid.
+constexpr int PLAN_MICRO_BLOCK = 32;                   // train_micro.cuh MICRO_BLOCK
+constexpr int PLAN_MICRO_MAX_BLOCKS = 1024;            // train_micro.cuh MICRO_MAX_BLOCKS
+constexpr int PLAN_MLP_NUM_PARAMS = 30492;             // train_kernels.cuh TrainGeom::NUM_PARAMS
+constexpr int PLAN_CONV_NUM_PARAMS = 12412;            // convnet.cuh ConvGeom::NUM_PARAMS
+constexpr size_t PLAN_MICRO_MLP_LDS = 25792 * 4;      // train_kernels.cuh TrainGeom::WL_OFF floats
+constexpr size_t PLAN_MICRO_CONV_LDS = 39392 * 4;      // train_conv_mfma.cuh ConvMfmaGeom::LDS_FLOATS floats = 157,568 B: one workgroup per CU
+
+struct MicroQuery {
+    int net_kind = 0;         // 0 Connect4Net, 1 Connect4ConvNet (f32 and bf16 alike)
+    int nb = 0;               // micro-batches of the minibatch, 1 .. PLAN_MICRO_MAX_BLOCKS
+    int max_workgroups = 0;   // the caller's cap; 0 = the device's CU count
+    int num_cus = 256;
+};
+
+struct MicroPlan {
+    int grid = 0, threads = 0;
+    size_t lds = 0;
+    int row_stride = 0;       // floats of a block-buffer row: [gradients][2 losses], padded to a multiple of 64
+    size_t buffer_bytes = 0;  // nb rows
+    int reduce_grid = 0, reduce_threads = 64;   // train_micro.cuh MICRO_REDUCE_THREADS: one thread per parameter and loss word
+};
+
+inline MicroPlan plan_micro_grads(const MicroQuery& q) {
+    MicroPlan p;
+    const int cap = q.max_workgroups > 0 ? q.max_workgroups : q.num_cus;
+    p.grid = q.nb < cap ? q.nb : cap;
+    if (p.grid < 1) p.grid = 1;
+    const int params = q.net_kind == 1 ? PLAN_CONV_NUM_PARAMS : PLAN_MLP_NUM_PARAMS;
+    p.threads = q.net_kind == 1 ? 512 : 1024;
+    p.lds = q.net_kind == 1 ? PLAN_MICRO_CONV_LDS : PLAN_MICRO_MLP_LDS;
+    p.row_stride = (params + 2 + 63) & ~63;
+    p.buffer_bytes = (size_t)q.nb * (size_t)p.row_stride * 4;
+    p.reduce_grid = (params + 2 + p.reduce_threads - 1) / p.reduce_threads;
     return p;
 }
 

@@ -20,7 +20,7 @@ ABI_SYMBOLS = [
     "syn_load_weights_conv", "syn_set_network_arithmetic", "syn_get_network_arithmetic", "syn_f16x2_plan_of_blob",
     "syn_policy_eval_batch", "syn_policy_eval_batch_device", "syn_eval_ctx_create", "syn_eval_ctx_submit", "syn_eval_ctx_wait",
     "syn_eval_ctx_eval", "syn_eval_ctx_last_error", "syn_eval_ctx_destroy", "syn_features_batch", "syn_linear_forward",
-    "syn_conv2d_forward", "syn_activation_forward", "syn_mcts_search", "syn_mcts_search_rollout", "syn_mcts_search_lockstep", "syn_selfplay_run_lockstep", "syn_frozen_search_rollout", "syn_selfplay_run", "syn_progress", "syn_cancel", "syn_trainer_set_precision", "syn_last_timing", "syn_last_launch_shape", "syn_last_cache_stats", "syn_debug_stdrng_u32",
+    "syn_conv2d_forward", "syn_activation_forward", "syn_mcts_search", "syn_mcts_search_rollout", "syn_mcts_search_lockstep", "syn_selfplay_run_lockstep", "syn_frozen_search_rollout", "syn_selfplay_run", "syn_progress", "syn_cancel", "syn_trainer_set_precision", "syn_trainer_set_batch_mode", "syn_trainer_get_batch_mode", "syn_last_timing", "syn_last_launch_shape", "syn_last_cache_stats", "syn_debug_stdrng_u32",
     "syn_debug_math", "syn_debug_fast_div", "syn_debug_small_int_math", "syn_debug_calibrate", "syn_trainer_init", "syn_trainer_init_conv", "syn_train_step", "syn_train_gradients_device",
     "syn_train_apply_device", "syn_train_gradients_enqueue", "syn_train_apply_enqueue", "syn_trainer_get_state", "syn_trainer_publish_weights", "syn_replay_deduplicate", "syn_train_set_data", "syn_train_epoch",
     "syn_replay_reserve", "syn_replay_clear", "syn_replay_size", "syn_selfplay_positions_device", "syn_replay_append_selfplay",
@@ -28,6 +28,9 @@ ABI_SYMBOLS = [
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
 ]
+
+
+BATCH_MODES = {"chained": 0, "micro": 1}   # SYN_TRAIN_BATCH_*
 
 
 class SynthesisAmdError(RuntimeError):
@@ -139,6 +142,8 @@ def load_library():
     lib.syn_progress.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_cancel.argtypes = [C.c_void_p]
     lib.syn_trainer_set_precision.argtypes = [C.c_void_p, C.c_int]
+    lib.syn_trainer_set_batch_mode.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    lib.syn_trainer_get_batch_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.syn_last_launch_shape.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_last_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -587,6 +592,20 @@ class Engine:
         """"f32" (default; bit-identical to the oracle) | "bf16" (Connect4ConvNet learner only: bf16 matrix cores, f32 accumulation,
         f32 master weights and Adam — BASELINE configs[4]'s "bf16 conv")."""
         self._check(self._lib.syn_trainer_set_precision(self._h, {"f32": 0, "bf16": 1}[precision]))
+
+    def trainer_set_batch_mode(self, mode="chained", max_workgroups=0):
+        """"chained" (default: the oracle's one chain over the whole minibatch, one workgroup) | "micro" (SYN_TRAIN_BATCH_MICRO: a
+        minibatch of 32 nb positions is nb micro-batches of 32, each the chained step of its 32 samples, summed in ascending order and
+        multiplied by 1 / nb — on up to max_workgroups workgroups, 0 = one per CU; the batch must then be a multiple of 32)."""
+        if mode not in BATCH_MODES:
+            raise ValueError(f"batch mode must be one of {sorted(BATCH_MODES)}, got {mode!r}")
+        self._check(self._lib.syn_trainer_set_batch_mode(self._h, BATCH_MODES[mode], int(max_workgroups)))
+
+    def trainer_batch_mode(self):
+        """(mode, max_workgroups, workgroups of the last micro-batch gradient launch: 0 if there has been none)."""
+        m, w, g = C.c_int(), C.c_int(), C.c_int()
+        self._check(self._lib.syn_trainer_get_batch_mode(self._h, C.byref(m), C.byref(w), C.byref(g)))
+        return {v: k for k, v in BATCH_MODES.items()}[m.value], w.value, g.value
 
     def train_step(self, my_bb, op_bb, target_pi, target_v, lr):
         my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()

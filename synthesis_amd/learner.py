@@ -14,7 +14,10 @@ With one rank it is exactly the single-GPU loop. The games an iteration plays, t
 weights do not depend on the number of ranks.
 
 `DataParallelLearner` is the other reading of configs[4] — a gradient all-reduce per optimiser step — kept for callers who want
-it (large batches): every rank computes the gradients of ITS shard of the batch (`syn_train_gradients_device`), the gradient
+it. A large batch on ONE GPU no longer needs it: batch_mode="micro" (Engine.trainer_set_batch_mode; include/synthesis_amd.h
+SYN_TRAIN_BATCH_MICRO) spreads a batch of 32 nb positions over up to nb workgroups as nb micro-batches of 32 and averages their
+gradients in a fixed order, where the default chained definition walks any batch on one workgroup (and a rank's large shard here
+does too, unless it is given the same batch_mode). Every rank computes the gradients of ITS shard of the batch (`syn_train_gradients_device`), the gradient
 buffer and the two loss sums travel in ONE all-reduce, every rank applies the same Adam update with grad_scale = 1 / world
 (`syn_train_apply_device`), so weights stay identical without a broadcast. Both networks. The data set and the epoch's
 permutation live on the device; a step gathers its shard there and the losses stay on the device until asked for.
@@ -44,6 +47,10 @@ class LearningLoop:
     net          "mlp" (Connect4Net, study-connect4/src/policies.rs:14-59) | "conv" (Connect4ConvNet)
     blob         initial parameters — identical on every rank (P::new(&vs), alpha_zero.rs:31)
     precision    "f32" | "bf16" (Connect4ConvNet's learner only: syn_trainer_set_precision)
+    batch_mode   "chained" (default: the oracle's step, one chain over the minibatch) | "micro" (SYN_TRAIN_BATCH_MICRO: iteration()'s
+                 batch_size must then be a multiple of 32; it is nb micro-batches of 32 on up to nb workgroups, gradients averaged in
+                 ascending order — another definition of the step, deterministic, not the chained bits above 32). No learning rate is
+                 rescaled for the larger batch; what large batches do to the trained player is not measured.
     dist         torch.distributed (initialised) or None for one rank
     sampler      "numpy" (default: numpy's PCG64 permutation seeded by (seed, iteration, epoch)) | "torch": BatchRandSampler's own
                  `Tensor::randperm(n, INT64_CPU)` (data.rs:29) — libtorch's CPU randperm from ONE generator seeded with `seed` and
@@ -67,7 +74,7 @@ class LearningLoop:
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", replay="host", symmetry="none", **hyper):
+                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", **hyper):
         import torch
 
         self._torch = torch
@@ -93,6 +100,8 @@ class LearningLoop:
             (engine.trainer_init_conv if net == "conv" else engine.trainer_init)(blob, **hyper)
             if precision != "f32":
                 engine.trainer_set_precision(precision)   # "bf16": the conv learner's bf16 matrix-core variant (BASELINE configs[4])
+            if batch_mode != "chained":
+                engine.trainer_set_batch_mode(batch_mode)
         # replay buffer (rank 0): positions as bitboards + targets + the game each step came from (data.rs:107-158)
         self.R = dict(my=np.zeros(0, np.uint64), op=np.zeros(0, np.uint64), pi=np.zeros((0, 9), np.float32),
                       v=np.zeros((0, 3), np.float32), gid=np.zeros(0, np.int64))
@@ -104,6 +113,7 @@ class LearningLoop:
             raise ValueError(f"replay must be 'host' or 'device', got {replay!r}")
         if symmetry not in ("none", "mirror"):
             raise ValueError(f"symmetry must be 'none' or 'mirror', got {symmetry!r}")
+        self.batch_mode = batch_mode
         self.replay = replay
         self.symmetry = symmetry
         self._device = int(device)
@@ -403,8 +413,10 @@ class LearningLoop:
 class DataParallelLearner:
     """Gradient all-reduce per optimiser step (see the module docstring). Every rank holds identical weights and Adam moments."""
 
-    def __init__(self, engine, blob, dist=None, device=0, net="mlp", collective_at_world_1=False, network_arithmetic="f32", **hyper):
-        """collective_at_world_1: keep the all-reduce in the step when the group has one rank (bench.py's `data_parallel_world1`:
+    def __init__(self, engine, blob, dist=None, device=0, net="mlp", collective_at_world_1=False, network_arithmetic="f32", batch_mode="chained", **hyper):
+        """batch_mode: "chained" | "micro" (Engine.trainer_set_batch_mode): with "micro" every rank's shard of a batch must be a multiple
+        of 32 positions; it runs as micro-batches of 32 over the rank's whole GPU.
+        collective_at_world_1: keep the all-reduce in the step when the group has one rank (bench.py's `data_parallel_world1`:
         the literal gradients -> RCCL all-reduce -> Adam path of BASELINE configs[4] on a one-GPU box).
         network_arithmetic: "f32" | "f16x2", the arithmetic the engine's self-play evaluates the published network in."""
         import torch
@@ -417,6 +429,9 @@ class DataParallelLearner:
         self.device = torch.device(f"cuda:{device}")
         self.n_params = CONV_NUM_PARAMS if net == "conv" else NUM_PARAMS
         (engine.trainer_init_conv if net == "conv" else engine.trainer_init)(blob, **hyper)
+        if batch_mode != "chained":
+            engine.trainer_set_batch_mode(batch_mode)
+        self.batch_mode = batch_mode
         if network_arithmetic != "f32":
             engine.set_network_arithmetic(network_arithmetic)
         # [gradients | pi-loss sum | v-loss sum]: one buffer, one all-reduce per step
