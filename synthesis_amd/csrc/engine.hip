@@ -162,6 +162,7 @@ struct syn_engine {
     std::atomic<bool> eval_attr_set[EVAL_KERNELS] = {};   // launch_eval: the kernel's LDS attribute is set (indexed by EvalKernel)
     size_t eval_poll_max = 1024;       // contexts: batches up to this size signal completion through pinned memory (SYN_DEBUG=1 SYN_EVAL_POLL_MAX)
     size_t eval_zero_copy_out = 4096;  // contexts: results of up to this many positions are written into the pinned buffer by the kernel itself
+    bool eval_throughput_only = false;   // syn_policy_eval_batch_device: the throughput kernel at every size (SYN_DEBUG=1 SYN_EVAL_THROUGHPUT=1: tests of its tile)
     struct syn_eval_ctx* eval_ctx = nullptr;   // syn_policy_eval_batch's own evaluation context (created on first use)
     std::string err;
     float last_kernel_ms = 0.0f;
@@ -562,6 +563,7 @@ int syn_engine_create(const syn_engine_config* cfg, int device, syn_engine** out
     h->max_explores = cfg->max_explores;
     if (const char* ev = debug_env("SYN_EVAL_POLL_MAX")) h->eval_poll_max = (size_t)std::atoll(ev);
     if (const char* ev = debug_env("SYN_EVAL_ZC_OUT")) h->eval_zero_copy_out = (size_t)std::atoll(ev);
+    if (const char* ev = debug_env("SYN_EVAL_THROUGHPUT")) h->eval_throughput_only = ev[0] == '1';
     // nodes.len() <= 1 + 9*(explores+1), rounded up to keep slabs 16-byte-record aligned per 4 nodes
     h->cap = (uint32_t)(1 + 9 * (cfg->max_explores + 1));
     h->cap = (h->cap + 3u) & ~3u;
@@ -918,7 +920,10 @@ int syn_policy_eval_batch_device(syn_engine* h, const uint64_t* d_my, const uint
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
     { const int rc16 = require_f16x2_image(h); if (rc16 != SYN_OK) return rc16; }
-    HIP_TRY(h, launch_eval(h, plan_eval(eval_query(h, n)), h->stream, d_my, d_op, n, d_logits, d_value));
+    EvalQuery q = eval_query(h, n);
+    // (the debug knob plans as for a batch just past the latency kernel's range: the throughput kernels take any n, idle workgroups return)
+    if (h->eval_throughput_only && (size_t)q.n <= PLAN_EVAL_TILE_MAX) q.n = (int)PLAN_EVAL_TILE_MAX + 1;
+    HIP_TRY(h, launch_eval(h, plan_eval(q), h->stream, d_my, d_op, n, d_logits, d_value));
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
     h->last_launches = 1;
     if (sync) {

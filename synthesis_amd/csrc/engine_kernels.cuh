@@ -780,12 +780,14 @@ __global__ __launch_bounds__(NT) void policy_eval_kernel(const float* __restrict
                                                          const unsigned long long* __restrict__ op_bb, int n,
                                                          float* __restrict__ logits, float* __restrict__ value) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // layer 1's spread and quad tables (l1_tables.cuh): static LDS beside the dynamic weight image, so the launch plan's size stands
+    __shared__ __attribute__((aligned(16))) unsigned char l1tab[L1Tables::BYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     stage_weight_image(smem, g_wimg, tid, NT);
+    build_l1_tables(l1tab, tid, NT);
     __syncthreads();
     const int ntiles = (n + 15) >> 4;
     const int j = lane & 15, q = lane >> 4;
-    const FeatureTable FT = make_feature_table(q);
     for (int tile = blockIdx.x * (NT / 64) + wave; tile < ntiles; tile += gridDim.x * (NT / 64)) {
         // the weight fragments do not depend on the tile: make their LDS OFFSET opaque per iteration so the ~120 reads stay
         // next to the MFMAs that consume them instead of being hoisted out of the loop into spilled registers. (An opaque
@@ -797,9 +799,9 @@ __global__ __launch_bounds__(NT) void policy_eval_kernel(const float* __restrict
         int pos = tile * 16 + j;
         bool valid = pos < n;
         uint64_t my = valid ? my_bb[pos] : 0ull, op = valid ? op_bb[pos] : 0ull;
-        uint64_t hi, lo;
-        feature_boards(my, op, hi, lo);
-        f32x4 o = mlp_tile16(wimg, bimg, lane, FT, hi, lo);
+        uint64_t hi_t, lo_t;
+        feature_boards_transposed(l1tab, my, op, hi_t, lo_t);
+        f32x4 o = mlp_tile16_l1(wimg, bimg, lane, L1FromTables(l1tab, hi_t, lo_t, q));
         if (valid) {
             if (q < 2) {
 #pragma unroll

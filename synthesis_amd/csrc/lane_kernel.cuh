@@ -1395,12 +1395,13 @@ template <int NW>
 struct LaneLds {
     // weight + bias image: 123,264 B (Connect4Net f32, mlp.cuh) or 124,320 B (Connect4Net as f16 pairs, f16x2_tile.cuh)
     static constexpr size_t IDX_OFF = (size_t)MlpGeom::IMG_FLOATS * 4 > (size_t)F16Geom::IMG_WORDS * 4 ? (size_t)MlpGeom::IMG_FLOATS * 4 : (size_t)F16Geom::IMG_WORDS * 4;
-    static constexpr size_t FT_OFF = IDX_OFF + (size_t)NW * 64;        // + 64 B compaction index per wave
-    static constexpr size_t PARK_OFF = FT_OFF + 64;                    // + the four feature shift tables (16 B each)
+    static constexpr size_t L1_OFF = IDX_OFF + (size_t)NW * 64;        // + 64 B compaction index per wave
+    static constexpr size_t PARK_OFF = L1_OFF + L1Tables::BYTES;       // + layer 1's spread and quad tables (l1_tables.cuh: 1 KB + 4 KB)
     static constexpr size_t FPU_OFF = PARK_OFF + (size_t)NW * 64 * 20;  // + 5 parked dwords per lane (root boards, turn|rng)
     // + the Fpu::Func draw's table of normal quantiles (noise.cuh: 2,945 floats; staged by the configuration families that draw)
     static constexpr size_t BYTES = FPU_OFF + (((size_t)FPU_NORMAL_CELLS + 1) * 4 + 15) / 16 * 16;
     static_assert(BYTES <= 160 * 1024, "one workgroup per CU: 160 KB of LDS");
+    static_assert(L1_OFF % 16 == 0, "the quad table is read 16 bytes at a time");
 };
 
 SYN_DEV uint64_t shfl_u64(uint64_t v, int src) {
@@ -1437,10 +1438,8 @@ __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams
     ring.hi = 0;
     ring.job = -1;
     static_assert(POLICY != 1 || (size_t)NW * 3 * 16 * 64 * 4 <= (size_t)MlpGeom::IMG_FLOATS * 4, "rings must fit the image region");
-    if (tid < 4) {
-        const FeatureTable f = make_feature_table(tid);
-        *reinterpret_cast<uint4*>(smem_raw + LaneLds<NW>::FT_OFF + tid * 16) = make_uint4(f.t[0], f.t[1], f.t[2], f.t[3]);
-    }
+    unsigned char* const l1tab = smem_raw + LaneLds<NW>::L1_OFF;
+    if (POLICY == 0) build_l1_tables(l1tab, tid, NT);
     // Fpu::Func: the draw's table of normal quantiles next to the weights (the parity family never draws)
     float* const fpu_tbl = reinterpret_cast<float*>(smem_raw + LaneLds<NW>::FPU_OFF);
     if (FAST != 1)
@@ -1549,12 +1548,14 @@ __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // Connect4Net's layer 1 reads the derived boards in feature order: transposed here by every tree lane, once per round
+        uint64_t hi_t = 0, lo_t = 0;
+        if (POLICY == 0 && n_need > 0) feature_boards_transposed(l1tab, Wk.my, Wk.op, hi_t, lo_t);
 #pragma unroll 1
         for (int j = 0; j * 16 < n_need; j++) {
             if (PROF) pTiles++;
             const unsigned long long lp_b0 = lp ? lp_now() : 0ull;
-            // everything a tile needs is re-derived here instead of living in registers across the whole matrix phase:
-            // the two derived boards (10 VALU) and the lane's feature shift table (one 16-byte LDS read)
+            // (the f16x2 tile re-derives its two boards here instead of keeping them in registers across the whole matrix phase)
             const int src = (int)idxw[16 * j + (lane & 15)];  // (slots past the last request read lane 0: finite input)
             f32x4 o;
             if (POLICY == 2) {
@@ -1584,19 +1585,15 @@ __global__ __launch_bounds__(64 * NW, 1) void selfplay_kernel_lanes(EngineParams
 #pragma unroll
                 for (int r = 0; r < 4; r++) o[r] *= os;
             } else {
-                uint64_t hi, lo;
-                feature_boards(Wk.my, Wk.op, hi, lo);
-                const uint4 ftw = *reinterpret_cast<const uint4*>(smem_raw + LaneLds<NW>::FT_OFF + (lane >> 4) * 16);
-                FeatureTable FT;
-                FT.t[0] = ftw.x; FT.t[1] = ftw.y; FT.t[2] = ftw.z; FT.t[3] = ftw.w;
-                const uint64_t thi = shfl_u64(hi, src), tlo = shfl_u64(lo, src);
+                // position (lane & 15)'s transposed boards -> this lane's four quad-table offsets -> one ds_read_b128 per operand quad
+                const uint64_t thi = shfl_u64(hi_t, src), tlo = shfl_u64(lo_t, src);
                 if (lp_abl(lp, ABL_TILE)) {
                     uint64_t thi2 = thi, tlo2 = tlo;
                     asm volatile("" : "+v"(thi2), "+v"(tlo2));
-                    const f32x4 o2 = mlp_tile16_pipe(wimg, bimg, lane, FT, thi2, tlo2);
+                    const f32x4 o2 = mlp_tile16_pipe_l1(wimg, bimg, lane, L1FromTables(l1tab, thi2, tlo2, lane >> 4));
                     asm volatile("" ::"v"(o2));
                 }
-                o = mlp_tile16_pipe(wimg, bimg, lane, FT, thi, tlo);   // (the hand-pipelined tile at every wave count: the plain one spills around the crossbar fetches below)
+                o = mlp_tile16_pipe_l1(wimg, bimg, lane, L1FromTables(l1tab, thi, tlo, lane >> 4));   // (the hand-pipelined tile at every wave count: the plain one spills around the crossbar fetches below)
             }
             // (raw outputs: the softmax over the three outcome logits runs per tree lane in phase C, lane_softmaxes)
             const unsigned long long lp_b1 = lp ? lp_now() : 0ull;

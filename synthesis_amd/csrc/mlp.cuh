@@ -15,6 +15,7 @@
 //     ds_read_b128 per lane fetches the A operands of 4 consecutive k-steps, conflict-free (lane-linear 16 B).
 #pragma once
 #include "device_common.cuh"
+#include "l1_tables.cuh"
 
 namespace syn {
 
@@ -96,6 +97,59 @@ SYN_DEV f32x4 feature_quad(const FeatureTable& T, uint64_t hi, uint64_t lo) {
     return b;
 }
 
+// ---- layer-1 B operands by table (l1_tables.cuh) -------------------------------------------------------------------------
+// The two tables in LDS: L1Tables::BYTES at `tab` (16-byte aligned), the spread table first. Built by every thread of the
+// workgroup before the barrier that publishes the weight image.
+SYN_DEV void build_l1_tables(unsigned char* tab, int tid, int nthreads) {
+    uint64_t* spread = reinterpret_cast<uint64_t*>(tab);
+    uint32_t* quad = reinterpret_cast<uint32_t*>(tab + L1Tables::SPREAD_BYTES);
+    for (int i = tid; i < L1Tables::SPREAD_ENTRIES; i += nthreads) spread[i] = l1_spread_entry((uint32_t)i);
+    for (int i = tid; i < L1Tables::QUAD_WORDS; i += nthreads) quad[i] = l1_quad_word((uint32_t)i >> 2, i & 3);
+}
+// feature_boards in feature order (bit f = cell f = 9*row + col): nine ds_read_b64 per board
+SYN_DEV void feature_boards_transposed(const unsigned char* tab, uint64_t my, uint64_t op, uint64_t& hi_t, uint64_t& lo_t) {
+    uint64_t hi, lo;
+    feature_boards(my, op, hi, lo);
+    // (the pattern is made opaque so that each read's address is two instructions, a bit-field extract and a shift-add onto the
+    //  table's base; left to itself the compiler prefers shift, mask and add)
+    auto spread = [&](uint32_t p) {
+        asm("" : "+v"(p));
+        return *reinterpret_cast<const uint64_t*>(tab + p * 8u);
+    };
+    hi_t = l1_transpose(hi, spread);
+    lo_t = l1_transpose(lo, spread);
+}
+
+// Where a tile takes its layer-1 operands from: quad<S4>() is the B operand of k-steps 4*S4 .. 4*S4+3 on this lane.
+// L1FromBoards builds it from the column-major boards (the row, quad and free kernels and the debug shapes);
+// L1FromTables reads it from the quad table at offsets made once per tile from the transposed boards of position j.
+struct L1FromBoards {
+    static constexpr bool IS_LDS_READ = false;
+    FeatureTable T;
+    uint64_t hi, lo;
+    template <int S4>
+    SYN_DEV f32x4 quad() const { return feature_quad<S4>(T, hi, lo); }
+};
+struct L1FromTables {
+    static constexpr bool IS_LDS_READ = true;
+    const f32x4* entry[4];   // this lane's four quad table entries (LDS)
+    SYN_DEV L1FromTables(const unsigned char* tab, uint64_t hi_t, uint64_t lo_t, int q) {
+        uint32_t idx[4];
+        l1_quad_indices(hi_t, lo_t, q, idx);
+#pragma unroll
+        for (int s4 = 0; s4 < 4; s4++) {
+            asm("" : "+v"(idx[s4]));   // (opaque, as in feature_boards_transposed: extract, then shift-add onto the base)
+            entry[s4] = reinterpret_cast<const f32x4*>(tab + L1Tables::SPREAD_BYTES) + idx[s4];
+        }
+    }
+    template <int S4>
+    SYN_DEV f32x4 quad() const { return *entry[S4]; }
+};
+template <class L1>
+SYN_DEV f32x4 l1_quad_of(const L1& l1, int s4) {   // s4 is a compile-time constant after unrolling
+    return s4 == 0 ? l1.template quad<0>() : s4 == 1 ? l1.template quad<1>() : s4 == 2 ? l1.template quad<2>() : l1.template quad<3>();
+}
+
 // One layer: acc[ob] (NOB blocks) = bias; for every group of 4 k-steps: 4*NOB MFMAs, interleaved over the blocks
 // so consecutive MFMAs never depend on each other (dependent latency 40 cycles > 32-cycle issue).
 template <int LAYER, int NOB, int S4, class BOperand>
@@ -144,16 +198,12 @@ SYN_DEV void relu_inplace(f32x4 (&acc)[NOB]) {
 }
 
 // Evaluates the network for the 16 positions of this wave's tile. Lane l = (j = l&15, q = l>>4) must pass the
-// bitboards of position j. Returns the last layer's D registers: lane (j,q) register r = raw output 4*q + r of
-// position j (outputs 0..8 = policy logits, 9..11 = outcome logits, 12..15 = padding).
-SYN_DEV f32x4 mlp_tile16(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane,
-                         const FeatureTable& FT, uint64_t hi, uint64_t lo) {
+// layer-1 operands of position j (L1FromBoards / L1FromTables). Returns the last layer's D registers: lane (j,q) register
+// r = raw output 4*q + r of position j (outputs 0..8 = policy logits, 9..11 = outcome logits, 12..15 = padding).
+template <class L1>
+SYN_DEV f32x4 mlp_tile16_l1(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, const L1& l1) {
     f32x4 h1[8];
-    mlp_layer<0, 8, 4>(wimg, bimg, lane, [&](int s4) {
-        // s4 is a compile-time constant after unrolling; dispatch to the templated quad
-        return s4 == 0 ? feature_quad<0>(FT, hi, lo) : s4 == 1 ? feature_quad<1>(FT, hi, lo)
-             : s4 == 2 ? feature_quad<2>(FT, hi, lo) : feature_quad<3>(FT, hi, lo);
-    }, h1);
+    mlp_layer<0, 8, 4>(wimg, bimg, lane, [&](int s4) { return l1_quad_of(l1, s4); }, h1);
     relu_inplace(h1);
 
     f32x4 h2[6];
@@ -171,6 +221,11 @@ SYN_DEV f32x4 mlp_tile16(const float* __restrict__ wimg, const float* __restrict
     f32x4 out[1];
     mlp_layer<4, 1, 3>(wimg, bimg, lane, [&](int s4) { return h4[s4]; }, out);
     return out[0];
+}
+// ... from the two derived boards of position j in the game's layout
+SYN_DEV f32x4 mlp_tile16(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane,
+                         const FeatureTable& FT, uint64_t hi, uint64_t lo) {
+    return mlp_tile16_l1(wimg, bimg, lane, L1FromBoards{FT, hi, lo});
 }
 
 // Output blocks [OB0, OB0 + NB) of a layer with NOB blocks in total: same operands, same per-output fma chains as
@@ -254,8 +309,8 @@ struct PipeRegs {
     f32x4 h1[8], h2[6], h3[4], h4[3];
 };
 
-template <int GI>
-SYN_DEV void pipe_prefetch(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, PipeRegs& R) {
+template <int GI, class L1>
+SYN_DEV void pipe_prefetch(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, const L1& l1, PipeRegs& R) {
     if constexpr (GI < PIPE_GROUPS) {
         constexpr PipeGroup G = pipe_group(GI);
         const float* wl = wimg + MlpGeom::W_OFF[G.layer] + lane * 4;
@@ -268,27 +323,23 @@ SYN_DEV void pipe_prefetch(const float* __restrict__ wimg, const float* __restri
             for (int ob = 0; ob < G.nb; ob++)
                 R.bb[ob] = *reinterpret_cast<const f32x4*>(bimg + MlpGeom::B_OFF[G.layer] + ((G.ob0 + ob) * 4 + q) * 4);
         }
+        // a layer-1 operand that is itself an LDS read travels with the group's weight fragments
+        if constexpr (L1::IS_LDS_READ && G.layer == 0) R.fq[GI & 1] = l1.template quad<G.s4>();
     }
 }
 
-template <int GI>
-SYN_DEV void pipe_features(const FeatureTable& FT, uint64_t hi, uint64_t lo, PipeRegs& R) {
-    if constexpr (GI < PIPE_GROUPS) {
+template <int GI, class L1>
+SYN_DEV void pipe_features(const L1& l1, PipeRegs& R) {
+    if constexpr (GI < PIPE_GROUPS && !L1::IS_LDS_READ) {
         constexpr PipeGroup G = pipe_group(GI);
-        if constexpr (G.layer == 0) {
-            if constexpr (G.s4 == 0) R.fq[GI & 1] = feature_quad<0>(FT, hi, lo);
-            else if constexpr (G.s4 == 1) R.fq[GI & 1] = feature_quad<1>(FT, hi, lo);
-            else if constexpr (G.s4 == 2) R.fq[GI & 1] = feature_quad<2>(FT, hi, lo);
-            else R.fq[GI & 1] = feature_quad<3>(FT, hi, lo);
-        }
+        if constexpr (G.layer == 0) R.fq[GI & 1] = l1.template quad<G.s4>();
     }
 }
 
-template <int GI>
-SYN_DEV void pipe_group_run(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, const FeatureTable& FT,
-                            uint64_t hi, uint64_t lo, PipeRegs& R) {
+template <int GI, class L1>
+SYN_DEV void pipe_group_run(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, const L1& l1, PipeRegs& R) {
     constexpr PipeGroup G = pipe_group(GI);
-    pipe_prefetch<GI + 1>(wimg, bimg, lane, R);
+    pipe_prefetch<GI + 1>(wimg, bimg, lane, l1, R);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (G.s4 == 0) {
 #pragma unroll
@@ -305,8 +356,8 @@ SYN_DEV void pipe_group_run(const float* __restrict__ wimg, const float* __restr
 #pragma unroll
         for (int ob = 0; ob < G.nb; ob++)
             R.acc[ob] = __builtin_amdgcn_mfma_f32_16x16x4f32(R.a[GI & 1][ob][r], b[r], R.acc[ob], 0, 0, 0);
-    // the next layer-1 group's operands are built from the boards in the shadow of this group's MFMAs
-    pipe_features<GI + 1>(FT, hi, lo, R);
+    // operands built from the boards: the next layer-1 group's are made in the shadow of this group's MFMAs
+    pipe_features<GI + 1>(l1, R);
     if constexpr (G.s4 == G.ns4 - 1 && G.layer < 4) {
 #pragma unroll
         for (int ob = 0; ob < G.nb; ob++) {
@@ -318,17 +369,22 @@ SYN_DEV void pipe_group_run(const float* __restrict__ wimg, const float* __restr
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (GI + 1 < PIPE_GROUPS) pipe_group_run<GI + 1>(wimg, bimg, lane, FT, hi, lo, R);
+    if constexpr (GI + 1 < PIPE_GROUPS) pipe_group_run<GI + 1>(wimg, bimg, lane, l1, R);
 }
 
-// Lane l = (j = l&15, q = l>>4) passes the two feature boards of position j; returns the last layer's D registers (raw).
+// Lane l = (j = l&15, q = l>>4) passes the layer-1 operands of position j; returns the last layer's D registers (raw).
+template <class L1>
+SYN_DEV f32x4 mlp_tile16_pipe_l1(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane, const L1& l1) {
+    PipeRegs R;
+    pipe_prefetch<0>(wimg, bimg, lane, l1, R);
+    pipe_features<0>(l1, R);
+    pipe_group_run<0>(wimg, bimg, lane, l1, R);
+    return R.acc[0];
+}
+// ... from the two derived boards of position j in the game's layout (the debug shapes)
 SYN_DEV f32x4 mlp_tile16_pipe(const float* __restrict__ wimg, const float* __restrict__ bimg, int lane,
                               const FeatureTable& FT, uint64_t hi, uint64_t lo) {
-    PipeRegs R;
-    pipe_prefetch<0>(wimg, bimg, lane, R);
-    pipe_features<0>(FT, hi, lo, R);
-    pipe_group_run<0>(wimg, bimg, lane, FT, hi, lo, R);
-    return R.acc[0];
+    return mlp_tile16_pipe_l1(wimg, bimg, lane, L1FromBoards{FT, hi, lo});
 }
 
 // policies.rs:54-57: softmax over the three outcome logits (libtorch: max-subtracted), exp = det_expf,
