@@ -318,6 +318,41 @@ int syn_frozen_search_rollout(syn_engine* h, const syn_mcts_config* cfg, const u
                               const uint64_t* my_bb, const uint64_t* op_bb, const int32_t* explores, int n,
                               int action_selection, syn_frozen_result* results);
 
+/* ---- matches between two networks ------------------------------------------------------------------------------ */
+
+/* One side of a match: MCTS::exploit's arguments (evaluator.rs:129-160). */
+typedef struct syn_match_player {
+    int32_t explores;          /* per-move explores, <= the engine's max_explores */
+    int32_t action;            /* SYN_ACTION_* */
+    syn_mcts_config mcts_cfg;
+} syn_match_player;
+
+/* Replaces: the game loop of eval_against_old (evaluator.rs:129-160) for n_games games between two networks, from given start
+ * positions, without leaving the device between the first ply and the last. Game g starts at (start_my[g], start_op[g]) with
+ * `first` to move there (start_my = the mover's stones), whatever the stone counts say. Ply k of every game is searched by player
+ * k % 2 with that player's parameters, configuration and explores — MCTS::with_capacity + explore_n, then best_action
+ * (mcts.rs:123-147, 273-294): what syn_mcts_search returns for that root — and the move played is best_action.
+ *   rewards[g]   +1 / 0 / -1 for `first` (game.reward, evaluator.rs:160); a full board without four in a row is a draw
+ *   plies[g]     moves played in the match (not counting the stones of the start position)
+ *   moves        n_games x 63 columns, 255 from the game's end on; may be NULL
+ *   final_bb     n_games x 2: the stones of `first`, then of `second`, after the last move; may be NULL
+ * Both blobs are parameters of the engine's current network kind (n_floats = 30492 for Connect4Net, 12412 for Connect4ConvNet, else
+ * SYN_ERR_INVALID_ARGUMENT) and are evaluated in the engine's current network arithmetic (f16x2: a blob without a plan is
+ * SYN_ERR_UNSUPPORTED). They are built into two image buffers the match owns: the engine's own network, its f16x2 image and its policy
+ * cache are bit for bit what they were before the call, and the match's searches neither read nor write the cache. The engine needs no
+ * weights of its own.
+ * Deterministic players only: SYN_FPU_NORMAL, SYN_FPU_FUNC and SYN_NOISE_DIRICHLET are SYN_ERR_UNSUPPORTED (their draws are keyed by
+ * job index, which changes as games end). explores above max_explores is SYN_ERR_CAPACITY. A start position must pass
+ * syn_mcts_search's check and neither side may have four in a row there (SYN_ERR_INVALID_ARGUMENT). Every refusal happens before
+ * anything changes. n_games may exceed concurrent_games (the searches queue as in syn_mcts_search); n_games == 0 is SYN_OK.
+ * Per ply the host launches the search, two small kernels and a scan and reads back one word (the number of games that go on);
+ * nothing is uploaded after the first launch. syn_last_timing: the summed device time of all plies and the number of launches (three
+ * per ply: search, advance, compaction). syn_cancel: the call returns SYN_ERR_CANCELLED after the ply in flight and the outputs are
+ * unspecified; syn_progress reports the current ply's search. */
+int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
+                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
+                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb);
+
 /* ---- self-play ------------------------------------------------------------------------------------------------- */
 
 /* Event counters summed over all games of a run (definitions: SURVEY.md §8d; used for algorithmic-bytes accounting) */

@@ -1,0 +1,151 @@
+"""Which of two checkpoints is stronger, with an error bar: many games between two networks on the device (Engine.match_run =
+syn_match_run), from many different openings, each opening played once per colour.
+
+Two network players under ActionSelection::NumVisits and Fpu::Const are deterministic, so every game from the empty board is the same
+game; the information is in the openings. `random_openings` draws them, `compare` plays every opening twice (A first, B first: ONE
+match_run call per colour) and reduces the results to a score with its standard error over openings and the Elo difference that score
+implies. `host_match` is the same match on the host path of match.play_match (one mcts_search per ply, numpy steps), from given
+starts: what the device match is timed and tested against.
+
+Host code only draws openings and does statistics — no search, no network."""
+import math
+
+import numpy as np
+
+from . import match
+
+_U = np.uint64
+_COL = _U(0x7F)
+
+
+def mirror(bb):
+    """left-right mirror image of bitboards (bit = row + 7 * col: column c <-> column 8 - c)"""
+    bb = np.asarray(bb, np.uint64)
+    out = np.zeros(bb.shape, np.uint64)
+    for c in range(9):
+        out |= ((bb >> _U(7 * c)) & _COL) << _U(7 * (8 - c))
+    return out
+
+
+def _heights(occ):
+    """stones per column, [n, 9]"""
+    cols = (occ[:, None] >> (_U(7) * np.arange(9, dtype=np.uint64))[None, :]) & _COL
+    h = np.zeros(cols.shape, np.int64)
+    for r in range(7):
+        h += ((cols >> _U(r)) & _U(1)).astype(np.int64)
+    return h
+
+
+def random_openings(n, plies, seed, max_rounds=32):
+    """n start positions (my, op: uint64 arrays, the stones of the player to move first), each reached from the empty board by `plies`
+    uniformly random legal moves; none is won or full, and no two are equal or mirror images of each other.
+
+    The draw, so that a seed names a set of openings: rng = numpy.random.default_rng(seed) (PCG64). Candidates come in rounds of
+    2 * n + 64 games played side by side; at every ply ONE rng.random(size) call gives each game a u in [0, 1), and the game plays its
+    floor(u * L)-th legal column in ascending order, L = its number of legal columns. A candidate that ended on the way (four in a row,
+    or a full board) is dropped. Survivors are taken in candidate order; one whose position or mirror image was taken before is
+    skipped. Raises ValueError when n distinct openings have not been found after max_rounds rounds (too few reachable positions at
+    that depth: at 2 plies there are 45 up to mirror)."""
+    n, plies = int(n), int(plies)
+    if n < 0 or plies < 0 or plies > 62:
+        raise ValueError("random_openings: need n >= 0 and 0 <= plies <= 62")
+    rng = np.random.default_rng(seed)
+    size = 2 * n + 64
+    seen, out_my, out_op = set(), [], []
+    for _ in range(max_rounds):
+        if len(out_my) >= n:
+            break
+        my = np.zeros(size, np.uint64); op = np.zeros(size, np.uint64)
+        alive = np.ones(size, bool)
+        for _ply in range(plies):
+            u = rng.random(size)
+            legal = _heights(my | op) < 7
+            count = legal.sum(axis=1)
+            k = np.minimum((u * count).astype(np.int64), np.maximum(count - 1, 0))
+            col = ((np.cumsum(legal, axis=1) - 1 == k[:, None]) & legal).argmax(axis=1)
+            my, op, over, _w = match.step(my, op, col)
+            alive &= ~over & (count > 0)
+        m_my, m_op = mirror(my), mirror(op)
+        for i in np.nonzero(alive)[0]:
+            a, b = (int(my[i]), int(op[i])), (int(m_my[i]), int(m_op[i]))
+            key = min(a, b)
+            if key in seen:
+                continue
+            seen.add(key)
+            out_my.append(a[0]); out_op.append(a[1])
+            if len(out_my) >= n:
+                break
+    if len(out_my) < n:
+        raise ValueError(f"random_openings: only {len(out_my)} distinct openings of {plies} plies after {max_rounds} rounds of {size} draws, {n} wanted")
+    return np.array(out_my[:n], np.uint64), np.array(out_op[:n], np.uint64)
+
+
+def elo(score):
+    """Elo difference implied by a score in [0, 1], clipped as match.score clips (to [1e-3, 1 - 1e-3])"""
+    s = min(max(float(score), 1e-3), 1 - 1e-3)
+    return float(-400.0 * math.log10(1.0 / s - 1.0))
+
+
+def pair_statistics(rewards_a_first, rewards_b_first):
+    """The statistics of `compare` from the two reward vectors alone. rewards_a_first[o]: the first mover's reward (+1 / 0 / -1) in
+    opening o's game with A moving first; rewards_b_first[o]: the first mover's reward in the game with B moving first (so A scores
+    its negative). p_o = mean of A's two game scores (win 1, draw 1/2, loss 0), in {0, 1/4, 1/2, 3/4, 1}: the unit of the error bar is
+    the opening, because the two games of an opening are not independent. S = mean(p_o), SE = std(p_o, ddof=1) / sqrt(n) (nan for
+    fewer than two openings); the Elo difference of S and of S -/+ 1.96 SE."""
+    r1 = np.asarray(rewards_a_first, np.float64).ravel()
+    r2 = np.asarray(rewards_b_first, np.float64).ravel()
+    if r1.size != r2.size:
+        raise ValueError("pair_statistics: one reward per opening and colour")
+    n = int(r1.size)
+    p = ((1.0 + r1) / 2.0 + (1.0 - r2) / 2.0) / 2.0
+    s = float(p.mean()) if n else float("nan")
+    se = float(p.std(ddof=1) / math.sqrt(n)) if n >= 2 else float("nan")
+    lo, hi = s - 1.96 * se, s + 1.96 * se
+    fin = lambda x: elo(x) if x == x else float("nan")  # noqa: E731
+    return dict(openings=n,
+                wins=int((r1 > 0).sum() + (r2 < 0).sum()), draws=int((r1 == 0).sum() + (r2 == 0).sum()),
+                losses=int((r1 < 0).sum() + (r2 > 0).sum()),
+                pair_scores=p, score=s, se=se, score_lo=lo, score_hi=hi, elo=fin(s), elo_lo=fin(lo), elo_hi=fin(hi))
+
+
+def compare(engine, blob_a, blob_b, openings, player_a, player_b):
+    """Network A (blob_a, searched as player_a says) against network B on every opening, once with A moving first and once with B:
+    two Engine.match_run calls, all games of a colour in one. `openings` = (my, op) as random_openings returns them; the players are
+    anything with .explores, .action and .mcts_cfg (match.Player). Returns pair_statistics' dict (W/D/L from A's side) plus
+    "plies_a_first" / "plies_b_first"."""
+    my, op = openings
+    g1 = engine.match_run(player_a, player_b, blob_a, blob_b, my, op)
+    g2 = engine.match_run(player_b, player_a, blob_b, blob_a, my, op)
+    out = pair_statistics(g1["rewards"], g2["rewards"])
+    out["plies_a_first"], out["plies_b_first"] = g1["plies"], g2["plies"]
+    return out
+
+
+def host_match(engine, first, second, start_my, start_op):
+    """match.play_match's loop for two network players, from given start positions instead of the empty board: per ply one
+    engine.load_weights of the mover's blob (first.weights / second.weights), one engine.mcts_search over the live games and a numpy
+    step. REPLACES the engine's network, as play_match does. Returns Engine.match_run's dict."""
+    my = np.array(start_my, np.uint64).ravel(); op = np.array(start_op, np.uint64).ravel()
+    n = int(my.size)
+    alive = np.ones(n, bool)
+    out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
+               final_bb=np.zeros((n, 2), np.uint64))
+    for ply in range(63):
+        idx = np.nonzero(alive)[0]
+        if idx.size == 0:
+            break
+        p = first if ply % 2 == 0 else second
+        engine.load_weights_conv(p.weights) if np.size(p.weights) == 12412 else engine.load_weights(p.weights)
+        res = engine.mcts_search(p.mcts_cfg, my[idx], op[idx], p.explores, action_selection=int(p.action))
+        out["moves"][idx, ply] = res["best_action"]
+        nmy, nop, over, w = match.step(my[idx], op[idx], res["best_action"])
+        my[idx], op[idx] = nmy, nop
+        out["plies"][idx] += 1
+        first_moved = ply % 2 == 0
+        out["rewards"][idx[over & w]] = 1.0 if first_moved else -1.0
+        done = idx[over]
+        # (after the move the mover's stones are `op`)
+        out["final_bb"][done, 0] = op[done] if first_moved else my[done]
+        out["final_bb"][done, 1] = my[done] if first_moved else op[done]
+        alive[done] = False
+    return out

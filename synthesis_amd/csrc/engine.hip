@@ -27,6 +27,7 @@
 #include "frozen_kernel.cuh"
 #include "train_kernels.cuh"
 #include "replay_kernels.cuh"
+#include "match_kernels.cuh"
 #include "train_mfma.cuh"
 #include "train_epoch.cuh"
 #include "convnet.cuh"
@@ -93,7 +94,8 @@ struct syn_engine {
     int num_cus = 256;
     hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;  // syn_progress / syn_cancel: independent of the launch stream
-    int* h_pin = nullptr;              // 64 pinned bytes for their transfers: [0..1] syn_progress, [8] syn_cancel's word, [9] its pre-read
+    int* h_pin = nullptr;              // 64 pinned bytes for their transfers: [0..1] syn_progress, [8] syn_cancel's word, [9] its pre-read;
+                                       // [12] (the launch stream's, not theirs) syn_match_run's live-game count
     // The call in flight (syn_selfplay_run / syn_mcts_search* / syn_frozen_search_rollout) as syn_progress / syn_cancel see it.
     // call_mu orders their state changes and serialises the users of aux_stream and h_pin.
     std::mutex call_mu;
@@ -131,6 +133,13 @@ struct syn_engine {
         // the image the current arithmetic evaluates
         const float* image() const { return f16x2() ? reinterpret_cast<const float*>(d_wimg16) : d_wimg; }
     } net;
+    // syn_match_run's own device memory: the two players' network images (never the engine's: a match leaves `net` and the policy
+    // cache as they were) and one allocation for the live-game arrays, the per-ply results and the per-game outputs (MatchLayout)
+    struct Match {
+        void* d_img[2] = {nullptr, nullptr};   // each sized for the largest image of either network in either arithmetic
+        unsigned char* d_buf = nullptr;
+        size_t buf_bytes = 0;
+    } match;
     int* d_job_next = nullptr;
     uint4* d_cache = nullptr;      // PolicyWithCache table (policy_cache_log2 > 0)
     int cache_log2 = 0;
@@ -493,7 +502,9 @@ static int launch_engine(syn_engine* h, const EngineParams& P, int jobs, int mod
     q.jobs = jobs;
     q.cap = h->cap;
     q.net_kind = h->net.kind;
-    q.f16 = h->net.f16x2() && P.wimg == h->net.image();
+    // (syn_match_run's images are built in the engine's arithmetic)
+    const bool match_image = P.wimg != nullptr && (P.wimg == h->match.d_img[0] || P.wimg == h->match.d_img[1]);
+    q.f16 = h->net.f16x2() && (P.wimg == h->net.image() || match_image);
     q.pool_trees = h->pool_trees;
     q.mode = mode;
     q.count = count;
@@ -614,6 +625,9 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_stat);
     hipFree(h->net.d_wimg);
     hipFree(h->net.d_wimg16);
+    hipFree(h->match.d_img[0]);
+    hipFree(h->match.d_img[1]);
+    hipFree(h->match.d_buf);
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
@@ -709,11 +723,37 @@ static int empty_policy_cache(syn_engine* h) {
     return SYN_OK;
 }
 
+// Parameters become something a kernel reads in two steps: the image of the blob that one arithmetic evaluates is built on the host,
+// then uploaded into a device buffer. install_network and ensure_f16x2_image run them for the engine's own buffers, syn_match_run for
+// the two buffers a match owns.
+struct HostImage {
+    bool f16x2 = false;
+    std::vector<float> f32;         // !f16x2: the f32 fragment image
+    std::vector<uint32_t> words;    // f16x2: the f16x2 image
+    const void* data() const { return f16x2 ? static_cast<const void*>(words.data()) : static_cast<const void*>(f32.data()); }
+    size_t bytes() const { return (f16x2 ? words.size() : f32.size()) * 4; }
+};
+// a device buffer that holds any image of either network
+constexpr size_t NET_IMAGE_MAX_BYTES = (size_t)(MlpGeom::IMG_FLOATS > F16Geom::IMG_WORDS ? MlpGeom::IMG_FLOATS : F16Geom::IMG_WORDS) * 4;
+// (f16x2: parameters without a plan are refused, SYN_ERR_UNSUPPORTED, before anything has been touched)
+static int build_host_image(syn_engine* h, int kind, const float* blob, bool f16x2, HostImage& im) {
+    im.f16x2 = f16x2;
+    if (f16x2) return f16x2_image_of(h, kind, blob, im.words);
+    g_net_desc[kind].build_f32(blob, im.f32);
+    return SYN_OK;
+}
+// enqueued on the engine's stream: the caller synchronises before `im` goes away
+static int enqueue_image_upload(syn_engine* h, const HostImage& im, void* d_dst) {
+    HIP_TRY(h, hipMemcpyAsync(d_dst, im.data(), im.bytes(), hipMemcpyHostToDevice, h->stream));
+    return SYN_OK;
+}
+
 // (Connect4ConvNet's f16x2 image, conv_f16x2_tile.cuh, lives in the same buffer as Connect4Net's: it is the smaller of the two)
-static int upload_f16x2_image(syn_engine* h, const std::vector<uint32_t>& words) {
+static int upload_f16x2_image(syn_engine* h, const HostImage& im) {
     HIP_TRY(h, hipSetDevice(h->device));   // (every caller has selected it by now; kept because this helper allocates: test_abi_and_host.py)
     if (!h->net.d_wimg16) HIP_TRY(h, hipMalloc(&h->net.d_wimg16, (size_t)F16Geom::IMG_WORDS * 4));
-    HIP_TRY(h, hipMemcpyAsync(h->net.d_wimg16, words.data(), words.size() * 4, hipMemcpyHostToDevice, h->stream));
+    const int rc = enqueue_image_upload(h, im, h->net.d_wimg16);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -745,9 +785,9 @@ static int ensure_f16x2_image(syn_engine* h) {
     if (N.img16_current) return SYN_OK;
     if (N.host_blob.size() != (size_t)g_net_desc[N.kind].num_params)
         return fail(h, SYN_ERR_UNSUPPORTED, "the engine holds no host copy of its parameters to build the f16x2 image from");
-    std::vector<uint32_t> words;
-    int rc = f16x2_image_of(h, N.kind, N.host_blob.data(), words);
-    if (rc == SYN_OK) rc = upload_f16x2_image(h, words);
+    HostImage im;
+    int rc = build_host_image(h, N.kind, N.host_blob.data(), true, im);
+    if (rc == SYN_OK) rc = upload_f16x2_image(h, im);
     if (rc != SYN_OK) return rc;
     N.img16_current = true;
     return SYN_OK;
@@ -763,16 +803,15 @@ static int install_network(syn_engine* h, int kind, const float* blob) {
     const NetDesc& d = g_net_desc[kind];
     const bool want16 = N.f16x2();
     if (blob) {
-        std::vector<uint32_t> im16;
-        if (want16) { const int rc = f16x2_image_of(h, kind, blob, im16); if (rc != SYN_OK) return rc; }
-        std::vector<float> img;
-        d.build_f32(blob, img);
+        HostImage im16, img;
+        if (want16) { const int rc = build_host_image(h, kind, blob, true, im16); if (rc != SYN_OK) return rc; }
+        build_host_image(h, kind, blob, false, img);
         if (want16) {
             N.img16_current = false;
             const int rc = upload_f16x2_image(h, im16);
             if (rc != SYN_OK) return rc;
         }
-        HIP_TRY(h, hipMemcpyAsync(N.d_wimg, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        { const int rc = enqueue_image_upload(h, img, N.d_wimg); if (rc != SYN_OK) return rc; }
         HIP_TRY(h, hipStreamSynchronize(h->stream));
     } else if (kind == 1) {
         // Connect4ConvNet: the fragment image of convnet.cuh is rebuilt from the canonical parameters on the device
@@ -1406,6 +1445,190 @@ int syn_mcts_search(syn_engine* h, const syn_mcts_config* cfg, const uint64_t* m
 int syn_mcts_search_rollout(syn_engine* h, const syn_mcts_config* cfg, uint64_t seed, const uint64_t* my_bb,
                             const uint64_t* op_bb, int n, int explores, int action_selection, syn_search_result* results) {
     return mcts_search_impl(h, cfg, my_bb, op_bb, n, explores, action_selection, results, true, seed);
+}
+
+// ------------------------------------------------------------------------------------------------ device-resident matches
+// syn_match_run (match_kernels.cuh): every game of the call is searched, stepped and retired on the device. Per ply the host enqueues
+// one MODE_SEARCH launch over the live games' roots with the mover's image, the advance kernel, the scan and the compaction, and reads
+// ONE word back: how many games go on. Nothing is uploaded inside the loop; the outputs come back once, after the last ply.
+// The searches never touch the policy cache (P.cache = nullptr): its entries are keyed by position alone and belong to the engine's own
+// network, so a match neither reads another network's evaluations nor leaves its own behind.
+struct MatchLayout {   // byte offsets into syn_engine::Match::d_buf, each section 256-byte aligned
+    size_t my[2], op[2], id[2];   // the live games, two sets: a ply's compaction reads one and writes the other
+    size_t keep, dst, scan;       // survivor flags, their exclusive sum, the scan's temporary storage
+    size_t results;               // DevSearchResult per live job of the current ply
+    size_t rewards, plies, moves, final_bb;   // MatchOut, per game
+    size_t live;                  // the word the host reads per ply
+    size_t total;
+};
+static MatchLayout match_layout(size_t n, size_t scan_bytes) {
+    MatchLayout L{};
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    for (int k = 0; k < 2; k++) { L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); }
+    L.keep = take(n * 4); L.dst = take(n * 4); L.scan = take(scan_bytes);
+    L.results = take(n * sizeof(DevSearchResult));
+    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16);
+    L.live = take(4);
+    L.total = at;
+    return L;
+}
+
+// c4::won (device_common.cuh, device code) for the host's check of the start positions: the same four anchored lines, its masks
+static bool host_won(uint64_t bb) {
+    const uint64_t d1 = bb & (bb >> 6) & (bb >> 12) & (bb >> 18) & c4::D1_MASK;
+    const uint64_t d2 = bb & (bb >> 8) & (bb >> 16) & (bb >> 24) & c4::D2_MASK;
+    const uint64_t hz = bb & (bb >> 7) & (bb >> 14) & (bb >> 21) & c4::H_MASK;
+    const uint64_t vt = bb & (bb >> 1) & (bb >> 2) & (bb >> 3) & c4::V_MASK;
+    return (d1 | d2 | hz | vt) != 0;
+}
+
+// one side of a match: its configuration must be one whose search is a function of the root alone
+static int check_match_player(syn_engine* h, const char* who, const syn_match_player* p, DevMctsCfg& m) {
+    if (!p) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", who);
+    if (p->action != SYN_ACTION_Q && p->action != SYN_ACTION_NUM_VISITS)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player's action selection %d is unknown", who, p->action);
+    if (p->mcts_cfg.fpu == SYN_FPU_NORMAL || p->mcts_cfg.fpu == SYN_FPU_FUNC || p->mcts_cfg.root_policy_noise == SYN_NOISE_DIRICHLET)
+        return fail(h, SYN_ERR_UNSUPPORTED, "syn_match_run: the %s player draws random numbers (SYN_FPU_NORMAL / SYN_FPU_FUNC / "
+                                            "SYN_NOISE_DIRICHLET); their streams are keyed by job index, which changes as games end: "
+                                            "a match takes deterministic players only", who);
+    if (p->explores < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player's explores must be >= 0", who);
+    if (p->explores > h->max_explores)
+        return fail(h, SYN_ERR_CAPACITY, "syn_match_run: the %s player's explores %d exceed the engine's max_explores %d", who,
+                    p->explores, h->max_explores);
+    return convert_mcts(h, &p->mcts_cfg, m);
+}
+
+int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
+                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
+                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
+    // ---- everything that can refuse the call, before anything of the engine or the device changes
+    const syn_match_player* const players[2] = {first, second};
+    const float* const blobs[2] = {blob_first, blob_second};
+    const int kind = h->net.kind;
+    const bool f16x2 = h->net.f16x2();
+    EngineParams P[2];
+    for (int s = 0; s < 2; s++) {
+        DevMctsCfg m{};
+        int rc = check_match_player(h, s == 0 ? "first" : "second", players[s], m);
+        if (rc == SYN_OK) rc = check_blob(h, kind, blobs[s], n_floats);
+        if (rc == SYN_OK) rc = common_params(h, P[s], players[s]->explores, /*need_weights=*/false);
+        if (rc != SYN_OK) return rc;
+        P[s].mcts = m;
+        P[s].cache = nullptr;
+        P[s].roll.num_explores = players[s]->explores;
+        P[s].action_selection = players[s]->action;
+    }
+    if (n_games == 0) return SYN_OK;
+    for (int g = 0; g < n_games; g++) {
+        if (!valid_root(start_my[g], start_op[g]))
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is not a searchable Connect4 position "
+                        "(overlapping / floating stones, bit 63 set, or no free column)", g);
+        if (host_won(start_my[g]) || host_won(start_op[g]))
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is a finished game: one side has four in a row", g);
+    }
+    HostImage im[2];
+    for (int s = 0; s < 2; s++) {
+        const int rc = build_host_image(h, kind, blobs[s], f16x2, im[s]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
+        if (rc != SYN_OK) return rc;
+    }
+    // ---- the match's own device memory
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t n = (size_t)n_games;
+    size_t scan_bytes = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, n_games, h->stream));
+    const MatchLayout L = match_layout(n, scan_bytes);
+    for (int s = 0; s < 2; s++)
+        if (!h->match.d_img[s]) HIP_TRY(h, hipMalloc(&h->match.d_img[s], NET_IMAGE_MAX_BYTES));
+    HIP_TRY(h, ensure_device_buffer(h->match.d_buf, h->match.buf_bytes, L.total));
+    unsigned char* const base = h->match.d_buf;
+    const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
+    unsigned long long* const d_my[2] = {u64_at(L.my[0]), u64_at(L.my[1])};
+    unsigned long long* const d_op[2] = {u64_at(L.op[0]), u64_at(L.op[1])};
+    int* const d_id[2] = {reinterpret_cast<int*>(base + L.id[0]), reinterpret_cast<int*>(base + L.id[1])};
+    unsigned* const d_keep = reinterpret_cast<unsigned*>(base + L.keep);
+    unsigned* const d_dst = reinterpret_cast<unsigned*>(base + L.dst);
+    DevSearchResult* const d_res = reinterpret_cast<DevSearchResult*>(base + L.results);
+    int* const d_live = reinterpret_cast<int*>(base + L.live);
+    MatchOut out;
+    out.rewards = reinterpret_cast<float*>(base + L.rewards);
+    out.plies = reinterpret_cast<int*>(base + L.plies);
+    out.moves = base + L.moves;
+    out.final_bb = u64_at(L.final_bb);
+
+    CallScope scope(h, n_games);
+    std::vector<int> iota(n);
+    for (size_t g = 0; g < n; g++) iota[g] = (int)g;
+    for (int s = 0; s < 2; s++) {
+        const int rc = enqueue_image_upload(h, im[s], h->match.d_img[s]);
+        if (rc != SYN_OK) return rc;
+        P[s].wimg = static_cast<const float*>(h->match.d_img[s]);
+    }
+    HIP_TRY(h, hipMemcpyAsync(d_my[0], start_my, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_op[0], start_op, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_id[0], iota.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(base + L.rewards, 0, L.moves - L.rewards, h->stream));   // rewards and plies
+    HIP_TRY(h, hipMemsetAsync(out.moves, MATCH_NO_MOVE, n * MATCH_T, h->stream));
+    HIP_TRY(h, hipMemsetAsync(out.final_bb, 0, n * 16, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the last upload from host memory: the loop below only launches and reads one word
+
+    float kernel_ms = 0.0f;
+    int launches = 0, live = n_games, ply = 0;
+    for (; live > 0 && ply < MATCH_T; ply++) {
+        const int s = ply & 1, cur = ply & 1, nxt = cur ^ 1;
+        // (a syn_cancel's word does not survive the next ply's reset: the loop itself stops at the first ply that ends after it)
+        HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));
+        if (ply == 0) HIP_TRY(h, scope.armed());
+        // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
+        HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(DevSearchResult), h->stream));
+        EngineParams Q = P[s];
+        Q.n_jobs = live;
+        Q.in_my = d_my[cur];
+        Q.in_op = d_op[cur];
+        Q.results = d_res;
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        if (const int rc = launch_engine(h, Q, live, MODE_SEARCH, false, false)) return rc;
+        const dim3 grid((unsigned)((live + 255) / 256)), block(256);
+        hipLaunchKernelGGL(match_advance_kernel, grid, block, 0, h->stream, d_res, live, ply, d_my[cur], d_op[cur], d_id[cur], d_keep, out);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(base + L.scan, scan_bytes, d_keep, d_dst, live, h->stream));
+        hipLaunchKernelGGL(match_compact_kernel, grid, block, 0, h->stream, d_keep, d_dst, live, d_my[cur], d_op[cur], d_id[cur], d_my[nxt],
+                           d_op[nxt], d_id[nxt], Q.error, d_live);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_pin + 12, d_live, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        float ms = 0.0f;
+        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        kernel_ms += ms;
+        launches += 3;   // the search, the advance and the compaction (the scan between them is the library's)
+        h->last_kernel_ms = kernel_ms;
+        h->last_launches = launches;
+        if (scope.cancelled())
+            return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the match: the outputs are unspecified", ply);
+        const int now = h->h_pin[12];
+        if (now == -2)
+            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)",
+                        h->cap / 4, h->max_explores);
+        if (now < 0) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+        if (now > live) return fail(h, SYN_ERR_HIP, "syn_match_run: %d games survived a ply that %d entered", now, live);
+        live = now;
+    }
+    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_match_run: %d games are unfinished after %d plies", live, MATCH_T);
+    HIP_TRY(h, hipMemcpyAsync(rewards, out.rewards, n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
+    if (final_bb) HIP_TRY(h, hipMemcpyAsync(final_bb, out.final_bb, n * 16, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->last_cache_hits = h->last_cache_misses = 0;   // a match does not use the policy cache
+    return SYN_OK;
 }
 
 // evaluator.rs:308-319 FrozenMCTS::exploit over RolloutPolicy for n roots (frozen_kernel.cuh)

@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "syn_replay_append_device", "syn_replay_append", "syn_replay_keep_games_from", "syn_replay_read",
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
+    "syn_match_run",
 ]
 
 
@@ -47,6 +48,10 @@ class CSearchResult(C.Structure):  # struct syn_search_result
         ("num_nodes", C.c_uint32), ("best_action", C.c_int32),
         ("target_pi", C.c_float * 9), ("target_q", C.c_float * 3),
     ]
+
+
+class CMatchPlayer(C.Structure):  # struct syn_match_player
+    _fields_ = [("explores", C.c_int32), ("action", C.c_int32), ("mcts_cfg", CMctsConfig)]
 
 
 class CF16x2Plan(C.Structure):  # struct syn_f16x2_plan
@@ -139,6 +144,8 @@ def load_library():
                                     [C.c_void_p] * 8
     lib.syn_selfplay_run_lockstep.argtypes = [C.c_void_p, C.POINTER(CRolloutConfig), C.c_uint64, C.c_uint64, C.c_int, C.c_int] + \
                                              [C.c_void_p] * 8
+    lib.syn_match_run.argtypes = [C.c_void_p, C.POINTER(CMatchPlayer), C.POINTER(CMatchPlayer), C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.syn_progress.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_cancel.argtypes = [C.c_void_p]
     lib.syn_trainer_set_precision.argtypes = [C.c_void_p, C.c_int]
@@ -436,6 +443,29 @@ class Engine:
         out = self._search_records(res, n)
         if rc == -7:
             out["cancelled"] = True
+        return out
+
+    # ---- eval_against_old's game loop (evaluator.rs:129-160) for many games, resident on the device
+    def match_run(self, first, second, blob_first, blob_second, start_my, start_op):
+        """syn_match_run: game g starts at (start_my[g], start_op[g]) with `first` to move; ply k is searched by player k % 2 with its
+        own blob. `first` / `second`: anything with .explores, .action and .mcts_cfg (a match.Player, an arena.ArenaPlayer); only
+        deterministic configurations. Both blobs are of the engine's current network kind and run in its current arithmetic; the
+        engine's own network and policy cache are untouched. Returns dict(rewards [n] for `first`, plies [n], moves [n, 63] (255 = no
+        move), final_bb [n, 2] = (first's stones, second's stones))."""
+        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
+        if my.size != op.size:
+            raise ValueError("start_my and start_op must have the same length")
+        b1 = np.ascontiguousarray(blob_first, dtype=np.float32).ravel()
+        b2 = np.ascontiguousarray(blob_second, dtype=np.float32).ravel()
+        if b1.size != b2.size:
+            raise ValueError("both blobs must be parameters of the same network")
+        n = int(my.size)
+        players = [CMatchPlayer(int(p.explores), int(p.action), p.mcts_cfg.to_c()) for p in (first, second)]
+        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
+                   final_bb=np.zeros((n, 2), np.uint64))
+        self._check(self._lib.syn_match_run(self._h, C.byref(players[0]), C.byref(players[1]), _p(b1), _p(b2), b1.size, _p(my), _p(op), n,
+                                            _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]), _p(out["final_bb"])))
         return out
 
     @staticmethod
