@@ -353,6 +353,44 @@ int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_
                   const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
                   float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb);
 
+/* What plays one side of a match, and for a network side the arithmetic its parameters are evaluated in. */
+enum { SYN_MATCH_SIDE_NETWORK = 0, SYN_MATCH_SIDE_BASELINE = 1 };
+enum { SYN_MATCH_ARITH_ENGINE = 0, SYN_MATCH_ARITH_F32 = 1, SYN_MATCH_ARITH_F16X2 = 2 };
+typedef struct syn_match_side {
+    int32_t kind;          /* SYN_MATCH_SIDE_* */
+    int32_t arithmetic;    /* SYN_MATCH_ARITH_*; network sides only */
+    syn_match_player player;
+    const float* blob;     /* network sides: parameters of the engine's network kind; baseline sides: NULL */
+    size_t n_floats;
+} syn_match_side;
+
+/* syn_match_run with a description per side. A zero-initialised kind / arithmetic means "network side, the engine's arithmetic": two
+ * such sides make the call behave as syn_match_run does, bit for bit (that call is this one with two such sides).
+ * Network side (SYN_MATCH_SIDE_NETWORK): what syn_match_run plays — MCTS::with_capacity + explore_n + best_action, the policy cache
+ *   off, deterministic configurations only, explores <= max_explores. `arithmetic` chooses the image this side's blob is built into
+ *   and the kernel family its plies launch, independently of the other side and of the engine: SYN_MATCH_ARITH_F32 against
+ *   SYN_MATCH_ARITH_F16X2 is one checkpoint's two arithmetics meeting, on an engine in either. SYN_MATCH_ARITH_F16X2 on a blob without
+ *   an f16x2 plan is SYN_ERR_UNSUPPORTED. The engine's own network, arithmetic, f16x2 image, host blob and policy cache are bit for
+ *   bit what they were before the call.
+ * Baseline side (SYN_MATCH_SIDE_BASELINE): FrozenMCTS::exploit(explores, cfg, &mut RolloutPolicy{rng}, game, action)
+ *   (evaluator.rs:308-319), the "VanillaMCTS<explores>" of eval_against_rollout_mcts / mcts_vs_mcts (evaluator.rs:163-228): what
+ *   the baseline search above computes for that root. Game g owns ONE generator, StdRng::seed_from_u64(seeds[g]), for the whole game,
+ *   from output word 0; every baseline ply of the game advances it, whichever side the ply belongs to (two baseline sides share it,
+ *   evaluator.rs:207-208), and a network ply does not touch it. rng_words[g] (may be NULL) is the first unused word when the game
+ *   ended (0 for every game when neither side is a baseline). seeds may be NULL only when neither side is a baseline.
+ *   player.mcts_cfg must be Exploration::Uct + Fpu::Const (else SYN_ERR_UNSUPPORTED); player.explores is bounded by the node pool as
+ *   in the baseline search (SYN_ERR_CAPACITY), not by max_explores; blob and n_floats are ignored and no weights are needed. The
+ *   generator's state stays on the device and follows its game through the compaction; a stream position past 0xC0000000 (the
+ *   baseline search's supported length) is detected on the device after the ply that reached it and ends the call with
+ *   SYN_ERR_CAPACITY: it is never wrapped.
+ * An unknown kind or arithmetic is SYN_ERR_INVALID_ARGUMENT. Everything else — start positions, the other outputs, refusals before
+ * anything changes, n_games beyond the engine's slots, n_games == 0, one word read back per ply and nothing uploaded after the first
+ * launch, the timing summed over plies, cancellation after the ply in flight — is as documented for syn_match_run. Both kinds of
+ * search use the engine's node pool and alternate on one stream. */
+int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
+                        const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                        uint64_t* final_bb, uint64_t* rng_words);
+
 /* ---- self-play ------------------------------------------------------------------------------------------------- */
 
 /* Event counters summed over all games of a run (definitions: SURVEY.md §8d; used for algorithmic-bytes accounting) */

@@ -5,7 +5,9 @@ Two network players under ActionSelection::NumVisits and Fpu::Const are determin
 game; the information is in the openings. `random_openings` draws them, `compare` plays every opening twice (A first, B first: ONE
 match_run call per colour) and reduces the results to a score with its standard error over openings and the Elo difference that score
 implies. `host_match` is the same match on the host path of match.play_match (one mcts_search per ply, numpy steps), from given
-starts: what the device match is timed and tested against.
+starts: what the device match is timed and tested against. A player may name an `.arithmetic` of its own ("f32" / "f16x2"): `compare`
+then plays through Engine.match_run_sides, so one checkpoint can meet itself in the other arithmetic; `compare_baseline` plays a
+checkpoint against the evaluator's VanillaMCTS<n> (match.vanilla_player) with the same statistics.
 
 Host code only draws openings and does statistics — no search, no network."""
 import math
@@ -108,14 +110,46 @@ def pair_statistics(rewards_a_first, rewards_b_first):
                 pair_scores=p, score=s, se=se, score_lo=lo, score_hi=hi, elo=fin(s), elo_lo=fin(lo), elo_hi=fin(hi))
 
 
+class _Side:
+    """a player's search settings with a blob of its own: what Engine.match_run_sides takes as a network side"""
+    frozen = False
+    rollout = False
+
+    def __init__(self, player, blob):
+        self.explores, self.action, self.mcts_cfg = player.explores, player.action, player.mcts_cfg
+        self.arithmetic = getattr(player, "arithmetic", None)
+        self.weights = blob
+
+
+def _match(engine, first, second, blob_first, blob_second, my, op):
+    """one colour of `compare`: Engine.match_run, or Engine.match_run_sides when a player names an arithmetic of its own"""
+    if getattr(first, "arithmetic", None) is None and getattr(second, "arithmetic", None) is None:
+        return engine.match_run(first, second, blob_first, blob_second, my, op)
+    return engine.match_run_sides(_Side(first, blob_first), _Side(second, blob_second), my, op)
+
+
 def compare(engine, blob_a, blob_b, openings, player_a, player_b):
     """Network A (blob_a, searched as player_a says) against network B on every opening, once with A moving first and once with B:
-    two Engine.match_run calls, all games of a colour in one. `openings` = (my, op) as random_openings returns them; the players are
-    anything with .explores, .action and .mcts_cfg (match.Player). Returns pair_statistics' dict (W/D/L from A's side) plus
-    "plies_a_first" / "plies_b_first"."""
+    two device matches, all games of a colour in one. `openings` = (my, op) as random_openings returns them; the players are
+    anything with .explores, .action and .mcts_cfg (match.Player) and an optional .arithmetic (None: the engine's, "f32", "f16x2" —
+    the same blob for both players and two arithmetics is one checkpoint against itself in the other arithmetic). Returns
+    pair_statistics' dict (W/D/L from A's side) plus "plies_a_first" / "plies_b_first"."""
     my, op = openings
-    g1 = engine.match_run(player_a, player_b, blob_a, blob_b, my, op)
-    g2 = engine.match_run(player_b, player_a, blob_b, blob_a, my, op)
+    g1 = _match(engine, player_a, player_b, blob_a, blob_b, my, op)
+    g2 = _match(engine, player_b, player_a, blob_b, blob_a, my, op)
+    out = pair_statistics(g1["rewards"], g2["rewards"])
+    out["plies_a_first"], out["plies_b_first"] = g1["plies"], g2["plies"]
+    return out
+
+
+def compare_baseline(engine, blob_a, openings, player_a, baseline, seeds):
+    """Network A against the evaluator's baseline (match.vanilla_player) on every opening, both colours, game o of either colour on
+    StdRng::seed_from_u64(seeds[o]): the absolute anchor of the reference's evaluator (eval_against_rollout_mcts) with compare's
+    statistics. Returns compare's dict."""
+    my, op = openings
+    a = _Side(player_a, blob_a)
+    g1 = engine.match_run_sides(a, baseline, my, op, seeds=seeds)
+    g2 = engine.match_run_sides(baseline, a, my, op, seeds=seeds)
     out = pair_statistics(g1["rewards"], g2["rewards"])
     out["plies_a_first"], out["plies_b_first"] = g1["plies"], g2["plies"]
     return out
@@ -124,28 +158,40 @@ def compare(engine, blob_a, blob_b, openings, player_a, player_b):
 def host_match(engine, first, second, start_my, start_op):
     """match.play_match's loop for two network players, from given start positions instead of the empty board: per ply one
     engine.load_weights of the mover's blob (first.weights / second.weights), one engine.mcts_search over the live games and a numpy
-    step. REPLACES the engine's network, as play_match does. Returns Engine.match_run's dict."""
+    step. A player with an .arithmetic ("f32" / "f16x2") is searched in it: the engine is switched before that player's plies, and
+    put back to the arithmetic it was in before returning. REPLACES the engine's network, as play_match does. Returns
+    Engine.match_run's dict."""
     my = np.array(start_my, np.uint64).ravel(); op = np.array(start_op, np.uint64).ravel()
     n = int(my.size)
     alive = np.ones(n, bool)
     out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
                final_bb=np.zeros((n, 2), np.uint64))
-    for ply in range(63):
-        idx = np.nonzero(alive)[0]
-        if idx.size == 0:
-            break
-        p = first if ply % 2 == 0 else second
-        engine.load_weights_conv(p.weights) if np.size(p.weights) == 12412 else engine.load_weights(p.weights)
-        res = engine.mcts_search(p.mcts_cfg, my[idx], op[idx], p.explores, action_selection=int(p.action))
-        out["moves"][idx, ply] = res["best_action"]
-        nmy, nop, over, w = match.step(my[idx], op[idx], res["best_action"])
-        my[idx], op[idx] = nmy, nop
-        out["plies"][idx] += 1
-        first_moved = ply % 2 == 0
-        out["rewards"][idx[over & w]] = 1.0 if first_moved else -1.0
-        done = idx[over]
-        # (after the move the mover's stones are `op`)
-        out["final_bb"][done, 0] = op[done] if first_moved else my[done]
-        out["final_bb"][done, 1] = my[done] if first_moved else op[done]
-        alive[done] = False
+    own = engine.network_arithmetic()[0] if any(getattr(p, "arithmetic", None) for p in (first, second)) else None
+    try:
+        for ply in range(63):
+            idx = np.nonzero(alive)[0]
+            if idx.size == 0:
+                break
+            p = first if ply % 2 == 0 else second
+            if own is not None:
+                # (switched to f32 for the load: a load in f16x2 builds an image the next switch may throw away)
+                engine.set_network_arithmetic("f32")
+            engine.load_weights_conv(p.weights) if np.size(p.weights) == 12412 else engine.load_weights(p.weights)
+            if own is not None:
+                engine.set_network_arithmetic(getattr(p, "arithmetic", None) or own)
+            res = engine.mcts_search(p.mcts_cfg, my[idx], op[idx], p.explores, action_selection=int(p.action))
+            out["moves"][idx, ply] = res["best_action"]
+            nmy, nop, over, w = match.step(my[idx], op[idx], res["best_action"])
+            my[idx], op[idx] = nmy, nop
+            out["plies"][idx] += 1
+            first_moved = ply % 2 == 0
+            out["rewards"][idx[over & w]] = 1.0 if first_moved else -1.0
+            done = idx[over]
+            # (after the move the mover's stones are `op`)
+            out["final_bb"][done, 0] = op[done] if first_moved else my[done]
+            out["final_bb"][done, 1] = my[done] if first_moved else op[done]
+            alive[done] = False
+    finally:
+        if own is not None:
+            engine.set_network_arithmetic(own)
     return out

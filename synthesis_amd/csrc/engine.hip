@@ -495,23 +495,17 @@ static int launch_planned(syn_engine* h, const LaunchPlan& plan, EngineParams P)
     return SYN_OK;
 }
 
-static int launch_engine(syn_engine* h, const EngineParams& P, int jobs, int mode, bool count, bool prof) {
-    LaunchQuery q;
-    q.num_cus = h->num_cus;
-    q.slots = h->slots;
-    q.jobs = jobs;
-    q.cap = h->cap;
-    q.net_kind = h->net.kind;
-    // (syn_match_run's images are built in the engine's arithmetic)
-    const bool match_image = P.wimg != nullptr && (P.wimg == h->match.d_img[0] || P.wimg == h->match.d_img[1]);
-    q.f16 = h->net.f16x2() && (P.wimg == h->net.image() || match_image);
-    q.pool_trees = h->pool_trees;
-    q.mode = mode;
-    q.count = count;
-    q.prof = prof;
-    q.fpu = P.mcts.fpu;
-    q.noise = P.mcts.noise;
-    q.family = cfg_family(P.mcts);
+// `arith`: PLAN_ARITH_* of the image P.wimg points at (launch_plan.hpp). The engine's own calls leave the default; a match side passes
+// the arithmetic its image was built in, so an f32 engine launches the f16x2 kernels for an f16x2 side and the reverse.
+static int launch_engine(syn_engine* h, const EngineParams& P, int jobs, int mode, bool count, bool prof, int arith = PLAN_ARITH_ENGINE) {
+    LaunchEngine e;
+    e.num_cus = h->num_cus;
+    e.slots = h->slots;
+    e.cap = h->cap;
+    e.net_kind = h->net.kind;
+    e.f16 = h->net.f16x2();
+    e.pool_trees = h->pool_trees;
+    const LaunchQuery q = launch_query(e, arith, jobs, mode, count, prof, P.mcts.fpu, P.mcts.noise, cfg_family(P.mcts));
     return launch_planned(h, plan_launch(q, read_launch_knobs()), P);
 }
 
@@ -1447,18 +1441,79 @@ int syn_mcts_search_rollout(syn_engine* h, const syn_mcts_config* cfg, uint64_t 
     return mcts_search_impl(h, cfg, my_bb, op_bb, n, explores, action_selection, results, true, seed);
 }
 
+// ------------------------------------------------------------------------------------------------ the evaluator's baseline
+// FrozenMCTS over RolloutPolicy (frozen_kernel.cuh). The baseline's trees live in the engine's node pool, re-partitioned for a call:
+// every tree gets the record capacity the largest search of the call can need (1 + 9 nodes per visit), and the pool holds as many
+// trees at once as fit. syn_frozen_search_rollout and a match's baseline sides (syn_match_run_sides) share the partition, the checks
+// of the configuration and the launch.
+struct FrozenPartition {
+    size_t nodes_per_tree = 0;   // record capacity of one tree
+    size_t lanes_max = 0;        // trees the pool holds at that capacity
+};
+static size_t frozen_worst_records(int explores) { return 1 + 9 * ((size_t)explores + 1); }
+static int frozen_partition(syn_engine* h, size_t max_need, FrozenPartition& part) {
+    const size_t nodes_per_tree = (max_need + 7) & ~(size_t)7;
+    const size_t pool_records = (size_t)h->pool_slots * h->cap * 2;  // 16-byte records in the 32-byte-per-node pool
+    if (max_need > 0x1FFFFFu || nodes_per_tree > pool_records)
+        return fail(h, SYN_ERR_CAPACITY, "a baseline search of %zu explores needs up to %zu node records; the engine's pool holds %zu "
+                    "and a tree at most 2,097,151", (max_need - 1) / 9 - 1, max_need, pool_records);
+    part.nodes_per_tree = nodes_per_tree;
+    part.lanes_max = pool_records / nodes_per_tree;
+    return SYN_OK;
+}
+// the baseline panics on anything else (evaluator.rs:418-421, 429-436)
+static int check_frozen_config(syn_engine* h, const syn_mcts_config* cfg) {
+    if (cfg->exploration != SYN_EXPLORATION_UCT)
+        return fail(h, SYN_ERR_UNSUPPORTED, "FrozenMCTS supports Exploration::Uct only (evaluator.rs:429-436)");
+    if (cfg->fpu != SYN_FPU_CONST)
+        return fail(h, SYN_ERR_UNSUPPORTED, "FrozenMCTS supports Fpu::Const only (evaluator.rs:418-421)");
+    return SYN_OK;
+}
+// One launch over P.n_roots roots: the caller has filled the roots, seeds, stream positions, explores, results and n_roots (device
+// arrays); the pool, the partition, the descent logs (grown here), the configuration and the error word are filled in.
+static size_t frozen_lanes(const FrozenPartition& part, int n_roots) {
+    return part.lanes_max < (size_t)n_roots ? part.lanes_max : (size_t)n_roots;
+}
+// the descent logs of a launch over n_roots roots, grown before the call's first enqueue (the buffer never shrinks)
+static int ensure_frozen_path(syn_engine* h, const FrozenPartition& part, int n_roots) {
+    const size_t grid = (frozen_lanes(part, n_roots) + 63) / 64;
+    HIP_TRY(h, ensure_device_buffer(h->d_path, h->path_bytes, grid * 4096 * sizeof(uint32_t)));
+    return SYN_OK;
+}
+static int launch_frozen(syn_engine* h, const FrozenPartition& part, const syn_mcts_config* cfg, int action_selection, FrozenParams P) {
+    const size_t n_lanes = frozen_lanes(part, P.n_roots);
+    const int grid = (int)((n_lanes + 63) / 64);  // one wave per workgroup
+    if (const int rc = ensure_frozen_path(h, part, P.n_roots)) return rc;
+    P.pool = reinterpret_cast<uint4*>(h->d_stat);
+    P.nodes_per_tree = part.nodes_per_tree;
+    P.path = reinterpret_cast<uint32_t*>(h->d_path);
+    P.n_lanes = (int)n_lanes;
+    P.c = cfg->c;
+    P.fpu_value = cfg->fpu_value;
+    P.solve = cfg->solve ? 1 : 0;
+    P.action_selection = action_selection;
+    P.error = h->d_job_next + 8;
+    hipLaunchKernelGGL(frozen_rollout_kernel, dim3(grid), dim3(64), 0, h->stream, P);
+    HIP_TRY(h, hipGetLastError());
+    h->last_shape = 5; h->last_grid = grid; h->last_threads = 64;
+    return SYN_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ device-resident matches
-// syn_match_run (match_kernels.cuh): every game of the call is searched, stepped and retired on the device. Per ply the host enqueues
-// one MODE_SEARCH launch over the live games' roots with the mover's image, the advance kernel, the scan and the compaction, and reads
-// ONE word back: how many games go on. Nothing is uploaded inside the loop; the outputs come back once, after the last ply.
+// syn_match_run / syn_match_run_sides (match_kernels.cuh): every game of the call is searched, stepped and retired on the device. Per
+// ply the host enqueues the mover's search over the live games' roots — one MODE_SEARCH launch with the mover's image in the mover's
+// arithmetic, or one frozen_rollout_kernel launch on the re-partitioned pool for a baseline side — then the advance kernel, the scan
+// and the compaction, and reads ONE word back: how many games go on. Nothing is uploaded inside the loop; the outputs come back once,
+// after the last ply. Both kinds of search use the engine's node pool and alternate on one stream: nothing runs concurrently.
 // The searches never touch the policy cache (P.cache = nullptr): its entries are keyed by position alone and belong to the engine's own
 // network, so a match neither reads another network's evaluations nor leaves its own behind.
 struct MatchLayout {   // byte offsets into syn_engine::Match::d_buf, each section 256-byte aligned
-    size_t my[2], op[2], id[2];   // the live games, two sets: a ply's compaction reads one and writes the other
+    size_t my[2], op[2], id[2], seed[2], word[2];   // the live games, two sets: a ply's compaction reads one and writes the other
     size_t keep, dst, scan;       // survivor flags, their exclusive sum, the scan's temporary storage
-    size_t results;               // DevSearchResult per live job of the current ply
-    size_t rewards, plies, moves, final_bb;   // MatchOut, per game
-    size_t live;                  // the word the host reads per ply
+    size_t results;               // DevSearchResult or FrozenResult per live job of the current ply
+    size_t explores[2];           // a baseline side's explores per root (frozen_rollout_kernel takes them from an array): filled once per call
+    size_t rewards, plies, moves, final_bb, rng_words;   // MatchOut, per game
+    size_t live;                  // [0] the word the host reads per ply, [1] the advance kernel's stream-position flag
     size_t total;
 };
 static MatchLayout match_layout(size_t n, size_t scan_bytes) {
@@ -1469,11 +1524,14 @@ static MatchLayout match_layout(size_t n, size_t scan_bytes) {
         at += (bytes + 255) & ~(size_t)255;
         return o;
     };
-    for (int k = 0; k < 2; k++) { L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); }
+    for (int k = 0; k < 2; k++) {
+        L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); L.seed[k] = take(n * 8); L.word[k] = take(n * 8);
+    }
     L.keep = take(n * 4); L.dst = take(n * 4); L.scan = take(scan_bytes);
-    L.results = take(n * sizeof(DevSearchResult));
-    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16);
-    L.live = take(4);
+    L.results = take(n * (sizeof(DevSearchResult) > sizeof(FrozenResult) ? sizeof(DevSearchResult) : sizeof(FrozenResult)));
+    for (int k = 0; k < 2; k++) L.explores[k] = take(n * 4);
+    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16); L.rng_words = take(n * 8);
+    L.live = take(8);
     L.total = at;
     return L;
 }
@@ -1487,9 +1545,8 @@ static bool host_won(uint64_t bb) {
     return (d1 | d2 | hz | vt) != 0;
 }
 
-// one side of a match: its configuration must be one whose search is a function of the root alone
+// a network side of a match: its configuration must be one whose search is a function of the root alone
 static int check_match_player(syn_engine* h, const char* who, const syn_match_player* p, DevMctsCfg& m) {
-    if (!p) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", who);
     if (p->action != SYN_ACTION_Q && p->action != SYN_ACTION_NUM_VISITS)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player's action selection %d is unknown", who, p->action);
     if (p->mcts_cfg.fpu == SYN_FPU_NORMAL || p->mcts_cfg.fpu == SYN_FPU_FUNC || p->mcts_cfg.root_policy_noise == SYN_NOISE_DIRICHLET)
@@ -1503,29 +1560,64 @@ static int check_match_player(syn_engine* h, const char* who, const syn_match_pl
     return convert_mcts(h, &p->mcts_cfg, m);
 }
 
-int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
-                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
-                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+// One side of a match as the loop uses it: a network side's MODE_SEARCH parameters and the arithmetic of its image, or a baseline
+// side's partition of the pool.
+struct MatchSide {
+    bool baseline = false;
+    int arith = PLAN_ARITH_ENGINE;   // network: the image's arithmetic, carried to launch_engine with every ply
+    bool f16 = false;                // ... resolved against the engine's
+    EngineParams P;                  // network
+    FrozenPartition part;            // baseline
+    const syn_match_player* player = nullptr;
+};
+
+// ---- everything that can refuse a side, before anything of the engine or the device changes
+static int check_match_side(syn_engine* h, const char* who, const syn_match_side* s, bool have_seeds, MatchSide& out) {
+    if (!s) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", who);
+    out.player = &s->player;
+    if (s->kind == SYN_MATCH_SIDE_BASELINE) {
+        out.baseline = true;
+        const syn_match_player& p = s->player;
+        if (p.action != SYN_ACTION_Q && p.action != SYN_ACTION_NUM_VISITS)
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player's action selection %d is unknown", who, p.action);
+        if (const int rc = check_frozen_config(h, &p.mcts_cfg)) return rc;
+        if (p.explores < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player's explores must be >= 0", who);
+        if (!have_seeds)
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is a baseline side, whose playouts need seeds: seeds is NULL", who);
+        return frozen_partition(h, frozen_worst_records(p.explores), out.part);
+    }
+    if (s->kind != SYN_MATCH_SIDE_NETWORK)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s side's kind %d is unknown", who, s->kind);
+    if (s->arithmetic != SYN_MATCH_ARITH_ENGINE && s->arithmetic != SYN_MATCH_ARITH_F32 && s->arithmetic != SYN_MATCH_ARITH_F16X2)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s side's arithmetic %d is unknown", who, s->arithmetic);
+    static_assert(SYN_MATCH_ARITH_ENGINE == PLAN_ARITH_ENGINE && SYN_MATCH_ARITH_F32 == PLAN_ARITH_F32 && SYN_MATCH_ARITH_F16X2 == PLAN_ARITH_F16X2,
+                  "launch_plan.hpp restates the header's SYN_MATCH_ARITH_*");
+    out.arith = s->arithmetic;
+    out.f16 = plan_call_f16(h->net.f16x2(), s->arithmetic);
+    DevMctsCfg m{};
+    int rc = check_match_player(h, who, &s->player, m);
+    if (rc == SYN_OK) rc = check_blob(h, h->net.kind, s->blob, s->n_floats);
+    if (rc == SYN_OK && out.f16) rc = require_lane_cap(h, "the f16x2 arithmetic");
+    if (rc == SYN_OK) rc = common_params(h, out.P, s->player.explores, /*need_weights=*/false);
+    if (rc != SYN_OK) return rc;
+    out.P.mcts = m;
+    out.P.cache = nullptr;
+    out.P.roll.num_explores = s->player.explores;
+    out.P.action_selection = s->player.action;
+    return SYN_OK;
+}
+
+static int match_run_impl(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
+                          const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                          uint64_t* final_bb, uint64_t* rng_words) {
     if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
     // ---- everything that can refuse the call, before anything of the engine or the device changes
-    const syn_match_player* const players[2] = {first, second};
-    const float* const blobs[2] = {blob_first, blob_second};
+    const syn_match_side* const sides[2] = {first, second};
     const int kind = h->net.kind;
-    const bool f16x2 = h->net.f16x2();
-    EngineParams P[2];
-    for (int s = 0; s < 2; s++) {
-        DevMctsCfg m{};
-        int rc = check_match_player(h, s == 0 ? "first" : "second", players[s], m);
-        if (rc == SYN_OK) rc = check_blob(h, kind, blobs[s], n_floats);
-        if (rc == SYN_OK) rc = common_params(h, P[s], players[s]->explores, /*need_weights=*/false);
-        if (rc != SYN_OK) return rc;
-        P[s].mcts = m;
-        P[s].cache = nullptr;
-        P[s].roll.num_explores = players[s]->explores;
-        P[s].action_selection = players[s]->action;
-    }
+    MatchSide S[2];
+    for (int s = 0; s < 2; s++)
+        if (const int rc = check_match_side(h, s == 0 ? "first" : "second", sides[s], seeds != nullptr, S[s])) return rc;
     if (n_games == 0) return SYN_OK;
     for (int g = 0; g < n_games; g++) {
         if (!valid_root(start_my[g], start_op[g]))
@@ -1536,71 +1628,102 @@ int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_
     }
     HostImage im[2];
     for (int s = 0; s < 2; s++) {
-        const int rc = build_host_image(h, kind, blobs[s], f16x2, im[s]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
+        if (S[s].baseline) continue;
+        const int rc = build_host_image(h, kind, sides[s]->blob, S[s].f16, im[s]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
         if (rc != SYN_OK) return rc;
     }
-    // ---- the match's own device memory
-    HIP_TRY(h, hipSetDevice(h->device));
+    // ---- the match's own device memory (the entry point has selected the engine's device)
     const size_t n = (size_t)n_games;
     size_t scan_bytes = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, n_games, h->stream));
     const MatchLayout L = match_layout(n, scan_bytes);
     for (int s = 0; s < 2; s++)
-        if (!h->match.d_img[s]) HIP_TRY(h, hipMalloc(&h->match.d_img[s], NET_IMAGE_MAX_BYTES));
+        if (!S[s].baseline && !h->match.d_img[s]) HIP_TRY(h, hipMalloc(&h->match.d_img[s], NET_IMAGE_MAX_BYTES));
     HIP_TRY(h, ensure_device_buffer(h->match.d_buf, h->match.buf_bytes, L.total));
+    for (int s = 0; s < 2; s++)
+        if (S[s].baseline)
+            if (const int rc = ensure_frozen_path(h, S[s].part, n_games)) return rc;
     unsigned char* const base = h->match.d_buf;
     const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
-    unsigned long long* const d_my[2] = {u64_at(L.my[0]), u64_at(L.my[1])};
-    unsigned long long* const d_op[2] = {u64_at(L.op[0]), u64_at(L.op[1])};
-    int* const d_id[2] = {reinterpret_cast<int*>(base + L.id[0]), reinterpret_cast<int*>(base + L.id[1])};
+    MatchLive live_set[2];
+    for (int k = 0; k < 2; k++)
+        live_set[k] = MatchLive{u64_at(L.my[k]), u64_at(L.op[k]), reinterpret_cast<int*>(base + L.id[k]), u64_at(L.seed[k]), u64_at(L.word[k])};
     unsigned* const d_keep = reinterpret_cast<unsigned*>(base + L.keep);
     unsigned* const d_dst = reinterpret_cast<unsigned*>(base + L.dst);
-    DevSearchResult* const d_res = reinterpret_cast<DevSearchResult*>(base + L.results);
+    void* const d_res = base + L.results;
+    int* const d_expl[2] = {reinterpret_cast<int*>(base + L.explores[0]), reinterpret_cast<int*>(base + L.explores[1])};
     int* const d_live = reinterpret_cast<int*>(base + L.live);
+    int* const d_stream_error = d_live + 1;
     MatchOut out;
     out.rewards = reinterpret_cast<float*>(base + L.rewards);
     out.plies = reinterpret_cast<int*>(base + L.plies);
     out.moves = base + L.moves;
     out.final_bb = u64_at(L.final_bb);
+    out.rng_words = u64_at(L.rng_words);
 
     CallScope scope(h, n_games);
     std::vector<int> iota(n);
     for (size_t g = 0; g < n; g++) iota[g] = (int)g;
+    std::vector<int> expl[2];
     for (int s = 0; s < 2; s++) {
+        if (S[s].baseline) {
+            expl[s].assign(n, S[s].player->explores);
+            HIP_TRY(h, hipMemcpyAsync(d_expl[s], expl[s].data(), n * 4, hipMemcpyHostToDevice, h->stream));
+            continue;
+        }
         const int rc = enqueue_image_upload(h, im[s], h->match.d_img[s]);
         if (rc != SYN_OK) return rc;
-        P[s].wimg = static_cast<const float*>(h->match.d_img[s]);
+        S[s].P.wimg = static_cast<const float*>(h->match.d_img[s]);
     }
-    HIP_TRY(h, hipMemcpyAsync(d_my[0], start_my, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_op[0], start_op, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_id[0], iota.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].my, start_my, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].op, start_op, n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].id, iota.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+    if (seeds) HIP_TRY(h, hipMemcpyAsync(live_set[0].seed, seeds, n * 8, hipMemcpyHostToDevice, h->stream));
+    else HIP_TRY(h, hipMemsetAsync(live_set[0].seed, 0, n * 8, h->stream));
+    HIP_TRY(h, hipMemsetAsync(live_set[0].word, 0, n * 8, h->stream));   // every game's generator starts at output word 0
     HIP_TRY(h, hipMemsetAsync(base + L.rewards, 0, L.moves - L.rewards, h->stream));   // rewards and plies
     HIP_TRY(h, hipMemsetAsync(out.moves, MATCH_NO_MOVE, n * MATCH_T, h->stream));
     HIP_TRY(h, hipMemsetAsync(out.final_bb, 0, n * 16, h->stream));
+    HIP_TRY(h, hipMemsetAsync(out.rng_words, 0, n * 8, h->stream));
+    HIP_TRY(h, hipMemsetAsync(d_live, 0, 8, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the last upload from host memory: the loop below only launches and reads one word
 
     float kernel_ms = 0.0f;
     int launches = 0, live = n_games, ply = 0;
     for (; live > 0 && ply < MATCH_T; ply++) {
         const int s = ply & 1, cur = ply & 1, nxt = cur ^ 1;
+        const MatchLive& A = live_set[cur];
         // (a syn_cancel's word does not survive the next ply's reset: the loop itself stops at the first ply that ends after it)
         HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));
         if (ply == 0) HIP_TRY(h, scope.armed());
-        // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
-        HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(DevSearchResult), h->stream));
-        EngineParams Q = P[s];
-        Q.n_jobs = live;
-        Q.in_my = d_my[cur];
-        Q.in_op = d_op[cur];
-        Q.results = d_res;
-        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-        if (const int rc = launch_engine(h, Q, live, MODE_SEARCH, false, false)) return rc;
         const dim3 grid((unsigned)((live + 255) / 256)), block(256);
-        hipLaunchKernelGGL(match_advance_kernel, grid, block, 0, h->stream, d_res, live, ply, d_my[cur], d_op[cur], d_id[cur], d_keep, out);
+        if (S[s].baseline) {
+            HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(FrozenResult), h->stream));
+            FrozenParams F{};
+            F.in_my = A.my; F.in_op = A.op; F.seeds = A.seed; F.rng_words = A.word; F.explores = d_expl[s];
+            F.n_roots = live;
+            F.results = static_cast<FrozenResult*>(d_res);
+            HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+            if (const int rc = launch_frozen(h, S[s].part, &S[s].player->mcts_cfg, S[s].player->action, F)) return rc;
+            hipLaunchKernelGGL(match_advance_kernel<FrozenResult>, grid, block, 0, h->stream, static_cast<const FrozenResult*>(d_res), live, ply,
+                               A.my, A.op, A.id, A.word, d_keep, d_stream_error, out);
+        } else {
+            // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
+            HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(DevSearchResult), h->stream));
+            EngineParams Q = S[s].P;
+            Q.n_jobs = live;
+            Q.in_my = A.my;
+            Q.in_op = A.op;
+            Q.results = static_cast<DevSearchResult*>(d_res);
+            HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+            if (const int rc = launch_engine(h, Q, live, MODE_SEARCH, false, false, S[s].arith)) return rc;
+            hipLaunchKernelGGL(match_advance_kernel<DevSearchResult>, grid, block, 0, h->stream, static_cast<const DevSearchResult*>(d_res), live,
+                               ply, A.my, A.op, A.id, A.word, d_keep, d_stream_error, out);
+        }
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(base + L.scan, scan_bytes, d_keep, d_dst, live, h->stream));
-        hipLaunchKernelGGL(match_compact_kernel, grid, block, 0, h->stream, d_keep, d_dst, live, d_my[cur], d_op[cur], d_id[cur], d_my[nxt],
-                           d_op[nxt], d_id[nxt], Q.error, d_live);
+        hipLaunchKernelGGL(match_compact_kernel, grid, block, 0, h->stream, d_keep, d_dst, live, A, live_set[nxt], h->d_job_next + 8,
+                           d_stream_error, d_live);
         HIP_TRY(h, hipGetLastError());
         HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
         HIP_TRY(h, hipMemcpyAsync(h->h_pin + 12, d_live, 4, hipMemcpyDeviceToHost, h->stream));
@@ -1614,6 +1737,10 @@ int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_
         if (scope.cancelled())
             return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the match: the outputs are unspecified", ply);
         const int now = h->h_pin[12];
+        if (now == -MATCH_ERR_STREAM)
+            return fail(h, SYN_ERR_CAPACITY, "a game's rollout generator passed output word 0xC0000000 at ply %d of the match: the baseline "
+                                             "search supports no longer stream", ply);
+        if (now < 0 && S[s].baseline) return fail(h, SYN_ERR_CAPACITY, "a baseline tree ran out of node records");
         if (now == -2)
             return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)",
                         h->cap / 4, h->max_explores);
@@ -1626,9 +1753,36 @@ int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_
     HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
     if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
     if (final_bb) HIP_TRY(h, hipMemcpyAsync(final_bb, out.final_bb, n * 16, hipMemcpyDeviceToHost, h->stream));
+    if (rng_words) HIP_TRY(h, hipMemcpyAsync(rng_words, out.rng_words, n * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->last_cache_hits = h->last_cache_misses = 0;   // a match does not use the policy cache
     return SYN_OK;
+}
+
+int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
+                        const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                        uint64_t* final_bb, uint64_t* rng_words) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine: the refusals come first in match_run_impl)
+    return match_run_impl(h, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words);
+}
+
+// two network sides in the engine's arithmetic
+int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
+                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
+                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
+    const syn_match_player* const players[2] = {first, second};
+    const float* const blobs[2] = {blob_first, blob_second};
+    syn_match_side sides[2];
+    for (int s = 0; s < 2; s++) {
+        if (!players[s]) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", s == 0 ? "first" : "second");
+        sides[s] = syn_match_side{SYN_MATCH_SIDE_NETWORK, SYN_MATCH_ARITH_ENGINE, *players[s], blobs[s], n_floats};
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return match_run_impl(h, &sides[0], &sides[1], start_my, start_op, nullptr, n_games, rewards, plies, moves, final_bb, nullptr);
 }
 
 // evaluator.rs:308-319 FrozenMCTS::exploit over RolloutPolicy for n roots (frozen_kernel.cuh)
@@ -1640,31 +1794,20 @@ int syn_frozen_search_rollout(syn_engine* h, const syn_mcts_config* cfg, const u
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_frozen_search_rollout");
     if (action_selection != SYN_ACTION_Q && action_selection != SYN_ACTION_NUM_VISITS)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown action selection %d", action_selection);
-    // the baseline panics on anything else (evaluator.rs:418-421, 429-436)
-    if (cfg->exploration != SYN_EXPLORATION_UCT)
-        return fail(h, SYN_ERR_UNSUPPORTED, "FrozenMCTS supports Exploration::Uct only (evaluator.rs:429-436)");
-    if (cfg->fpu != SYN_FPU_CONST)
-        return fail(h, SYN_ERR_UNSUPPORTED, "FrozenMCTS supports Fpu::Const only (evaluator.rs:418-421)");
+    if (const int rc = check_frozen_config(h, cfg)) return rc;
     if (n == 0) return SYN_OK;
-    // The baseline's trees live in the engine's node pool, re-partitioned for this call: every tree gets the record capacity
-    // the largest search of the batch can need (1 + 9 nodes per visit), and the pool holds as many trees at once as fit.
     size_t max_need = 0;
     for (int i = 0; i < n; i++) {
         if (!valid_root(my_bb[i], op_bb[i]))
             return fail(h, SYN_ERR_INVALID_ARGUMENT, "root %d is not a searchable Connect4 position", i);
         if (explores[i] < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "explores[%d] must be >= 0", i);
-        const size_t worst = 1 + 9 * ((size_t)explores[i] + 1);
+        const size_t worst = frozen_worst_records(explores[i]);
         if (worst > max_need) max_need = worst;
-        if (rng_words[i] > 0xC0000000ull)
+        if (rng_words[i] > MATCH_WORD_LIMIT)
             return fail(h, SYN_ERR_INVALID_ARGUMENT, "rng_words[%d] is beyond the supported stream length", i);
     }
-    const size_t nodes_per_tree = (max_need + 7) & ~(size_t)7;
-    const size_t pool_records = (size_t)h->pool_slots * h->cap * 2;  // 16-byte records in the 32-byte-per-node pool
-    if (max_need > 0x1FFFFFu || nodes_per_tree > pool_records)
-        return fail(h, SYN_ERR_CAPACITY, "a baseline search of %zu explores needs up to %zu node records; the engine's pool holds %zu "
-                    "and a tree at most 2,097,151", (max_need - 1) / 9 - 1, max_need, pool_records);
-    size_t n_lanes = pool_records / nodes_per_tree;
-    if (n_lanes > (size_t)n) n_lanes = (size_t)n;
+    FrozenPartition part;
+    if (const int rc = frozen_partition(h, max_need, part)) return rc;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nb = (size_t)n;
     int rc = ensure_scratch(h, nb * (8 * 4 + 4 + sizeof(FrozenResult)) + 256);
@@ -1675,15 +1818,7 @@ int syn_frozen_search_rollout(syn_engine* h, const syn_mcts_config* cfg, const u
     unsigned long long* d_words = d_seed + nb;
     FrozenResult* d_res = reinterpret_cast<FrozenResult*>(d_words + nb);
     int* d_expl = reinterpret_cast<int*>(d_res + nb);
-    const int grid = (int)((n_lanes + 63) / 64);  // one wave per workgroup
-    const size_t need_path = (size_t)grid * 4096 * sizeof(uint32_t);
-    if (need_path > h->path_bytes) {
-        if (h->d_path) (void)hipFree(h->d_path);
-        h->d_path = nullptr;
-        h->path_bytes = 0;
-        HIP_TRY(h, hipMalloc(&h->d_path, need_path));
-        h->path_bytes = need_path;
-    }
+    if (const int prc = ensure_frozen_path(h, part, n)) return prc;
     HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, nb * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, nb * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(d_seed, seeds, nb * 8, hipMemcpyHostToDevice, h->stream));
@@ -1693,24 +1828,13 @@ int syn_frozen_search_rollout(syn_engine* h, const syn_mcts_config* cfg, const u
     HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));
     HIP_TRY(h, scope.armed());  // (this kernel takes its roots in a grid-stride loop, not from the job counter: a syn_cancel
                                 //  during the call is accepted and has no effect — every root is searched)
-    FrozenParams P;
-    P.pool = reinterpret_cast<uint4*>(h->d_stat);
-    P.nodes_per_tree = nodes_per_tree;
-    P.path = reinterpret_cast<uint32_t*>(h->d_path);
+    FrozenParams P{};
     P.in_my = d_my; P.in_op = d_op; P.seeds = d_seed; P.rng_words = d_words; P.explores = d_expl;
     P.n_roots = n;
-    P.n_lanes = (int)n_lanes;
-    P.c = cfg->c;
-    P.fpu_value = cfg->fpu_value;
-    P.solve = cfg->solve ? 1 : 0;
-    P.action_selection = action_selection;
     P.results = d_res;
-    P.error = h->d_job_next + 8;
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(frozen_rollout_kernel, dim3(grid), dim3(64), 0, h->stream, P);
-    HIP_TRY(h, hipGetLastError());
+    if (const int lrc = launch_frozen(h, part, cfg, action_selection, P)) return lrc;
     HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-    h->last_shape = 5; h->last_grid = grid; h->last_threads = 64;
     static_assert(sizeof(FrozenResult) == sizeof(syn_frozen_result), "device and ABI result records must match");
     int kerr = 0;
     HIP_TRY(h, hipMemcpyAsync(results, d_res, nb * sizeof(FrozenResult), hipMemcpyDeviceToHost, h->stream));

@@ -44,6 +44,43 @@ struct LaunchQuery {
     int family = 0;           // mcts.cuh cfg_family: 1 parity (= cfg_is_fast), 2 the reference's Fpu::Func configuration, 0 anything else
 };
 
+// The arithmetic of the network image ONE call evaluates. A call of the engine's own network leaves PLAN_ARITH_ENGINE: the engine's
+// current arithmetic. A match side (syn_match_run_sides) whose blob was built into an image of its own says which kind that image is,
+// whatever the engine is in: the kernel family follows the image, never the engine.
+constexpr int PLAN_ARITH_ENGINE = 0, PLAN_ARITH_F32 = 1, PLAN_ARITH_F16X2 = 2;
+inline bool plan_call_f16(bool engine_f16, int call_arith) {
+    return call_arith == PLAN_ARITH_F16X2 || (call_arith != PLAN_ARITH_F32 && engine_f16);
+}
+
+// What of an engine the selection reads (engine.hip fills it from syn_engine) ...
+struct LaunchEngine {
+    int num_cus = 256;
+    int slots = 0;
+    unsigned cap = 0;
+    int net_kind = 0;
+    bool f16 = false;     // the engine's own network arithmetic is f16x2
+    int pool_trees = 0;
+};
+// ... and the query of one call on it: `call_arith` = PLAN_ARITH_* of the image the call's EngineParams::wimg points at
+inline LaunchQuery launch_query(const LaunchEngine& e, int call_arith, int jobs, int mode, bool count, bool prof, int fpu, int noise,
+                                int family) {
+    LaunchQuery q;
+    q.num_cus = e.num_cus;
+    q.slots = e.slots;
+    q.jobs = jobs;
+    q.cap = e.cap;
+    q.net_kind = e.net_kind;
+    q.f16 = plan_call_f16(e.f16, call_arith);
+    q.pool_trees = e.pool_trees;
+    q.mode = mode;
+    q.count = count;
+    q.prof = prof;
+    q.fpu = fpu;
+    q.noise = noise;
+    q.family = family;
+    return q;
+}
+
 struct LaunchPlan {
     bool error = false;   // cap > LANE_MAX_CAP for a configuration that only the lane-per-tree kernels play
     int shape = 0;        // as syn_last_launch_shape reports it: 1 / 2 row-per-tree (= workgroups per CU), 3 quads, 4 lanes, 5 producer/consumer,

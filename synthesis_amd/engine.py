@@ -27,7 +27,7 @@ ABI_SYMBOLS = [
     "syn_replay_append_device", "syn_replay_append", "syn_replay_keep_games_from", "syn_replay_read",
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
-    "syn_match_run",
+    "syn_match_run", "syn_match_run_sides",
 ]
 
 
@@ -52,6 +52,21 @@ class CSearchResult(C.Structure):  # struct syn_search_result
 
 class CMatchPlayer(C.Structure):  # struct syn_match_player
     _fields_ = [("explores", C.c_int32), ("action", C.c_int32), ("mcts_cfg", CMctsConfig)]
+
+
+class CMatchSide(C.Structure):  # struct syn_match_side
+    _fields_ = [("kind", C.c_int32), ("arithmetic", C.c_int32), ("player", CMatchPlayer), ("blob", C.c_void_p), ("n_floats", C.c_size_t)]
+
+
+MATCH_SIDE_KINDS = {"network": 0, "baseline": 1}             # SYN_MATCH_SIDE_*
+MATCH_ARITHMETICS = {None: 0, "f32": 1, "f16x2": 2}          # SYN_MATCH_ARITH_*; None = the engine's
+
+
+def decode_match_side(side):
+    """(kind, arithmetic) names of a CMatchSide: a zero-filled one is ("network", None), a network side in the engine's arithmetic"""
+    kinds = {v: k for k, v in MATCH_SIDE_KINDS.items()}
+    ariths = {v: k for k, v in MATCH_ARITHMETICS.items()}
+    return kinds[side.kind], ariths[side.arithmetic]
 
 
 class CF16x2Plan(C.Structure):  # struct syn_f16x2_plan
@@ -146,6 +161,8 @@ def load_library():
                                              [C.c_void_p] * 8
     lib.syn_match_run.argtypes = [C.c_void_p, C.POINTER(CMatchPlayer), C.POINTER(CMatchPlayer), C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.syn_match_run_sides.argtypes = [C.c_void_p, C.POINTER(CMatchSide), C.POINTER(CMatchSide), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.syn_progress.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_cancel.argtypes = [C.c_void_p]
     lib.syn_trainer_set_precision.argtypes = [C.c_void_p, C.c_int]
@@ -466,6 +483,56 @@ class Engine:
                    final_bb=np.zeros((n, 2), np.uint64))
         self._check(self._lib.syn_match_run(self._h, C.byref(players[0]), C.byref(players[1]), _p(b1), _p(b2), b1.size, _p(my), _p(op), n,
                                             _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]), _p(out["final_bb"])))
+        return out
+
+    def match_run_sides(self, first, second, start_my, start_op, seeds=None):
+        """syn_match_run_sides: match_run with a description per side. A side is anything with .explores, .action, .mcts_cfg, .frozen,
+        .weights and an optional .arithmetic (a match.Player):
+          .frozen True   the evaluator's baseline, FrozenMCTS over RolloutPolicy (match.vanilla_player). Game g's playouts come from
+                         StdRng::seed_from_u64(seeds[g]), one generator per game for the whole game, shared by two baseline sides.
+          .frozen False  a network side: .weights is its blob (of the engine's network kind), .arithmetic None (the engine's), "f32" or
+                         "f16x2" — the two sides may differ from each other and from the engine.
+        `seeds` is needed when a side is a baseline. Returns match_run's dict plus "rng_words" [n]: each game's stream position at its
+        end. The engine's own network, arithmetic and policy cache are untouched."""
+        sides, keep = [], []
+        for p in (first, second):
+            side, blob = self.match_side(p)
+            sides.append(side)
+            keep.append(blob)   # (the struct holds a raw pointer into it)
+        return self.match_run_sides_c(sides[0], sides[1], start_my, start_op, seeds)
+
+    @staticmethod
+    def match_side(p):
+        """(CMatchSide, the array its blob pointer points into or None) of a player object"""
+        arithmetic = getattr(p, "arithmetic", None)
+        if arithmetic not in MATCH_ARITHMETICS:
+            raise ValueError(f"a side's arithmetic must be None, 'f32' or 'f16x2', got {arithmetic!r}")
+        player = CMatchPlayer(int(p.explores), int(p.action), p.mcts_cfg.to_c())
+        if getattr(p, "frozen", False):
+            return CMatchSide(MATCH_SIDE_KINDS["baseline"], 0, player, None, 0), None
+        if getattr(p, "rollout", False):
+            raise ValueError("a rollout_player (the self-play MCTS tree over RolloutPolicy) is not a side of a device match: its playout "
+                             "seed is keyed by ply x batch size in play_match, so it stays with the host path")
+        if getattr(p, "weights", None) is None:
+            raise ValueError("a network side of a device match needs its own .weights (the engine cannot hand back the blob it holds)")
+        blob = np.ascontiguousarray(p.weights, dtype=np.float32).ravel()
+        return CMatchSide(MATCH_SIDE_KINDS["network"], MATCH_ARITHMETICS[arithmetic], player, blob.ctypes.data, blob.size), blob
+
+    def match_run_sides_c(self, side_first, side_second, start_my, start_op, seeds=None):
+        """match_run_sides on two CMatchSide structs as they are (the blobs they point to must stay alive for the call)"""
+        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
+        if my.size != op.size:
+            raise ValueError("start_my and start_op must have the same length")
+        n = int(my.size)
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n,)))
+        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
+                   final_bb=np.zeros((n, 2), np.uint64), rng_words=np.zeros(n, np.uint64))
+        self._check(self._lib.syn_match_run_sides(self._h, C.byref(side_first), C.byref(side_second), _p(my), _p(op), _p(sd), n,
+                                                  _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]), _p(out["final_bb"]),
+                                                  _p(out["rng_words"])))
         return out
 
     @staticmethod

@@ -62,6 +62,8 @@ class Player:
     frozen: bool = False           # True: the evaluator's FrozenMCTS baseline over RolloutPolicy (evaluator.rs:230-534)
     weights: object = None         # network players: this player's own weight blob (None: whatever the engine holds) — lets
                                    # two different checkpoints meet on one engine (eval_against_old, evaluator.rs:129-160)
+    arithmetic: str = None         # network players on the device path (play_match_device, Engine.match_run_sides, arena.compare):
+                                   # None = the engine's arithmetic, "f32" or "f16x2" = this side's own
 
 
 def rollout_player(explores, name=None):
@@ -80,17 +82,22 @@ def vanilla_player(explores, name=None, action=ActionSelection.Q):
                   action, rollout=True, frozen=True)
 
 
-def play_match(engine, first: Player, second: Player, n_games, seed=0, seeds=None, record=None):
+def play_match(engine, first: Player, second: Player, n_games=None, seed=0, seeds=None, record=None, starts=None):
     """n_games from the empty board, `first` moving first. Returns rewards for `first` per game: +1 win, 0 draw, -1 loss
     (game.reward(first_player), evaluator.rs:160) and the number of plies. Game g's rollout generator is
     StdRng::seed_from_u64(seeds[g]) (default seed + g), shared by both sides and alive for the whole game when the players
-    are vanilla players (evaluator.rs:171-172, 207-208). `record`: optional dict that receives "moves" [n_games, 63]."""
+    are vanilla players (evaluator.rs:171-172, 207-208). `record`: optional dict that receives "moves" [n_games, 63] and
+    "rng_words" [n_games]. `starts` = (my, op): the games start there instead, `first` to move (n_games may then be left out)."""
     net = [p for p in (first, second) if not p.frozen and not p.rollout]
     if len(net) == 2 and (net[0].weights is None) != (net[1].weights is None):
         # the engine cannot hand back the weights it currently holds, so after the first swap a `weights=None` player would
         # silently search with its opponent's network
         raise ValueError("play_match: give both network players explicit weights, or neither (both then use the engine's network)")
-    my = np.zeros(n_games, np.uint64); op = np.zeros(n_games, np.uint64)
+    if starts is None:
+        my = np.zeros(n_games, np.uint64); op = np.zeros(n_games, np.uint64)
+    else:
+        my = np.array(starts[0], np.uint64).ravel(); op = np.array(starts[1], np.uint64).ravel()
+        n_games = int(my.size)
     alive = np.ones(n_games, bool)
     reward = np.zeros(n_games, np.float32)
     plies = np.zeros(n_games, np.int32)
@@ -126,6 +133,34 @@ def play_match(engine, first: Player, second: Player, n_games, seed=0, seeds=Non
     return reward, plies
 
 
+def play_match_device(engine, first: Player, second: Player, n_games=None, seed=0, seeds=None, starts=None, record=None):
+    """play_match without the host between the plies: ONE Engine.match_run_sides call plays every game on the device — searches, steps
+    and, for vanilla players, each game's rollout generator (StdRng::seed_from_u64(seeds[g]), default seed + g, alive for the whole
+    game and shared by two vanilla players). Same return value and `record` keys as play_match; games from the empty board, or from
+    `starts` = (my, op) with `first` to move. Network players need explicit .weights and may each name an .arithmetic; the engine's own
+    network is untouched. A rollout_player (rollout=True, frozen=False) is refused: play_match keys its playout seed by ply x batch
+    size (seed + ply * n_games), which no per-game state on the device reproduces, so those matches stay with the host path."""
+    for p in (first, second):
+        if p.rollout and not p.frozen:
+            raise ValueError(f"play_match_device: {p.name} is a rollout_player: its playout seed is keyed by ply x batch size in play_match "
+                             "(seed + ply * n_games), so it stays with the host path (play_match)")
+    if starts is None:
+        if n_games is None:
+            raise ValueError("play_match_device: give n_games or starts")
+        my = np.zeros(int(n_games), np.uint64); op = np.zeros(int(n_games), np.uint64)
+    else:
+        my = np.ascontiguousarray(starts[0], np.uint64).ravel(); op = np.ascontiguousarray(starts[1], np.uint64).ravel()
+        if n_games is not None and int(n_games) != my.size:
+            raise ValueError("play_match_device: n_games and starts disagree")
+    n = int(my.size)
+    seeds = (np.uint64(seed) + np.arange(n, dtype=np.uint64)) if seeds is None else np.asarray(seeds, np.uint64)
+    out = engine.match_run_sides(first, second, my, op, seeds=seeds)
+    if record is not None:
+        record["moves"] = out["moves"]
+        record["rng_words"] = out["rng_words"]
+    return out["rewards"], out["plies"]
+
+
 def pgn_records(white_name, black_name, white_rewards):
     """add_pgn_result (synthesis/src/utils.rs:31-52) for a batch of games: the text the evaluator appends to results.pgn,
     which its rating tool (the external bayeselo binary, utils.rs:54-72) reads."""
@@ -155,13 +190,15 @@ class EvaluationConfig:
     rollout_num_explores: tuple = (800, 1600, 3200)
 
 
-def evaluation_round(engine, cfg: EvaluationConfig, i_iter, model_name, model_weights, best_k):
+def evaluation_round(engine, cfg: EvaluationConfig, i_iter, model_name, model_weights, best_k, device=False):
     """One pass of the evaluator's loop body (evaluator.rs:22-99) for model `i_iter`, every search on the device and all
     pairings of a kind batched into one lockstep match each. Returns the PGN text the reference appends to results.pgn, in its
     order: (1) baseline i_iter % n against every other baseline, seed i_iter (mcts_vs_mcts, :24-41); (2) the model against
     every baseline, seeds 0..num_games_against_rollout-1, as first and as second player (:63-86); (3) the model against each
     kept older model, both colours (eval_against_old, :89-95). `best_k`: list of (name, weights). Ratings and the choice of
-    which models to keep are the external bayeselo's job in the reference (utils.rs:54-72) and stay with the caller."""
+    which models to keep are the external bayeselo's job in the reference (utils.rs:54-72) and stay with the caller.
+    device=True: every match through play_match_device (one device-resident call each) instead of play_match: the same text."""
+    run = play_match_device if device else play_match
     pgn = []
     ladder = list(cfg.rollout_num_explores)
     i = i_iter % len(ladder)
@@ -169,22 +206,22 @@ def evaluation_round(engine, cfg: EvaluationConfig, i_iter, model_name, model_we
         if i == j:
             continue
         a, b = vanilla_player(ladder[i], action=cfg.rollout_action), vanilla_player(ladder[j], action=cfg.rollout_action)
-        r, _ = play_match(engine, a, b, 1, seeds=[i_iter])
+        r, _ = run(engine, a, b, 1, seeds=[i_iter])
         pgn.append(pgn_records(a.name, b.name, r))
     me = Player(model_name, cfg.policy_num_explores, cfg.policy_mcts_cfg, cfg.policy_action, weights=model_weights)
     seeds = np.arange(cfg.num_games_against_rollout, dtype=np.uint64)
     for ex in ladder:
         opp = vanilla_player(ex, action=cfg.rollout_action)
-        r1, _ = play_match(engine, me, opp, seeds.size, seeds=seeds)
-        r2, _ = play_match(engine, opp, me, seeds.size, seeds=seeds)
+        r1, _ = run(engine, me, opp, seeds.size, seeds=seeds)
+        r2, _ = run(engine, opp, me, seeds.size, seeds=seeds)
         for g in range(seeds.size):  # the reference interleaves the two colours per seed
             pgn.append(pgn_records(me.name, opp.name, r1[g:g + 1]))
             pgn.append(pgn_records(opp.name, me.name, r2[g:g + 1]))
     for prev_name, prev_w in best_k:
         old = Player(prev_name, cfg.policy_num_explores, cfg.policy_mcts_cfg, cfg.policy_action, weights=prev_w)
-        r, _ = play_match(engine, me, old, 1)
+        r, _ = run(engine, me, old, 1)
         pgn.append(pgn_records(me.name, old.name, r))
-        r, _ = play_match(engine, old, me, 1)
+        r, _ = run(engine, old, me, 1)
         pgn.append(pgn_records(old.name, me.name, r))
     return "".join(pgn)
 

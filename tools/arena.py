@@ -9,9 +9,12 @@ count) and the same explores, so the games are deterministic and the spread come
 side, the score S = mean of the per-opening pair scores, its standard error over openings, and the Elo difference of S and of
 S -/+ 1.96 SE (clipped at scores 0.001 / 0.999: +-1200 means "off the scale", not a measurement).
 
-A match runs both sides in ONE engine's arithmetic, so a checkpoint in f32 cannot meet itself in f16x2 here. What two engines can say
-is whether the arithmetic changes the measurement: --same-games-in f16x2 plays the same match a second time on an engine in that
-arithmetic and reports its W/D/L and score beside the first, with the number of pair scores and game lengths that differ."""
+--arith-a / --arith-b give a side an arithmetic of its own, whatever the engine is in (Engine.match_run_sides): the same file twice with
+--arith-a f32 --arith-b f16x2 is one checkpoint against itself in the faster arithmetic — what that arithmetic costs in playing
+strength. --baseline N plays A against the evaluator's VanillaMCTS<N> (FrozenMCTS over RolloutPolicy, the reference's absolute scale)
+on the same openings, both colours, opening o on StdRng::seed_from_u64(seed + o); B is then not read (pass A again). The same JSON line.
+--same-games-in f16x2 plays the same match a second time on an engine in that arithmetic and reports its W/D/L and score beside the
+first, with the number of pair scores and game lengths that differ."""
 import argparse
 import json
 import os
@@ -31,6 +34,9 @@ def main():
     ap.add_argument("--explores", type=int, default=800)
     ap.add_argument("--net", choices=("mlp", "conv"), default="mlp")
     ap.add_argument("--arithmetic", choices=("f32", "f16x2"), default="f32")
+    ap.add_argument("--arith-a", choices=("f32", "f16x2"), default=None, help="A's own arithmetic (default: the engine's, --arithmetic)")
+    ap.add_argument("--arith-b", choices=("f32", "f16x2"), default=None, help="B's own arithmetic")
+    ap.add_argument("--baseline", type=int, default=0, metavar="N", help="play A against VanillaMCTS<N> instead of B")
     ap.add_argument("--same-games-in", choices=("f32", "f16x2"), default=None,
                     help="also play the match in this arithmetic (a second engine) and count the games that differ")
     ap.add_argument("--seed", type=int, default=0)
@@ -46,7 +52,9 @@ def main():
     blob_a = np.load(args.a).astype(np.float32).ravel()
     blob_b = np.load(args.b).astype(np.float32).ravel()
     openings = arena.random_openings(args.openings, args.opening_plies, args.seed)
-    player = match.Player("net", args.explores, sa.parity_mcts_config())
+    player_a = match.Player("net", args.explores, sa.parity_mcts_config(), arithmetic=args.arith_a)
+    player_b = match.Player("net", args.explores, sa.parity_mcts_config(), arithmetic=args.arith_b)
+    seeds = np.uint64(args.seed) + np.arange(args.openings, dtype=np.uint64)
     slots = args.concurrent or max(16, min(args.openings, 65536))
 
     def run(arithmetic):
@@ -54,11 +62,16 @@ def main():
             (eng.load_weights_conv if args.net == "conv" else eng.load_weights)(blob_a)   # selects the engine's network kind
             eng.set_network_arithmetic(arithmetic)
             t0 = time.perf_counter()
-            r = arena.compare(eng, blob_a, blob_b, openings, player, player)
+            if args.baseline:
+                r = arena.compare_baseline(eng, blob_a, openings, player_a, match.vanilla_player(args.baseline), seeds)
+            else:
+                r = arena.compare(eng, blob_a, blob_b, openings, player_a, player_b)
             return r, time.perf_counter() - t0
 
     r, seconds = run(args.arithmetic)
-    rec = dict(tool="tools/arena.py", a=os.path.basename(args.a), b=os.path.basename(args.b), net=args.net, arithmetic=args.arithmetic,
+    b_name = f"VanillaMCTS{args.baseline}" if args.baseline else os.path.basename(args.b)
+    rec = dict(tool="tools/arena.py", a=os.path.basename(args.a), b=b_name, net=args.net, arithmetic=args.arithmetic,
+               arith_a=args.arith_a or args.arithmetic, arith_b=None if args.baseline else (args.arith_b or args.arithmetic),
                openings=args.openings, opening_plies=args.opening_plies, opening_seed=args.seed, explores=args.explores,
                games=2 * args.openings, wins=r["wins"], draws=r["draws"], losses=r["losses"], score=round(r["score"], 5),
                se=round(r["se"], 5), score_interval=[round(r["score_lo"], 5), round(r["score_hi"], 5)], elo=round(r["elo"], 1),
