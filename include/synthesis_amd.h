@@ -391,6 +391,32 @@ int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_ma
                         const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
                         uint64_t* final_bb, uint64_t* rng_words);
 
+/* ---- tournaments between K players ----------------------------------------------------------------------------- */
+
+#define SYN_TOURNAMENT_MAX_PLAYERS 64
+/* A whole schedule of games between n_players players in ONE device-resident loop. players[p] is a side exactly as
+ * syn_match_run_sides takes it (a network side with its own blob, search settings and arithmetic, or a VanillaMCTS<n> baseline side).
+ * Game g starts at (start_my[g], start_op[g]) with players[first[g]] to move there and players[second[g]] moving second, on the
+ * generator StdRng::seed_from_u64(seeds[g]) (seeds may be NULL only when no player is a baseline side).
+ * Definition: game g's record — rewards[g] for the first mover, plies[g], its 63 move slots, final_bb[g] (the first mover's stones, the
+ * second mover's) and rng_words[g] — is bit for bit what
+ *     syn_match_run_sides(h, &players[first[g]], &players[second[g]], &start_my[g], &start_op[g], &seeds[g], 1, ...)
+ * returns for that one game: a game's record depends on its own position and generator alone, never on its job index.
+ * first[g] == second[g] (a player against itself) and a player that appears in no game are allowed. n_games == 0 is SYN_OK.
+ * Every refusal of syn_match_run_sides is a refusal here, for any player of the call whether it plays or not, before anything of the
+ * engine or the device changes; also n_players outside 1 .. SYN_TOURNAMENT_MAX_PLAYERS and an index outside [0, n_players)
+ * (SYN_ERR_INVALID_ARGUMENT, naming the game). The engine's own network, host blob, f16x2 image and policy cache stay untouched: the
+ * call owns one image buffer per network player, and its searches run with the cache off.
+ * The loop: at ply t every live game is at the same parity, and the live games are kept grouped by the player that moves (game order
+ * inside a group). Per ply: ONE search launch per player that has games to move in, over all of them whatever pairing each belongs
+ * to; the advance kernel per group; a stable (n_players + 1)-way regroup by the next mover (two kernels and a scan); n_players + 2
+ * words read back (the groups' starts and the ply's error word). Nothing is uploaded after the first launch.
+ * syn_last_timing: the summed device time of all plies and the number of launches (two per non-empty group and two for the regroup,
+ * per ply). syn_cancel, syn_progress, the capacity errors and the 63-ply bound behave as documented for syn_match_run. */
+int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
+                       const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards,
+                       int32_t* plies, uint8_t* moves, uint64_t* final_bb, uint64_t* rng_words);
+
 /* ---- self-play ------------------------------------------------------------------------------------------------- */
 
 /* Event counters summed over all games of a run (definitions: SURVEY.md §8d; used for algorithmic-bytes accounting) */
@@ -648,6 +674,10 @@ int syn_debug_fast_div(syn_engine* h, const float* a, const float* b, int n, flo
  * div2_by_small_int differs from the IEEE division, [1] = the same for div2_safe_range, [2] = square roots where sqrt_normal_range
  * differs from sqrtf. All three must be 0. */
 int syn_debug_small_int_math(syn_engine* h, int b_lo, int b_hi, unsigned long long* mismatches3);
+/* The tournament's stable multi-way regroup alone (count, scan, scatter) on the ids 0 .. n-1: keys[i] in [0, n_keys] (n_keys = dropped),
+ * 1 <= n_keys <= SYN_TOURNAMENT_MAX_PLAYERS. perm_out[0 .. seg_out[n_keys]) = the ids grouped by ascending key, input order kept inside
+ * a group (the rest of perm_out[0 .. n) is -1); seg_out[0 .. n_keys] = where each group starts, seg_out[n_keys] = the survivors. */
+int syn_debug_tournament_regroup(syn_engine* h, const int32_t* keys, int n, int n_keys, int32_t* perm_out, int32_t* seg_out);
 
 /* PMC calibration probe (tools/calibrate_pmc.py): gathers n_spans 288-byte sibling spans of 32-byte node records at
  * record offsets d_span_off[i] from d_base (device pointers), optionally rewriting 16 bytes per touched record. */

@@ -9,6 +9,11 @@ starts: what the device match is timed and tested against. A player may name an 
 then plays through Engine.match_run_sides, so one checkpoint can meet itself in the other arithmetic; `compare_baseline` plays a
 checkpoint against the evaluator's VanillaMCTS<n> (match.vanilla_player) with the same statistics.
 
+More than two players: `tournament` / `round_robin` / `gauntlet` play every pair of a schedule on every opening, once per colour, in ONE
+Engine.tournament_run (syn_tournament_run: one device-resident loop, one search launch per player and ply) and return compare's
+statistics per pair; `ratings` puts the pairs on one scale (maximum-likelihood Bradley-Terry strengths as Elo, bootstrap intervals
+over openings).
+
 Host code only draws openings and does statistics — no search, no network."""
 import math
 
@@ -152,6 +157,179 @@ def compare_baseline(engine, blob_a, openings, player_a, baseline, seeds):
     g2 = engine.match_run_sides(baseline, a, my, op, seeds=seeds)
     out = pair_statistics(g1["rewards"], g2["rewards"])
     out["plies_a_first"], out["plies_b_first"] = g1["plies"], g2["plies"]
+    return out
+
+
+# ---- more than two players: one device-resident tournament (Engine.tournament_run = syn_tournament_run) and a rating fit
+def round_robin_pairs(n_players):
+    """every unordered pair (a, b), a < b, in ascending order"""
+    return [(a, b) for a in range(int(n_players)) for b in range(a + 1, int(n_players))]
+
+
+def gauntlet_pairs(n_candidates, n_anchors):
+    """every candidate (players 0 .. n_candidates - 1) with every anchor (the players after them), and no other pair"""
+    return [(c, int(n_candidates) + a) for c in range(int(n_candidates)) for a in range(int(n_anchors))]
+
+
+def schedule(pairs, n_openings, n_players=None):
+    """The games of a tournament: for every opening (outer loop) and every pair (a, b) of `pairs` two games, a moving first, then b
+    moving first — interleaved by opening, not grouped by pairing. Returns dict(first, second, opening, pair [n_games], a_first
+    [n_games] bool, pairs). Raises ValueError on a pair named twice (in either order), a self-pairing or an index out of range."""
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    seen = set()
+    for a, b in pairs:
+        if a == b or a < 0 or b < 0 or (n_players is not None and max(a, b) >= n_players):
+            raise ValueError(f"schedule: pair ({a}, {b}) is a self-pairing or names a player that does not exist")
+        if (min(a, b), max(a, b)) in seen:
+            raise ValueError(f"schedule: pair ({a}, {b}) is named twice")
+        seen.add((min(a, b), max(a, b)))
+    n_openings, m = int(n_openings), len(pairs)
+    pa = np.array([p[0] for p in pairs], np.int32).reshape(m)
+    pb = np.array([p[1] for p in pairs], np.int32).reshape(m)
+    one = np.stack([np.stack([pa, pb], 1), np.stack([pb, pa], 1)], 1).reshape(2 * m, 2)   # per opening: (a, b), (b, a) per pair
+    first = np.tile(one[:, 0], n_openings).astype(np.int32)
+    second = np.tile(one[:, 1], n_openings).astype(np.int32)
+    return dict(first=first, second=second, opening=np.repeat(np.arange(n_openings, dtype=np.int64), 2 * m),
+                pair=np.tile(np.repeat(np.arange(m, dtype=np.int64), 2), n_openings),
+                a_first=np.tile(np.array([True, False] * m, bool), n_openings), pairs=pairs)
+
+
+def tournament(engine, players, pairs, openings, seeds=None):
+    """Every pair of `pairs` on every opening, once per colour, all games in ONE Engine.tournament_run. `players`: what
+    Engine.match_run_sides takes as sides (a network player carries its own .weights and an optional .arithmetic; match.vanilla_player is
+    a baseline); `seeds` [n_openings]: game o of either colour of every pair plays on StdRng::seed_from_u64(seeds[o]), as in
+    compare_baseline (needed when a player is a baseline). Returns dict(n_players, pairs, stats = {pair: pair_statistics' dict from that
+    pair's two reward vectors plus "plies_a_first" / "plies_b_first" — compare's numbers for the pair}, games = tournament_run's raw
+    arrays, schedule)."""
+    my, op = (np.asarray(x, np.uint64).ravel() for x in openings)
+    sch = schedule(pairs, my.size, len(players))
+    o = sch["opening"]
+    game_seeds = None if seeds is None else np.asarray(seeds, np.uint64).ravel()[o]
+    games = engine.tournament_run(players, sch["first"], sch["second"], my[o], op[o], seeds=game_seeds)
+    stats = {}
+    for j, pair in enumerate(sch["pairs"]):
+        g1 = np.nonzero((sch["pair"] == j) & sch["a_first"])[0]      # (in opening order)
+        g2 = np.nonzero((sch["pair"] == j) & ~sch["a_first"])[0]
+        st = pair_statistics(games["rewards"][g1], games["rewards"][g2])
+        st["plies_a_first"], st["plies_b_first"] = games["plies"][g1], games["plies"][g2]
+        stats[pair] = st
+    return dict(n_players=len(players), pairs=sch["pairs"], stats=stats, games=games, schedule=sch)
+
+
+def round_robin(engine, players, openings, seeds=None):
+    """`tournament` over all pairs"""
+    return tournament(engine, players, round_robin_pairs(len(players)), openings, seeds=seeds)
+
+
+def gauntlet(engine, candidates, anchors, openings, seeds=None):
+    """`tournament` of every candidate against every anchor only; the players are candidates + anchors, in that order"""
+    players = list(candidates) + list(anchors)
+    return tournament(engine, players, gauntlet_pairs(len(candidates), len(anchors)), openings, seeds=seeds)
+
+
+def results_from_pair_scores(n_players, pair_scores):
+    """What `ratings` reads of a tournament's return value, from {(a, b): p_o per opening} alone (p_o = a's mean score of the opening's
+    two games, as pair_statistics defines it): for recorded or synthetic results."""
+    pairs = [(int(a), int(b)) for a, b in pair_scores]
+    return dict(n_players=int(n_players), pairs=pairs,
+                stats={p: dict(pair_scores=np.asarray(v, np.float64).ravel()) for p, v in zip(pairs, pair_scores.values())})
+
+
+def _bradley_terry(S, N, tol=1e-13, max_iter=200000):
+    """MM iteration gamma_i <- S_i / sum_j n_ij / (gamma_i + gamma_j) for a batch: S [B, K] total scores, N [B, K, K] games per pair
+    (symmetric, zero diagonal). Returns gamma [B, K] (geometric mean 1 over each row's positive entries) and the iterations taken."""
+    B, K = S.shape
+    g = np.ones((B, K))
+    it = 0
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for it in range(1, max_iter + 1):
+            den = (N / (g[:, :, None] + g[:, None, :])).sum(axis=2)
+            new = np.where(den > 0, S / den, g)
+            pos = new > 0
+            logs = np.where(pos, np.log(np.where(pos, new, 1.0)), 0.0)
+            new = np.where(pos, new / np.exp(logs.sum(axis=1, keepdims=True) / np.maximum(pos.sum(axis=1, keepdims=True), 1)), 0.0)
+            change = np.where(pos & (g > 0), np.abs(np.log(np.where(pos, new, 1.0)) - np.log(np.where(g > 0, g, 1.0))), 0.0)
+            g = new
+            if not np.isfinite(g).all() or change.max() < tol:
+                break
+    return g, it
+
+
+def ratings(results, anchor=0, prior_draws=0.0, bootstrap=400, seed=0):
+    """Maximum-likelihood Bradley-Terry strengths of a tournament's players, as Elo relative to player `anchor`:
+    400 * log10(gamma_i / gamma_anchor), fitted on game scores (a draw counts as half a win) by the MM iteration
+    gamma_i <- S_i / sum_j n_ij / (gamma_i + gamma_j). `prior_draws` adds that many virtual drawn games to every played pair.
+    With prior_draws == 0 a player whose total score is 0 or maximal, or a pairing graph that is not connected, has no finite maximum:
+    ValueError naming the player or the component.
+    Intervals: the 2.5 / 97.5 percentiles of `bootstrap` refits over openings resampled with replacement — the SAME resampled indices
+    for every pair, because an opening's games are not independent across colours or pairs (every pair must have played the same
+    openings) — drawn from numpy.random.default_rng(seed); a refit without a finite maximum counts as +/- 10000 Elo.
+    Returns dict(elo [K], elo_lo [K], elo_hi [K], gamma [K], anchor, iterations, bootstrap, score = {pair: a's score},
+    score_sd = {pair: standard deviation of a's score over the refits' resamples}). A rating is a statement about these players on
+    these openings under these search settings, and nothing else."""
+    K = int(results["n_players"])
+    pairs = [tuple(p) for p in results["pairs"]]
+    if not 0 <= int(anchor) < K:
+        raise ValueError(f"ratings: anchor {anchor} is not one of the {K} players")
+    P = [np.asarray(results["stats"][p]["pair_scores"], np.float64).ravel() for p in pairs]
+    n_open = {p.size for p in P}
+    if len(n_open) > 1:
+        raise ValueError("ratings: every pair must have played the same openings")
+    n_open = n_open.pop() if n_open else 0
+    d = float(prior_draws)
+    # the pairing graph must be connected
+    comp = list(range(K))
+
+    def find(x):
+        while comp[x] != x:
+            comp[x] = comp[comp[x]]
+            x = comp[x]
+        return x
+    for a, b in pairs:
+        if n_open > 0:
+            comp[find(a)] = find(b)
+    roots = {}
+    for i in range(K):
+        roots.setdefault(find(i), []).append(i)
+    if len(roots) > 1:
+        smallest = min(roots.values(), key=len)
+        raise ValueError(f"ratings: the pairing graph is not connected: players {smallest} have played nobody outside their component")
+
+    def totals(idx):
+        """S [B, K], N [B, K, K], pair scores [B, pairs] for resampled opening indices idx [B, n_open]"""
+        B = idx.shape[0]
+        S = np.zeros((B, K)); N = np.zeros((B, K, K)); sc = np.zeros((B, len(pairs)))
+        for j, (a, b) in enumerate(pairs):
+            tot = 2.0 * P[j][idx].sum(axis=1)           # a's score over the 2 * n_open games
+            S[:, a] += tot + d / 2; S[:, b] += 2.0 * n_open - tot + d / 2
+            N[:, a, b] += 2.0 * n_open + d; N[:, b, a] += 2.0 * n_open + d
+            sc[:, j] = tot / (2.0 * n_open)
+        return S, N, sc
+
+    S, N, sc = totals(np.arange(n_open)[None, :])
+    if d == 0.0:
+        for i in range(K):
+            if S[0, i] == 0.0 or S[0, i] == N[0, i].sum():
+                raise ValueError(f"ratings: player {i} scored {'nothing' if S[0, i] == 0.0 else 'every point'}: its rating has no finite "
+                                 "maximum (prior_draws > 0 gives one)")
+    g, iters = _bradley_terry(S, N)
+    elo_of = lambda gam: 400.0 * (np.log10(gam) - np.log10(gam[:, anchor:anchor + 1]))  # noqa: E731
+    point = elo_of(g)[0]
+    out = dict(elo=point, gamma=g[0], anchor=int(anchor), iterations=iters, bootstrap=int(bootstrap),
+               score={p: float(sc[0, j]) for j, p in enumerate(pairs)})
+    if bootstrap and n_open > 0:
+        rng = np.random.default_rng(seed)
+        idx = rng.integers(0, n_open, size=(int(bootstrap), n_open))
+        Sb, Nb, scb = totals(idx)
+        gb, _ = _bradley_terry(Sb, Nb, tol=1e-10, max_iter=20000)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            eb = elo_of(gb)
+        eb = np.clip(np.nan_to_num(eb, nan=0.0, posinf=1e4, neginf=-1e4), -1e4, 1e4)
+        out["elo_lo"], out["elo_hi"] = np.percentile(eb, 2.5, axis=0), np.percentile(eb, 97.5, axis=0)
+        out["score_sd"] = {p: float(scb[:, j].std(ddof=1)) for j, p in enumerate(pairs)}
+    else:
+        out["elo_lo"], out["elo_hi"] = point.copy(), point.copy()
+        out["score_sd"] = {p: float("nan") for p in pairs}
     return out
 
 

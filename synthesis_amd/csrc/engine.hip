@@ -6,6 +6,7 @@
 // the handle's GPU or returns an error code.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -28,6 +29,7 @@
 #include "train_kernels.cuh"
 #include "replay_kernels.cuh"
 #include "match_kernels.cuh"
+#include "tournament_kernels.cuh"
 #include "train_mfma.cuh"
 #include "train_epoch.cuh"
 #include "convnet.cuh"
@@ -94,8 +96,9 @@ struct syn_engine {
     int num_cus = 256;
     hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;  // syn_progress / syn_cancel: independent of the launch stream
-    int* h_pin = nullptr;              // 64 pinned bytes for their transfers: [0..1] syn_progress, [8] syn_cancel's word, [9] its pre-read;
-                                       // [12] (the launch stream's, not theirs) syn_match_run's live-game count
+    int* h_pin = nullptr;              // 512 pinned bytes for their transfers: [0..1] syn_progress, [8] syn_cancel's word, [9] its pre-read;
+                                       // [12] (the launch stream's, not theirs) syn_match_run's live-game count; [16 .. 16 + K + 2)
+                                       // (likewise) syn_tournament_run's group starts and error word
     // The call in flight (syn_selfplay_run / syn_mcts_search* / syn_frozen_search_rollout) as syn_progress / syn_cancel see it.
     // call_mu orders their state changes and serialises the users of aux_stream and h_pin.
     std::mutex call_mu;
@@ -140,6 +143,11 @@ struct syn_engine {
         unsigned char* d_buf = nullptr;
         size_t buf_bytes = 0;
     } match;
+    // syn_tournament_run's network images, one per network player of the call (the live-game arrays share match.d_buf: a call lays
+    // it out afresh)
+    struct Tournament {
+        void* d_img[SYN_TOURNAMENT_MAX_PLAYERS] = {};
+    } tour;
     int* d_job_next = nullptr;
     uint4* d_cache = nullptr;      // PolicyWithCache table (policy_cache_log2 > 0)
     int cache_log2 = 0;
@@ -581,7 +589,7 @@ int syn_engine_create(const syn_engine_config* cfg, int device, syn_engine** out
         if ((e = hipDeviceGetStreamPriorityRange(&lo, &hi)) != hipSuccess) return bail("hipDeviceGetStreamPriorityRange", e);
         if ((e = hipStreamCreateWithPriority(&h->aux_stream, hipStreamNonBlocking, hi)) != hipSuccess) return bail("hipStreamCreate", e);
     }
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), 64)) != hipSuccess) return bail("hipHostMalloc", e);
+    if ((e = hipHostMalloc(reinterpret_cast<void**>(&h->h_pin), 512)) != hipSuccess) return bail("hipHostMalloc", e);
     if ((e = hipEventCreate(&h->ev0)) != hipSuccess) return bail("hipEventCreate", e);
     if ((e = hipEventCreate(&h->ev1)) != hipSuccess) return bail("hipEventCreate", e);
     // the launch may round the slot count up to a whole workgroup (<= 1024 trees: lane kernel)
@@ -622,6 +630,7 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->match.d_img[0]);
     hipFree(h->match.d_img[1]);
     hipFree(h->match.d_buf);
+    for (void* img : h->tour.d_img) hipFree(img);
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
@@ -1783,6 +1792,306 @@ int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_
     }
     HIP_TRY(h, hipSetDevice(h->device));
     return match_run_impl(h, &sides[0], &sides[1], start_my, start_op, nullptr, n_games, rewards, plies, moves, final_bb, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------------ device-resident tournaments
+// syn_tournament_run (tournament_kernels.cuh): the match loop for a schedule of games between K players. The live games are kept
+// grouped by mover; per ply every non-empty group gets its player's search over its range of the arrays (the match's two kinds of
+// launch, on the player's image or partition) and the advance kernel, then one stable regroup by next mover, and the host reads the
+// groups' starts and the error word back. The job counter is reset before every search launch; the search kernels' error word sits in
+// the same 64-byte block and is reset once per ply only, so what the first group raised is still there after the last.
+struct RegroupBuffers {   // device
+    unsigned* counts;   // [n_keys + 1][n_blocks]
+    unsigned* base;     // their exclusive sum
+    void* temp;         // the scan's temporary storage
+    size_t temp_bytes;
+};
+static size_t regroup_cells(size_t n, int n_keys) { return (size_t)(n_keys + 1) * ((n + TOURNAMENT_BLOCK - 1) / TOURNAMENT_BLOCK); }
+// count, scan, scatter over key[0 .. n_live) on the engine's stream; seg_out holds n_keys + 2 words
+static int enqueue_regroup(syn_engine* h, const int* key, int n_live, int n_keys, const RegroupBuffers& B, const MatchLive& from,
+                           const MatchLive& to, const int* search_error, const int* stream_error, int* seg_out) {
+    const dim3 grid((unsigned)((n_live + TOURNAMENT_BLOCK - 1) / TOURNAMENT_BLOCK)), block(TOURNAMENT_BLOCK);
+    size_t temp_bytes = B.temp_bytes;
+    hipLaunchKernelGGL(tournament_count_kernel, grid, block, 0, h->stream, key, n_live, n_keys, B.counts);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(B.temp, temp_bytes, B.counts, B.base, (int)regroup_cells((size_t)n_live, n_keys), h->stream));
+    hipLaunchKernelGGL(tournament_scatter_kernel, grid, block, 0, h->stream, key, n_live, n_keys, B.base, from, to, search_error,
+                       stream_error, seg_out);
+    HIP_TRY(h, hipGetLastError());
+    return SYN_OK;
+}
+
+struct TournamentLayout {   // byte offsets into syn_engine::Match::d_buf, each section 256-byte aligned
+    size_t my[2], op[2], id[2], seed[2], word[2];   // the live games, two sets
+    size_t key, counts, base, scan;                 // the regroup's
+    size_t results;                                 // TOURNAMENT_RESULT_STRIDE bytes per live job: group [lo, hi) owns the bytes from lo * stride
+    size_t explores;                                // baseline players' explores per root: player p's run starts at its own offset
+    size_t first, second;                           // the schedule, per game
+    size_t rewards, plies, moves, final_bb, rng_words;
+    size_t seg;                                     // [0 .. K] group starts, [K + 1] error word, [K + 2] the advance kernels' stream-position flag
+    size_t total;
+};
+constexpr size_t TOURNAMENT_RESULT_STRIDE =
+    ((sizeof(DevSearchResult) > sizeof(FrozenResult) ? sizeof(DevSearchResult) : sizeof(FrozenResult)) + 15) & ~(size_t)15;
+static TournamentLayout tournament_layout(size_t n, int n_players, size_t cells, size_t scan_bytes, size_t n_explores) {
+    TournamentLayout L{};
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    for (int k = 0; k < 2; k++) {
+        L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); L.seed[k] = take(n * 8); L.word[k] = take(n * 8);
+    }
+    L.key = take(n * 4); L.counts = take(cells * 4); L.base = take(cells * 4); L.scan = take(scan_bytes);
+    L.results = take(n * TOURNAMENT_RESULT_STRIDE);
+    L.explores = take(n_explores * 4);
+    L.first = take(n * 4); L.second = take(n * 4);
+    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16); L.rng_words = take(n * 8);
+    L.seg = take((size_t)(n_players + 3) * 4);
+    L.total = at;
+    return L;
+}
+
+int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
+                       const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards,
+                       int32_t* plies, uint8_t* moves, uint64_t* final_bb, uint64_t* rng_words) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_games < 0 || (n_games > 0 && (!first || !second || !start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_tournament_run");
+    if (n_players < 1 || n_players > SYN_TOURNAMENT_MAX_PLAYERS)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: n_players %d is outside 1 .. %d", n_players, SYN_TOURNAMENT_MAX_PLAYERS);
+    if (!players) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: players is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine)
+    // ---- everything that can refuse the call, before anything of the engine or the device changes
+    const int K = n_players;
+    const int kind = h->net.kind;
+    std::vector<MatchSide> S((size_t)K);
+    for (int p = 0; p < K; p++) {
+        char who[24];
+        std::snprintf(who, sizeof(who), "tournament's #%d", p);
+        if (const int rc = check_match_side(h, who, &players[p], seeds != nullptr, S[p])) return rc;
+    }
+    for (int g = 0; g < n_games; g++) {
+        if (first[g] < 0 || first[g] >= K || second[g] < 0 || second[g] >= K)
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: game %d names players %d and %d; there are %d", g, first[g],
+                        second[g], K);
+        if (!valid_root(start_my[g], start_op[g]))
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is not a searchable Connect4 position "
+                        "(overlapping / floating stones, bit 63 set, or no free column)", g);
+        if (host_won(start_my[g]) || host_won(start_op[g]))
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is a finished game: one side has four in a row", g);
+    }
+    std::vector<HostImage> im((size_t)K);
+    for (int p = 0; p < K; p++) {
+        if (S[p].baseline) continue;
+        const int rc = build_host_image(h, kind, players[p].blob, S[p].f16, im[p]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
+        if (rc != SYN_OK) return rc;
+    }
+    if (n_games == 0) return SYN_OK;
+    // ---- the schedule: how many games each player appears in, and the games in their first ply's order (grouped by first mover)
+    const size_t n = (size_t)n_games;
+    std::vector<int> appears((size_t)K, 0), seg((size_t)K + 1, 0);
+    for (size_t g = 0; g < n; g++) {
+        appears[first[g]]++;
+        if (second[g] != first[g]) appears[second[g]]++;
+        seg[first[g] + 1]++;
+    }
+    for (int p = 0; p < K; p++) seg[p + 1] += seg[p];
+    std::vector<int> order(n);
+    {
+        std::vector<int> at(seg.begin(), seg.end() - 1);
+        for (size_t g = 0; g < n; g++) order[at[first[g]]++] = (int)g;
+    }
+    std::vector<size_t> expl_at((size_t)K, 0);
+    size_t n_explores = 0;
+    for (int p = 0; p < K; p++)
+        if (S[p].baseline) { expl_at[p] = n_explores; n_explores += (size_t)appears[p]; }
+    // ---- device memory
+    const size_t cells = regroup_cells(n, K);
+    size_t scan_bytes = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cells, h->stream));
+    const TournamentLayout L = tournament_layout(n, K, cells, scan_bytes, n_explores);
+    for (int p = 0; p < K; p++)
+        if (!S[p].baseline && !h->tour.d_img[p]) HIP_TRY(h, hipMalloc(&h->tour.d_img[p], NET_IMAGE_MAX_BYTES));
+    HIP_TRY(h, ensure_device_buffer(h->match.d_buf, h->match.buf_bytes, L.total));
+    for (int p = 0; p < K; p++)
+        if (S[p].baseline && appears[p] > 0)
+            if (const int rc = ensure_frozen_path(h, S[p].part, appears[p])) return rc;
+    unsigned char* const base = h->match.d_buf;
+    const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
+    MatchLive live_set[2];
+    for (int k = 0; k < 2; k++)
+        live_set[k] = MatchLive{u64_at(L.my[k]), u64_at(L.op[k]), reinterpret_cast<int*>(base + L.id[k]), u64_at(L.seed[k]), u64_at(L.word[k])};
+    int* const d_key = reinterpret_cast<int*>(base + L.key);
+    const RegroupBuffers R{reinterpret_cast<unsigned*>(base + L.counts), reinterpret_cast<unsigned*>(base + L.base), base + L.scan, scan_bytes};
+    unsigned char* const d_res = base + L.results;
+    int* const d_expl = reinterpret_cast<int*>(base + L.explores);
+    int* const d_first = reinterpret_cast<int*>(base + L.first);
+    int* const d_second = reinterpret_cast<int*>(base + L.second);
+    int* const d_seg = reinterpret_cast<int*>(base + L.seg);
+    int* const d_stream_error = d_seg + K + 2;
+    MatchOut out;
+    out.rewards = reinterpret_cast<float*>(base + L.rewards);
+    out.plies = reinterpret_cast<int*>(base + L.plies);
+    out.moves = base + L.moves;
+    out.final_bb = u64_at(L.final_bb);
+    out.rng_words = u64_at(L.rng_words);
+
+    CallScope scope(h, n_games);
+    std::vector<unsigned long long> s_my(n), s_op(n), s_seed(n, 0ull);
+    for (size_t i = 0; i < n; i++) {
+        s_my[i] = start_my[order[i]];
+        s_op[i] = start_op[order[i]];
+        if (seeds) s_seed[i] = seeds[order[i]];
+    }
+    std::vector<int> expl(n_explores);
+    for (int p = 0; p < K; p++) {
+        if (S[p].baseline) {
+            std::fill(expl.begin() + (ptrdiff_t)expl_at[p], expl.begin() + (ptrdiff_t)(expl_at[p] + (size_t)appears[p]), S[p].player->explores);
+            continue;
+        }
+        const int rc = enqueue_image_upload(h, im[p], h->tour.d_img[p]);
+        if (rc != SYN_OK) return rc;
+        S[p].P.wimg = static_cast<const float*>(h->tour.d_img[p]);
+    }
+    if (n_explores) HIP_TRY(h, hipMemcpyAsync(d_expl, expl.data(), n_explores * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].my, s_my.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].op, s_op.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].id, order.data(), n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(live_set[0].seed, s_seed.data(), n * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_first, first, n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(d_second, second, n * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(live_set[0].word, 0, n * 8, h->stream));   // every game's generator starts at output word 0
+    HIP_TRY(h, hipMemsetAsync(base + L.rewards, 0, L.moves - L.rewards, h->stream));   // rewards and plies
+    HIP_TRY(h, hipMemsetAsync(out.moves, MATCH_NO_MOVE, n * MATCH_T, h->stream));
+    HIP_TRY(h, hipMemsetAsync(out.final_bb, 0, n * 16, h->stream));
+    HIP_TRY(h, hipMemsetAsync(out.rng_words, 0, n * 8, h->stream));
+    HIP_TRY(h, hipMemsetAsync(d_seg, 0, (size_t)(K + 3) * 4, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the last upload from host memory: the loop below only launches and reads K + 2 words
+
+    float kernel_ms = 0.0f;
+    int launches = 0, live = n_games, ply = 0;
+    int* const h_seg = h->h_pin + 16;
+    for (; live > 0 && ply < MATCH_T; ply++) {
+        const int cur = ply & 1, nxt = cur ^ 1;
+        const MatchLive& A = live_set[cur];
+        bool any_launch = false, any_baseline = false, any_network = false;
+        // (a syn_cancel's word does not survive the next reset: the loop itself stops at the first ply that ends after it)
+        HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));   // the counters and, once per ply, the error word
+        if (ply == 0) HIP_TRY(h, scope.armed());
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        for (int p = 0; p < K; p++) {
+            const int lo = seg[p], cnt = seg[p + 1] - seg[p];
+            if (cnt == 0) continue;
+            if (any_launch) HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 32, h->stream));   // the counters alone: the error word stays
+            any_launch = true;
+            const dim3 grid((unsigned)((cnt + 255) / 256)), block(256);
+            unsigned char* const res = d_res + (size_t)lo * TOURNAMENT_RESULT_STRIDE;
+            // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
+            if (S[p].baseline) {
+                any_baseline = true;
+                HIP_TRY(h, hipMemsetAsync(res, 0, (size_t)cnt * sizeof(FrozenResult), h->stream));
+                FrozenParams F{};
+                F.in_my = A.my + lo; F.in_op = A.op + lo; F.seeds = A.seed + lo; F.rng_words = A.word + lo; F.explores = d_expl + expl_at[p];
+                F.n_roots = cnt;
+                F.results = reinterpret_cast<FrozenResult*>(res);
+                if (const int rc = launch_frozen(h, S[p].part, &S[p].player->mcts_cfg, S[p].player->action, F)) return rc;
+                hipLaunchKernelGGL(tournament_advance_kernel<FrozenResult>, grid, block, 0, h->stream, reinterpret_cast<const FrozenResult*>(res),
+                                   lo, cnt, ply, A.my, A.op, A.id, A.word, d_first, d_second, K, d_key, d_stream_error, out);
+            } else {
+                any_network = true;
+                HIP_TRY(h, hipMemsetAsync(res, 0, (size_t)cnt * sizeof(DevSearchResult), h->stream));
+                EngineParams Q = S[p].P;
+                Q.n_jobs = cnt;
+                Q.in_my = A.my + lo;
+                Q.in_op = A.op + lo;
+                Q.results = reinterpret_cast<DevSearchResult*>(res);
+                if (const int rc = launch_engine(h, Q, cnt, MODE_SEARCH, false, false, S[p].arith)) return rc;
+                hipLaunchKernelGGL(tournament_advance_kernel<DevSearchResult>, grid, block, 0, h->stream,
+                                   reinterpret_cast<const DevSearchResult*>(res), lo, cnt, ply, A.my, A.op, A.id, A.word, d_first, d_second, K,
+                                   d_key, d_stream_error, out);
+            }
+            HIP_TRY(h, hipGetLastError());
+            launches += 2;   // the search and the advance
+        }
+        if (const int rc = enqueue_regroup(h, d_key, live, K, R, A, live_set[nxt], h->d_job_next + 8, d_stream_error, d_seg)) return rc;
+        launches += 2;       // the count and the scatter (the scan between them is the library's)
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h_seg, d_seg, (size_t)(K + 2) * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        float ms = 0.0f;
+        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        kernel_ms += ms;
+        h->last_kernel_ms = kernel_ms;
+        h->last_launches = launches;
+        if (scope.cancelled())
+            return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the tournament: the outputs are unspecified", ply);
+        const int err = h_seg[K + 1];
+        if (err == -MATCH_ERR_STREAM)
+            return fail(h, SYN_ERR_CAPACITY, "a game's rollout generator passed output word 0xC0000000 at ply %d of the tournament: the "
+                                             "baseline search supports no longer stream", ply);
+        if (err < 0 && any_baseline && !any_network) return fail(h, SYN_ERR_CAPACITY, "a baseline tree ran out of node records");
+        if (err == -2)
+            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks or records (lane-per-tree kernel: %u blocks per tree for "
+                                             "max_explores %d; baseline trees: their partition of the pool)", h->cap / 4, h->max_explores);
+        if (err < 0) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+        bool sane = h_seg[0] == 0 && h_seg[K] <= live;
+        for (int p = 0; p < K && sane; p++) sane = h_seg[p] <= h_seg[p + 1];
+        if (!sane) return fail(h, SYN_ERR_HIP, "syn_tournament_run: the regroup of ply %d returned group starts that are no partition of "
+                                               "at most %d games", ply, live);
+        for (int p = 0; p <= K; p++) seg[p] = h_seg[p];
+        live = seg[K];
+    }
+    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_tournament_run: %d games are unfinished after %d plies", live, MATCH_T);
+    HIP_TRY(h, hipMemcpyAsync(rewards, out.rewards, n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
+    if (final_bb) HIP_TRY(h, hipMemcpyAsync(final_bb, out.final_bb, n * 16, hipMemcpyDeviceToHost, h->stream));
+    if (rng_words) HIP_TRY(h, hipMemcpyAsync(rng_words, out.rng_words, n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->last_cache_hits = h->last_cache_misses = 0;   // a tournament does not use the policy cache
+    return SYN_OK;
+}
+
+int syn_debug_tournament_regroup(syn_engine* h, const int32_t* keys, int n, int n_keys, int32_t* perm_out, int32_t* seg_out) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n_keys < 1 || n_keys > TOURNAMENT_MAX_KEYS || !seg_out || (n > 0 && (!keys || !perm_out)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_debug_tournament_regroup");
+    for (int i = 0; i < n; i++)
+        if (keys[i] < 0 || keys[i] > n_keys)
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_debug_tournament_regroup: key %d of job %d is outside [0, %d]", keys[i], i, n_keys);
+    for (int k = 0; k <= n_keys; k++) seg_out[k] = 0;
+    if (n == 0) return SYN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nb = (size_t)n, cells = regroup_cells(nb, n_keys);
+    size_t scan_bytes = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cells, h->stream));
+    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_key = 0, o_in = o_key + pad(nb * 4), o_out = o_in + pad(nb * 4), o_counts = o_out + pad(nb * 4),
+                 o_base = o_counts + pad(cells * 4), o_seg = o_base + pad(cells * 4), o_scan = o_seg + pad((size_t)(n_keys + 2) * 4);
+    if (const int rc = ensure_scratch(h, o_scan + pad(scan_bytes))) return rc;
+    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
+    int* const d_key = reinterpret_cast<int*>(base + o_key);
+    int* const d_seg = reinterpret_cast<int*>(base + o_seg);
+    const MatchLive from{nullptr, nullptr, reinterpret_cast<int*>(base + o_in), nullptr, nullptr};
+    const MatchLive to{nullptr, nullptr, reinterpret_cast<int*>(base + o_out), nullptr, nullptr};
+    const RegroupBuffers R{reinterpret_cast<unsigned*>(base + o_counts), reinterpret_cast<unsigned*>(base + o_base), base + o_scan, scan_bytes};
+    std::vector<int> iota(nb);
+    for (size_t i = 0; i < nb; i++) iota[i] = (int)i;
+    HIP_TRY(h, hipMemcpyAsync(d_key, keys, nb * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(from.id, iota.data(), nb * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemsetAsync(to.id, 0xFF, nb * 4, h->stream));
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (const int rc = enqueue_regroup(h, d_key, n, n_keys, R, from, to, nullptr, nullptr, d_seg)) return rc;
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(perm_out, to.id, nb * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(seg_out, d_seg, (size_t)(n_keys + 1) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
+    h->last_launches = 2;
+    return SYN_OK;
 }
 
 // evaluator.rs:308-319 FrozenMCTS::exploit over RolloutPolicy for n roots (frozen_kernel.cuh)

@@ -43,24 +43,19 @@ struct MatchOut {
 // returns SYN_ERR_CANCELLED then. The column is checked before it is played: a record never comes from an illegal move.
 // word[i] is the stream position the ply's search left (a network ply leaves it alone). A position past MATCH_WORD_LIMIT raises
 // stream_error[0]: every thread that sees one stores the same 1, so the plain stores need no order among themselves.
+// The rules for ONE job (shared with tournament_advance_kernel, tournament_kernels.cuh): job i's search record is `res`, its game g.
+// Returns whether the game goes on.
 template <class Result>
-__global__ void __launch_bounds__(256) match_advance_kernel(
-    const Result* __restrict__ results, int n_live, int ply, unsigned long long* __restrict__ my, unsigned long long* __restrict__ op,
-    const int* __restrict__ id, const unsigned long long* __restrict__ word, unsigned* __restrict__ keep, int* __restrict__ stream_error,
-    MatchOut out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_live) return;
-    const int col = results[i].best_action;
+SYN_DEV bool match_advance_job(const Result& res, int i, int g, int ply, unsigned long long* __restrict__ my,
+                               unsigned long long* __restrict__ op, const unsigned long long* __restrict__ word,
+                               int* __restrict__ stream_error, const MatchOut& out) {
+    const int col = res.best_action;
     const uint64_t m = my[i], o = op[i], occ = m | o;
     const unsigned long long w_pos = word[i];
     if (w_pos > MATCH_WORD_LIMIT) stream_error[0] = 1;
-    const bool searched = results[i].num_nodes != 0u && col >= 0 && col < c4::WIDTH;
+    const bool searched = res.num_nodes != 0u && col >= 0 && col < c4::WIDTH;
     const int h = searched ? c4::col_height(occ, col) : c4::HEIGHT;
-    if (h >= c4::HEIGHT) {
-        keep[i] = 0u;
-        return;
-    }
-    const int g = id[i];
+    if (h >= c4::HEIGHT) return false;
     const uint64_t bit = 1ull << (h + 7 * col);
     const uint64_t mover = m | bit;
     const bool w = c4::won(mover);
@@ -73,12 +68,21 @@ __global__ void __launch_bounds__(256) match_advance_kernel(
         out.final_bb[2 * (size_t)g + 0] = first_moved ? mover : o;
         out.final_bb[2 * (size_t)g + 1] = first_moved ? o : mover;
         out.rng_words[g] = w_pos;
-        keep[i] = 0u;
-    } else {
-        my[i] = o;      // the opponent moves next: its stones first
-        op[i] = mover;
-        keep[i] = 1u;
+        return false;
     }
+    my[i] = o;      // the opponent moves next: its stones first
+    op[i] = mover;
+    return true;
+}
+
+template <class Result>
+__global__ void __launch_bounds__(256) match_advance_kernel(
+    const Result* __restrict__ results, int n_live, int ply, unsigned long long* __restrict__ my, unsigned long long* __restrict__ op,
+    const int* __restrict__ id, const unsigned long long* __restrict__ word, unsigned* __restrict__ keep, int* __restrict__ stream_error,
+    MatchOut out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_live) return;
+    keep[i] = match_advance_job(results[i], i, id[i], ply, my, op, word, stream_error, out) ? 1u : 0u;
 }
 
 // The live games' arrays, one set: a ply's compaction reads one set and writes the other.

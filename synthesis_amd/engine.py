@@ -27,8 +27,9 @@ ABI_SYMBOLS = [
     "syn_replay_append_device", "syn_replay_append", "syn_replay_keep_games_from", "syn_replay_read",
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
-    "syn_match_run", "syn_match_run_sides",
+    "syn_match_run", "syn_match_run_sides", "syn_tournament_run", "syn_debug_tournament_regroup",
 ]
+TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
 
 BATCH_MODES = {"chained": 0, "micro": 1}   # SYN_TRAIN_BATCH_*
@@ -163,6 +164,9 @@ def load_library():
                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.syn_match_run_sides.argtypes = [C.c_void_p, C.POINTER(CMatchSide), C.POINTER(CMatchSide), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.syn_tournament_run.argtypes = [C.c_void_p, C.POINTER(CMatchSide), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.syn_debug_tournament_regroup.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.syn_progress.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.syn_cancel.argtypes = [C.c_void_p]
     lib.syn_trainer_set_precision.argtypes = [C.c_void_p, C.c_int]
@@ -535,6 +539,40 @@ class Engine:
                                                   _p(out["rng_words"])))
         return out
 
+    def tournament_run(self, players, first, second, start_my, start_op, seeds=None):
+        """syn_tournament_run: a whole schedule of games between len(players) players in one device-resident loop. `players` are
+        objects match_side accepts (what match_run_sides takes as a side); game g starts at (start_my[g], start_op[g]) with
+        players[first[g]] to move and players[second[g]] moving second, on the generator of seeds[g] (needed when a player is a baseline).
+        Game g's record is what match_run_sides(players[first[g]], players[second[g]], ...) returns for that one game. Returns
+        match_run_sides' dict. The engine's own network, arithmetic and policy cache are untouched."""
+        sides, keep = [], []
+        for p in players:
+            side, blob = self.match_side(p)
+            sides.append(side)
+            keep.append(blob)   # (the struct holds a raw pointer into it)
+        return self.tournament_run_c(sides, first, second, start_my, start_op, seeds)
+
+    def tournament_run_c(self, sides, first, second, start_my, start_op, seeds=None, n_players=None):
+        """tournament_run on CMatchSide structs as they are (the blobs they point to must stay alive for the call); n_players
+        overrides len(sides) (the refusal tests)"""
+        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
+        fi = np.ascontiguousarray(first, dtype=np.int32).ravel()
+        se = np.ascontiguousarray(second, dtype=np.int32).ravel()
+        if not (my.size == op.size == fi.size == se.size):
+            raise ValueError("first, second, start_my and start_op must have the same length")
+        n = int(my.size)
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n,)))
+        arr = (CMatchSide * max(len(sides), 1))(*sides)
+        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
+                   final_bb=np.zeros((n, 2), np.uint64), rng_words=np.zeros(n, np.uint64))
+        self._check(self._lib.syn_tournament_run(self._h, arr, len(sides) if n_players is None else int(n_players), _p(fi), _p(se), _p(my),
+                                                 _p(op), _p(sd), n, _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]),
+                                                 _p(out["final_bb"]), _p(out["rng_words"])))
+        return out
+
     @staticmethod
     def _search_records(res, n):
         raw = np.frombuffer(res, dtype=np.uint8).reshape(max(n, 1), C.sizeof(CSearchResult))[:n]
@@ -668,6 +706,13 @@ class Engine:
         nl = C.c_int()
         self._check(self._lib.syn_last_timing(self._h, C.byref(ms), C.byref(nl)))
         return float(ms.value)
+
+    def last_timing(self):
+        """syn_last_timing: (device milliseconds, kernel launches) of the last call; summed over plies for a match or a tournament"""
+        ms = C.c_float()
+        nl = C.c_int()
+        self._check(self._lib.syn_last_timing(self._h, C.byref(ms), C.byref(nl)))
+        return float(ms.value), int(nl.value)
 
     # ---- learner step (alpha_zero.rs:31-36,72-94) and replay de-duplication (data.rs:196-235)
     def trainer_init(self, blob, weight_decay=1e-6, policy_weight=1.0, value_weight=1.0, beta1=0.9, beta2=0.999,
@@ -884,6 +929,15 @@ class Engine:
         out = np.zeros(int(n), np.uint32)
         self._check(self._lib.syn_debug_stdrng_u32(self._h, int(seed), int(n), _p(out)))
         return out
+
+    def debug_tournament_regroup(self, keys, n_keys):
+        """syn_debug_tournament_regroup: (perm [n] = ids 0..n-1 grouped by ascending key, input order kept inside a group, -1 past the
+        survivors; seg [n_keys + 1] = where each group starts, seg[n_keys] = the survivors). keys[i] == n_keys drops job i."""
+        k = np.ascontiguousarray(keys, np.int32).ravel()
+        perm = np.full(k.size, -1, np.int32)
+        seg = np.zeros(int(n_keys) + 1, np.int32)
+        self._check(self._lib.syn_debug_tournament_regroup(self._h, _p(k), int(k.size), int(n_keys), _p(perm), _p(seg)))
+        return perm, seg
 
     def debug_fast_div(self, a, b):
         a = np.ascontiguousarray(a, np.float32).ravel()
