@@ -64,8 +64,11 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, one GPU per rank) | gloo (every rank on GPU 0: tests)")
     ap.add_argument("--reference-fpu", action="store_true", help="self-play with Fpu::Func(|| Normal(1.0, 0.1)) (main.rs:43-47)")
     ap.add_argument("--dump-weights", default="", help="write the final weights of every rank to <prefix>.rank<r>.npy")
-    ap.add_argument("--sampler", default="numpy", choices=["numpy", "torch"], help="order of an epoch's batches: numpy's PCG64 or "
-                    "libtorch's randperm stream (what the reference's BatchRandSampler draws, data.rs:29); learning loop only")
+    ap.add_argument("--sampler", default="numpy", choices=["numpy", "torch", "device"], help="order of an epoch's batches: numpy's PCG64, "
+                    "libtorch's randperm stream (what the reference's BatchRandSampler draws, data.rs:29), or device = the device-side "
+                    "sampler (an iteration's epochs in one call, no permutation on the host); learning loop only")
+    ap.add_argument("--flip", action="store_true", help="--sampler device only: every epoch mirrors a random half of the rows while it "
+                    "gathers them (both orientations at the plain data set's epoch cost; its effect on strength is not measured)")
     ap.add_argument("--logs", default="", help="directory for what the reference writes per iteration (alpha_zero.rs:37,97-100): "
                     "models/model_{i}.ot and latest_{states,pis,vs}.npy (the learning loop's rank 0)")
     ap.add_argument("--net", default="mlp", choices=["mlp", "conv"], help="mlp = the reference's Connect4Net; conv = Connect4ConvNet "
@@ -85,6 +88,10 @@ def main():
     args = ap.parse_args()
     if args.replay != "host" and args.data_parallel:
         raise SystemExit("--replay device belongs to the learning loop: --data-parallel keeps one replay buffer per rank on the host")
+    if args.sampler == "device" and args.data_parallel:
+        raise SystemExit("--sampler device belongs to the learning loop: --data-parallel draws its order on the host")
+    if args.flip and args.sampler != "device":
+        raise SystemExit("--flip is part of the device sampler's gather: add --sampler device")
 
     import torch  # noqa: F401  (before the engine: one HIP runtime per process)
 
@@ -127,7 +134,7 @@ def main():
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
-                            batch_mode=args.batch_mode, **hyper)
+                            batch_mode=args.batch_mode, flip=args.flip, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -547,6 +547,45 @@ int syn_train_set_data(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_
                        const float* target_v, size_t n);
 int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses);
 
+/* ---- Device-side epoch sampler (DESIGN.md §6.4 "Device-side epoch sampler"; not in the reference): a second, opt-in definition of
+ * "an epoch's order" that the device computes from a 64-bit key, so that an iteration's epochs are ONE call and the host neither draws a
+ * permutation nor uploads indices. All arithmetic is unsigned 64-bit with wrap-around:
+ *   finalise(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *   sm(seed, idx) = finalise(seed + (idx + 1) * 0x9E3779B97F4A7C15), idx a uint32 and idx + 1 computed in 32 bits (idx = 2^32 - 1
+ *     gives 0) — csrc/noise.cuh noise_splitmix64, the generator behind the self-play noise
+ *   SAMPLER_TAG = 0x5AD3C0DE5EED1E55
+ *   key of epoch e (a uint32):            K_e = sm(key ^ SAMPLER_TAG, e)
+ *   sort key of row i of an n-row set:    k_i = sm(K_e, i), 0 <= i < n <= 2^31 - 1   (the multiplier is odd and finalise a bijection:
+ *                                         the k_i are pairwise distinct, so the order below is unique)
+ *   perm_e = the row indices in ascending order of k_i;   flip_e[i] = k_i & 1
+ * Epoch e runs n_steps = n / batch optimiser steps (drop_last); step s takes the rows perm_e[s*batch .. (s+1)*batch) in that order. With
+ * flip = SYN_SAMPLER_FLIP_RANDOM a row i with flip_e[i] = 1 enters as (mirror my, mirror op, pi[8 - c], v) — the left-right mirror
+ * image of "Mirror symmetry" below — otherwise, and always with SYN_SAMPLER_FLIP_NONE, as stored. The stored data set is never modified.
+ *
+ * syn_train_epochs_sampled runs the epochs first_epoch .. first_epoch + n_epochs - 1 over the learner's current data set
+ * (syn_train_set_data / syn_replay_deduplicate_to_trainer[_symmetric]): per epoch a key kernel, a radix sort of the n (k_i, i) pairs,
+ * a gather of the first n_steps*batch sorted rows with the flip folded in, and then exactly what syn_train_epoch runs on its gathered
+ * batches — the same persistent kernels with their snapshot / give-up / queued fallback, the queued launches above 32 positions and
+ * SYN_TRAIN_BATCH_MICRO with its rules — so epoch e leaves the bits of syn_train_epoch(perm_e[0 .. n_steps*batch)) over the data set
+ * with the flagged rows mirrored. step_losses ([n_epochs][n_steps][2], may be NULL) receives every step's (pi_loss, v_loss);
+ * *n_steps (may be NULL) = steps per epoch. The optimiser step count advances by n_epochs * n_steps.
+ * n < batch (*n_steps = 0) and n_epochs = 0 are SYN_OK with the learner unchanged. Refused, with the learner bit for bit as it was:
+ * cfg NULL, flip outside {0, 1}, n_epochs < 0, batch < 1, first_epoch + n_epochs > 2^32 (SYN_ERR_INVALID_ARGUMENT; also when there is
+ * no data set), no trainer (SYN_ERR_NO_WEIGHTS), and SYN_TRAIN_BATCH_MICRO's refusals of a batch (syn_trainer_set_batch_mode).
+ * Whether random flipping trains a stronger player is not measured (tools/arena.py is the instrument).
+ *
+ * syn_debug_sampler: perm_e and flip_e of epoch `epoch` alone for n rows (1 <= n <= 2^31 - 1) as host arrays: perm_out[n] in step
+ * order, flip_out[n] indexed by ROW (either may be NULL). cfg->key is used, first_epoch and flip are ignored; needs no trainer. */
+typedef struct syn_sampler_config {
+    uint64_t key;
+    uint32_t first_epoch;
+    int32_t flip; /* SYN_SAMPLER_FLIP_* */
+} syn_sampler_config;
+enum { SYN_SAMPLER_FLIP_NONE = 0, SYN_SAMPLER_FLIP_RANDOM = 1 };
+int syn_train_epochs_sampled(syn_engine* h, const syn_sampler_config* cfg, int n_epochs, int batch, float lr,
+                             float* step_losses /* [n_epochs][n_steps][2], may be NULL */, size_t* n_steps /* per epoch, out */);
+int syn_debug_sampler(syn_engine* h, const syn_sampler_config* cfg, uint32_t epoch, size_t n, int32_t* perm_out, uint8_t* flip_out);
+
 /* Replaces: ReplayBuffer::deduplicate (data.rs:196-235): identical states are merged, their targets summed in buffer
  * order and divided by the count. Outputs are sized for n entries; *out_count = number of unique states, emitted in
  * ascending (my_bb, op_bb) order (the reference's order is HashMap iteration order, i.e. unspecified). */

@@ -28,6 +28,7 @@
 #include "frozen_kernel.cuh"
 #include "train_kernels.cuh"
 #include "replay_kernels.cuh"
+#include "sampler_kernels.cuh"
 #include "match_kernels.cuh"
 #include "tournament_kernels.cuh"
 #include "train_mfma.cuh"
@@ -2908,21 +2909,34 @@ static int check_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int b
             return fail(h, SYN_ERR_INVALID_ARGUMENT, "perm[%zu] = %d is outside the %zu uploaded states", i, perm[i], n);
     return SYN_OK;
 }
-// lays the scratch out and gathers the epoch's batches
+// scratch: [perm ni x 4][losses n_steps x 8][step-ordered batches: my, op (8 B each), pi (36 B), v (12 B) per sample]
+//          [per-step Adam scalars n_steps x 8][diagnostic stamps 4 KB]
+struct EpochStageLayout {
+    size_t perm_bytes, loss_bytes, batch_bytes;
+    size_t bytes() const { return perm_bytes + loss_bytes + batch_bytes + loss_bytes + 4096; }
+};
+static EpochStageLayout epoch_stage_layout(size_t n_steps, int batch) {
+    const size_t ni = n_steps * (size_t)batch;
+    return {(ni * 4 + 255) & ~(size_t)255, (n_steps * 8 + 255) & ~(size_t)255, (ni * 64 + 255) & ~(size_t)255};
+}
+// the stage's pointers into the scratch at `base` (derived after ensure_scratch: the buffer may have moved)
+static EpochStage epoch_stage_at(void* base, const EpochStageLayout& lay, size_t ni) {
+    unsigned char* sc = static_cast<unsigned char*>(base);
+    EpochStage st{};
+    st.d_perm = reinterpret_cast<int*>(sc);
+    st.d_losses = reinterpret_cast<float*>(sc + lay.perm_bytes);
+    st.batches = train_sections(sc + lay.perm_bytes + lay.loss_bytes, ni);
+    st.d_adam = reinterpret_cast<float*>(sc + lay.perm_bytes + lay.loss_bytes + lay.batch_bytes);
+    st.d_stamps = reinterpret_cast<unsigned long long*>(sc + lay.perm_bytes + lay.loss_bytes + lay.batch_bytes + lay.loss_bytes);
+    return st;
+}
+// "stage the step-ordered batches" from the caller's permutation: lays the scratch out and gathers the epoch's batches
 static int stage_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, EpochStage* st) {
     const size_t n = h->learner.train_data_n, ni = n_steps * (size_t)batch;
-    // scratch: [perm ni x 4][losses n_steps x 8][step-ordered batches: my, op (8 B each), pi (36 B), v (12 B) per sample]
-    //          [per-step Adam scalars n_steps x 8][diagnostic stamps 4 KB]
-    const size_t perm_bytes = (ni * 4 + 255) & ~(size_t)255, loss_bytes = (n_steps * 8 + 255) & ~(size_t)255;
-    const size_t batch_bytes = (ni * 64 + 255) & ~(size_t)255;
-    const int rc = ensure_scratch(h, perm_bytes + loss_bytes + batch_bytes + loss_bytes + 4096 + 256);
+    const EpochStageLayout lay = epoch_stage_layout(n_steps, batch);
+    const int rc = ensure_scratch(h, lay.bytes() + 256);
     if (rc != SYN_OK) return rc;
-    unsigned char* sc = static_cast<unsigned char*>(h->d_scratch);
-    st->d_perm = reinterpret_cast<int*>(sc);
-    st->d_losses = reinterpret_cast<float*>(sc + perm_bytes);
-    st->batches = train_sections(sc + perm_bytes + loss_bytes, ni);
-    st->d_adam = reinterpret_cast<float*>(sc + perm_bytes + loss_bytes + batch_bytes);
-    st->d_stamps = reinterpret_cast<unsigned long long*>(sc + perm_bytes + loss_bytes + batch_bytes + loss_bytes);
+    *st = epoch_stage_at(h->d_scratch, lay, ni);
     HIP_TRY(h, hipMemcpyAsync(st->d_perm, perm, ni * 4, hipMemcpyHostToDevice, h->stream));
     // one gather for the whole epoch (the sampler's index_select), so a step reads its batch from consecutive addresses
     // instead of chasing perm -> sample inside the latency-bound step kernel
@@ -3139,15 +3153,10 @@ static int epoch_queued(syn_engine* h, const EpochStage& st, size_t n_steps, int
     return SYN_OK;
 }
 
-int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses) {
-    int rc = check_epoch(h, perm, n_steps, batch);
-    if (rc != SYN_OK || n_steps == 0) return rc;
-    rc = check_micro_batch(h, batch);
-    if (rc != SYN_OK) return rc;
-    HIP_TRY(h, hipSetDevice(h->device));
-    EpochStage st{};
-    rc = stage_epoch(h, perm, n_steps, batch, &st);
-    if (rc != SYN_OK) return rc;
+// "run the staged epoch": the n_steps optimiser steps over st.batches, whoever ordered them (the caller's permutation: stage_epoch; the
+// device sampler: syn_train_epochs_sampled). Returns after the epoch: the stream is idle and the scratch may be staged again.
+static int run_staged_epoch(syn_engine* h, const EpochStage& st, size_t n_steps, int batch, float lr, float* step_losses) {
+    int rc = SYN_OK;
     // SYN_TRAIN_BATCH_MICRO: three queued launches per step (blocks, reduce, Adam) whatever the batch, one synchronisation at the end;
     // no workgroup waits for another, so there is no snapshot and never a persistent kernel
     if (h->learner.batch_mode == SYN_TRAIN_BATCH_MICRO) return epoch_queued(h, st, n_steps, batch, lr, step_losses);
@@ -3162,6 +3171,120 @@ int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batc
         if (rc != SYN_OK || done) return rc;
     }
     return epoch_queued(h, st, n_steps, batch, lr, step_losses);
+}
+
+int syn_train_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, float lr, float* step_losses) {
+    int rc = check_epoch(h, perm, n_steps, batch);
+    if (rc != SYN_OK || n_steps == 0) return rc;
+    rc = check_micro_batch(h, batch);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    EpochStage st{};
+    rc = stage_epoch(h, perm, n_steps, batch, &st);
+    if (rc != SYN_OK) return rc;
+    return run_staged_epoch(h, st, n_steps, batch, lr, step_losses);
+}
+
+// ---- the device-side epoch sampler (sampler_kernels.cuh; include/synthesis_amd.h syn_train_epochs_sampled)
+// The sort's buffers for n rows: keys and row indices, in and out, and hipcub's temporary storage.
+struct SamplerBuffers {
+    unsigned long long* k_in;
+    unsigned long long* k_out;
+    int* i_in;
+    int* i_out;
+    void* tmp;
+    size_t tmp_bytes;
+};
+static size_t sampler_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+static int sampler_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total) {
+    *tmp_bytes = 0;
+    HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                                  (const int*)nullptr, (int*)nullptr, (int)n, 0, 64, h->stream));
+    *total = 2 * sampler_pad(n * 8) + 2 * sampler_pad(n * 4) + sampler_pad(*tmp_bytes);
+    return SYN_OK;
+}
+static SamplerBuffers sampler_buffers_at(void* base, size_t n, size_t tmp_bytes) {
+    unsigned char* b = static_cast<unsigned char*>(base);
+    const size_t k = sampler_pad(n * 8), i = sampler_pad(n * 4);
+    return {reinterpret_cast<unsigned long long*>(b), reinterpret_cast<unsigned long long*>(b + k), reinterpret_cast<int*>(b + 2 * k),
+            reinterpret_cast<int*>(b + 2 * k + i), b + 2 * k + 2 * i, tmp_bytes};
+}
+// epoch `epoch`'s order on the stream: B.i_out = perm_e, B.k_out = the keys in that order (bit 0 = the row's flip flag)
+static int enqueue_sampler(syn_engine* h, const SamplerBuffers& B, uint64_t key, uint32_t epoch, size_t n) {
+    const int ni = (int)n;
+    hipLaunchKernelGGL(sampler_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sampler_epoch_key(key, epoch), ni,
+                       B.k_in, B.i_in);
+    HIP_TRY(h, hipGetLastError());
+    size_t tmp = B.tmp_bytes;
+    HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(B.tmp, tmp, B.k_in, B.k_out, B.i_in, B.i_out, ni, 0, 64, h->stream));
+    return SYN_OK;
+}
+
+int syn_train_epochs_sampled(syn_engine* h, const syn_sampler_config* cfg, int n_epochs, int batch, float lr, float* step_losses,
+                             size_t* n_steps_out) {
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    if (n_steps_out) *n_steps_out = 0;
+    if (!cfg) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: cfg is NULL");
+    if (cfg->flip != SYN_SAMPLER_FLIP_NONE && cfg->flip != SYN_SAMPLER_FLIP_RANDOM)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: unknown flip mode %d", cfg->flip);
+    if (n_epochs < 0 || batch < 1) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: n_epochs = %d, batch = %d", n_epochs, batch);
+    if ((uint64_t)cfg->first_epoch + (uint64_t)n_epochs > (1ull << 32))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: epochs %u + %d run past 2^32", cfg->first_epoch, n_epochs);
+    const size_t n = h->learner.train_data_n;
+    if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "call syn_train_set_data first");
+    const size_t n_steps = n / (size_t)batch, ni = n_steps * (size_t)batch;
+    if (n_epochs == 0 || n_steps == 0) return SYN_OK;
+    rc = check_micro_batch(h, batch);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    // one scratch for the whole call: the epoch's stage, then the sort's buffers; every pointer is derived after the one ensure_scratch
+    // (nothing below it grows the scratch), and epoch e + 1 is staged over epoch e's once run_staged_epoch has returned
+    const EpochStageLayout lay = epoch_stage_layout(n_steps, batch);
+    size_t tmp_bytes = 0, sort_bytes = 0;
+    rc = sampler_bytes(h, n, &tmp_bytes, &sort_bytes);
+    if (rc != SYN_OK) return rc;
+    const size_t o_sort = sampler_pad(lay.bytes());
+    rc = ensure_scratch(h, o_sort + sort_bytes + 256);
+    if (rc != SYN_OK) return rc;
+    EpochStage st = epoch_stage_at(h->d_scratch, lay, ni);
+    const SamplerBuffers B = sampler_buffers_at(static_cast<unsigned char*>(h->d_scratch) + o_sort, n, tmp_bytes);
+    st.d_perm = B.i_out;
+    const TrainSource data = train_sections(h->learner.d_train_data, n);
+    for (int e = 0; e < n_epochs; e++) {
+        rc = enqueue_sampler(h, B, cfg->key, cfg->first_epoch + (uint32_t)e, n);
+        if (rc != SYN_OK) return rc;
+        hipLaunchKernelGGL(sampler_gather_kernel, dim3((unsigned)((ni * 16 + 255) / 256)), dim3(256), 0, h->stream, B.k_out, B.i_out, (int)ni,
+                           (int)n, cfg->flip == SYN_SAMPLER_FLIP_RANDOM ? 1 : 0, data.my, data.op, data.pi, data.v, st.batches.my,
+                           st.batches.op, st.batches.pi, st.batches.v);
+        HIP_TRY(h, hipGetLastError());
+        rc = run_staged_epoch(h, st, n_steps, batch, lr, step_losses ? step_losses + (size_t)e * n_steps * 2 : nullptr);
+        if (rc != SYN_OK) return rc;
+    }
+    if (n_steps_out) *n_steps_out = n_steps;
+    return SYN_OK;
+}
+
+int syn_debug_sampler(syn_engine* h, const syn_sampler_config* cfg, uint32_t epoch, size_t n, int32_t* perm_out, uint8_t* flip_out) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (!cfg || n < 1 || n > 0x7FFFFFFFu) return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_debug_sampler");
+    HIP_TRY(h, hipSetDevice(h->device));
+    size_t tmp_bytes = 0, sort_bytes = 0;
+    int rc = sampler_bytes(h, n, &tmp_bytes, &sort_bytes);
+    if (rc != SYN_OK) return rc;
+    rc = ensure_scratch(h, sort_bytes + sampler_pad(n) + 256);
+    if (rc != SYN_OK) return rc;
+    const SamplerBuffers B = sampler_buffers_at(h->d_scratch, n, tmp_bytes);
+    unsigned char* d_flip = static_cast<unsigned char*>(h->d_scratch) + sort_bytes;
+    rc = enqueue_sampler(h, B, cfg->key, epoch, n);
+    if (rc != SYN_OK) return rc;
+    hipLaunchKernelGGL(sampler_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, sampler_epoch_key(cfg->key, epoch),
+                       (int)n, d_flip);
+    HIP_TRY(h, hipGetLastError());
+    if (perm_out) HIP_TRY(h, hipMemcpyAsync(perm_out, B.i_out, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (flip_out) HIP_TRY(h, hipMemcpyAsync(flip_out, d_flip, n, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
 }
 
 int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads) {

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "syn_replay_deduplicate_to_trainer", "syn_train_get_data",
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
     "syn_match_run", "syn_match_run_sides", "syn_tournament_run", "syn_debug_tournament_regroup",
+    "syn_train_epochs_sampled", "syn_debug_sampler",
 ]
 TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
@@ -78,6 +79,10 @@ class CF16x2Plan(C.Structure):  # struct syn_f16x2_plan
 class CTrainConfig(C.Structure):  # struct syn_train_config
     _fields_ = [("weight_decay", C.c_float), ("policy_weight", C.c_float), ("value_weight", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float)]
+
+
+class CSamplerConfig(C.Structure):  # struct syn_sampler_config
+    _fields_ = [("key", C.c_uint64), ("first_epoch", C.c_uint32), ("flip", C.c_int32)]
 
 
 class CCounters(C.Structure):  # struct syn_counters
@@ -196,6 +201,9 @@ def load_library():
     lib.syn_trainer_publish_weights.argtypes = [C.c_void_p]
     lib.syn_train_set_data.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.syn_train_epoch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p]
+    lib.syn_train_epochs_sampled.argtypes = [C.c_void_p, C.POINTER(CSamplerConfig), C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                             C.POINTER(C.c_size_t)]
+    lib.syn_debug_sampler.argtypes = [C.c_void_p, C.POINTER(CSamplerConfig), C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.syn_replay_deduplicate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_size_t)]
@@ -800,6 +808,30 @@ class Engine:
         losses = np.zeros((steps, 2), np.float32)
         self._check(self._lib.syn_train_epoch(self._h, _p(perm), steps, int(batch_size), float(lr), _p(losses)))
         return losses
+
+    def train_epochs_sampled(self, key, n_epochs, batch_size, lr, first_epoch=0, flip=False):
+        """syn_train_epochs_sampled: the epochs first_epoch .. first_epoch + n_epochs - 1 over the current data set in ONE call, every
+        epoch's order (and, with flip=True, which rows enter mirrored) drawn on the device from `key` (include/synthesis_amd.h "Device-side
+        epoch sampler"). Returns the per-step losses [n_epochs, n_steps, 2], n_steps = rows // batch_size (drop_last)."""
+        n = C.c_size_t(0)
+        if self._lib.syn_train_get_data(self._h, None, None, None, None, 1 << 62, C.byref(n)) != 0:
+            n = C.c_size_t(0)   # (no trainer: the call below reports it)
+        per = int(n.value) // int(batch_size) if int(batch_size) >= 1 else 0
+        losses = np.zeros((max(int(n_epochs), 0), per, 2), np.float32)
+        cfg = CSamplerConfig(int(key) & 0xFFFFFFFFFFFFFFFF, int(first_epoch), int(bool(flip)) if isinstance(flip, (bool, np.bool_)) else int(flip))
+        steps = C.c_size_t()
+        self._check(self._lib.syn_train_epochs_sampled(self._h, C.byref(cfg), int(n_epochs), int(batch_size), float(lr), _p(losses),
+                                                       C.byref(steps)))
+        return losses[:, : int(steps.value)]
+
+    def debug_sampler(self, key, epoch, n, flip=False):
+        """syn_debug_sampler: (perm [n] int32 = epoch `epoch`'s row order, flags [n] uint8 by row = which rows flip=True would mirror)
+        for an n-row data set; needs no trainer. `flip` only fills the config: the flags do not depend on it."""
+        perm = np.zeros(int(n), np.int32)
+        flags = np.zeros(int(n), np.uint8)
+        cfg = CSamplerConfig(int(key) & 0xFFFFFFFFFFFFFFFF, 0, int(bool(flip)))
+        self._check(self._lib.syn_debug_sampler(self._h, C.byref(cfg), int(epoch), int(n), _p(perm), _p(flags)))
+        return perm, flags
 
     def trainer_publish_weights(self):
         self._check(self._lib.syn_trainer_publish_weights(self._h))

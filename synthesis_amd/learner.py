@@ -40,6 +40,12 @@ def _lr_at(schedule, i_iter):
     return lr
 
 
+def _sampler_key(seed, i_iter):
+    """sampler="device": the key of iteration i_iter's epochs (0-based, like _lr_at's) — (seed mod 2^32) * 2^32 + (i_iter mod 2^32), a
+    64-bit number; epoch e of the iteration is the sampler's epoch e (include/synthesis_amd.h "Device-side epoch sampler")"""
+    return ((int(seed) & 0xFFFFFFFF) << 32) | (int(i_iter) & 0xFFFFFFFF)
+
+
 class LearningLoop:
     """alpha_zero.rs:16-118 with self-play on every rank and the learner on rank 0 (see the module docstring).
 
@@ -57,6 +63,12 @@ class LearningLoop:
                  advanced epoch after epoch: the reference's algorithm and generator TYPE, not its stream — in a reference run
                  `tch::manual_seed(seed)` (alpha_zero.rs:28) is followed by `P::new(&vs)` (:31), whose parameter initialisation draws
                  from that same global generator before the first randperm, so the permutations of a Rust run differ
+                 | "device": the device-side epoch sampler — an iteration's epochs are ONE Engine.train_epochs_sampled call keyed by
+                 `_sampler_key(seed, iteration)`, the host draws no permutation and uploads no indices; a third definition of the
+                 order (include/synthesis_amd.h "Device-side epoch sampler"), same records in both replay modes
+    flip         sampler="device" only (else ValueError): every epoch mirrors a random half of the rows while it gathers them (the
+                 sampler's flip flags) — both orientations at the plain data set's epoch cost, where symmetry="mirror" doubles the
+                 data set. Whether it trains a stronger player is not measured (tools/arena.py).
     network_arithmetic  "f32" (default) | "f16x2": the arithmetic this rank's engine evaluates the network in during self-play
                  (include/synthesis_amd.h syn_set_network_arithmetic; both networks). The learner itself trains in `precision`.
     replay       "host" (default: the replay buffer is a dict of numpy arrays on the learner's rank; self-play downloads its padded
@@ -74,7 +86,15 @@ class LearningLoop:
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", **hyper):
+                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, **hyper):
+        if sampler not in ("numpy", "torch", "device"):
+            raise ValueError(f"sampler must be 'numpy', 'torch' or 'device', got {sampler!r}")
+        if flip and sampler != "device":
+            raise ValueError(f"flip=True needs sampler='device' (the flip is part of the device sampler's gather), got sampler={sampler!r}")
+        if replay not in ("host", "device"):
+            raise ValueError(f"replay must be 'host' or 'device', got {replay!r}")
+        if symmetry not in ("none", "mirror"):
+            raise ValueError(f"symmetry must be 'none' or 'mirror', got {symmetry!r}")
         import torch
 
         self._torch = torch
@@ -107,18 +127,13 @@ class LearningLoop:
                       v=np.zeros((0, 3), np.float32), gid=np.zeros(0, np.int64))
         self.games_played = 0
         self.iterations_done = 0
-        if sampler not in ("numpy", "torch"):
-            raise ValueError(f"sampler must be 'numpy' or 'torch', got {sampler!r}")
-        if replay not in ("host", "device"):
-            raise ValueError(f"replay must be 'host' or 'device', got {replay!r}")
-        if symmetry not in ("none", "mirror"):
-            raise ValueError(f"symmetry must be 'none' or 'mirror', got {symmetry!r}")
         self.batch_mode = batch_mode
         self.replay = replay
         self.symmetry = symmetry
         self._device = int(device)
         self._replay_reserved = 0
         self.sampler = sampler
+        self.flip = bool(flip)
         self._torch_gen = torch.Generator().manual_seed(self.seed) if sampler == "torch" else None
         self.logs_dir = logs_dir if self.rank == 0 else None
         if self.logs_dir:
@@ -283,17 +298,7 @@ class LearningLoop:
                 n_unique = self.engine.replay_deduplicate_to_trainer()
             t_dedup = time.perf_counter() - t2
             t3 = time.perf_counter()
-            steps, epoch_losses = 0, []
-            n_steps = n_unique // batch_size
-            for ep in range(epochs):
-                if self.sampler == "torch":
-                    perm = self._torch.randperm(n_unique, generator=self._torch_gen, dtype=self._torch.int64).numpy()
-                else:
-                    perm = np.random.default_rng([self.seed, it, ep]).permutation(n_unique)
-                if n_steps:
-                    sl = self.engine.train_epoch(perm[: n_steps * batch_size], batch_size, lr)
-                    epoch_losses.append((sl.astype(np.float64).sum(axis=0) * batch_size / n_unique).tolist())
-                steps += n_steps
+            steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=steps_in_buffer, unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
@@ -310,6 +315,25 @@ class LearningLoop:
                 np.save(os.path.join(self.logs_dir, "latest_vs.npy"), D["vs"])
         self._finish_iteration(rec, t0, t_play, t_gather, t_dedup, t_train)
         return rec
+
+    def _epochs(self, it, epochs, batch_size, lr, n_unique):
+        """Iteration `it`'s epochs of optimiser steps over the learner's data set of n_unique rows (alpha_zero.rs:72-94), both replay
+        modes: (optimiser steps, epoch_losses). The host samplers draw a permutation and make one train_epoch call per epoch;
+        sampler="device" is ONE call whose order the device draws from _sampler_key(seed, it)."""
+        n_steps = n_unique // batch_size   # drop_last = true (data.rs:41-62)
+        if self.sampler == "device":
+            per_epoch = self.engine.train_epochs_sampled(_sampler_key(self.seed, it), epochs, batch_size, lr, flip=self.flip)
+        else:
+            per_epoch = []
+            for ep in range(epochs):
+                if self.sampler == "torch":   # BatchRandSampler::new (data.rs:29)
+                    perm = self._torch.randperm(n_unique, generator=self._torch_gen, dtype=self._torch.int64).numpy()
+                else:
+                    perm = np.random.default_rng([self.seed, it, ep]).permutation(n_unique)
+                if n_steps:
+                    per_epoch.append(self.engine.train_epoch(perm[: n_steps * batch_size], batch_size, lr))
+        epoch_losses = [(sl.astype(np.float64).sum(axis=0) * batch_size / n_unique).tolist() for sl in per_epoch] if n_steps else []
+        return epochs * n_steps, epoch_losses
 
     def _finish_iteration(self, rec, t0, t_play, t_gather, t_dedup, t_train):
         """model_{i+1} (alpha_zero.rs:97,194): the trained parameters become every rank's self-play network; the record's timings"""
@@ -368,17 +392,7 @@ class LearningLoop:
             # ---- epochs of optimiser steps (alpha_zero.rs:72-94): one upload, one persistent kernel launch per epoch
             t3 = time.perf_counter()
             self.engine.train_set_data(D["my_bb"], D["op_bb"], D["pis"], D["vs"])
-            steps, epoch_losses = 0, []
-            n_steps = n_unique // batch_size   # drop_last = true (data.rs:41-62)
-            for ep in range(epochs):
-                if self.sampler == "torch":   # BatchRandSampler::new (data.rs:29)
-                    perm = self._torch.randperm(n_unique, generator=self._torch_gen, dtype=self._torch.int64).numpy()
-                else:
-                    perm = np.random.default_rng([self.seed, it, ep]).permutation(n_unique)
-                if n_steps:
-                    sl = self.engine.train_epoch(perm[: n_steps * batch_size], batch_size, lr)
-                    epoch_losses.append((sl.astype(np.float64).sum(axis=0) * batch_size / n_unique).tolist())
-                steps += n_steps
+            steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=int(self.R["my"].size), unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
