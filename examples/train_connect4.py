@@ -85,7 +85,14 @@ def main():
     ap.add_argument("--symmetry", default="none", choices=["none", "mirror"], help="mirror = the de-duplication merges a position with "
                     "its left-right mirror image and hands the learner both orientations (up to twice the data set per epoch; self-play "
                     "and the network are unchanged)")
+    ap.add_argument("--holdout", type=float, default=0.0, help="fraction of GAMES kept away from the learner: their positions become the "
+                    "engine's evaluation set and every iteration's record gains the held-out losses and accuracies of the weights before "
+                    "and after its epochs, on all held-out rows and on the unseen ones (0 = off; learning loop only)")
     args = ap.parse_args()
+    if args.holdout and args.data_parallel:
+        raise SystemExit("--holdout belongs to the learning loop: --data-parallel hands every position to the learner")
+    if not 0.0 <= args.holdout < 1.0:
+        raise SystemExit(f"--holdout is a fraction of games in [0, 1), got {args.holdout}")
     if args.replay != "host" and args.data_parallel:
         raise SystemExit("--replay device belongs to the learning loop: --data-parallel keeps one replay buffer per rank on the host")
     if args.sampler == "device" and args.data_parallel:
@@ -134,7 +141,7 @@ def main():
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
-                            batch_mode=args.batch_mode, flip=args.flip, **hyper)
+                            batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -666,6 +666,79 @@ int syn_replay_deduplicate_symmetric(syn_engine* h, const uint64_t* my_bb, const
  * *n_canonical = U, *n_total = U + M, either may be NULL. Same error codes. */
 int syn_replay_deduplicate_to_trainer_symmetric(syn_engine* h, size_t* n_canonical, size_t* n_total);
 
+/* ---- Held-out evaluation (csrc/dataset_eval.cuh; not in the reference): the losses of a set of parameters on a data
+ * set, forward only. Every other loss this library reports is the by-product of an optimiser step; this call is an OBSERVER: the
+ * trainer's weights, moments, step count and data set, the engine's network, arithmetic, f16x2 image, host blob, policy cache and replay
+ * buffer and the evaluation set are bit for bit what they were before it.
+ *
+ * The engine holds a second data set beside the learner's, the EVALUATION SET, in the same layout (my_bb[n], op_bb[n], pi[n][9],
+ * v[n][3]). No trainer call reads or writes it and it needs no trainer. syn_dataset_set uploads it from host arrays (n = 0 empties it,
+ * the pointers may then be NULL; n > 2^31 - 1 is SYN_ERR_INVALID_ARGUMENT); syn_dataset_get copies it out as syn_train_get_data does the
+ * learner's (arrays sized for `capacity` rows, any may be NULL; *n = the set's size, also on SYN_ERR_CAPACITY).
+ *
+ * syn_dataset_evaluate evaluates the rows [first_row, first_row + n_rows) of `which` — SYN_DATASET_TRAIN: the learner's current data
+ * set, SYN_DATASET_EVAL: the evaluation set — with the parameters
+ *   blob == NULL   the trainer's current weights (n_floats is ignored), or
+ *   blob != NULL   n_floats parameters on the host; n_floats selects the network (30492: Connect4Net, 12412: Connect4ConvNet). They are
+ *                  built into an image buffer the call owns; this form needs no trainer and no weights loaded into the engine.
+ * The definition is the f32 learner's. Row i of the range belongs to block j = i / 32; a block has rows_j = 32 rows, the last one
+ * n_rows mod 32 when that is not zero. Per block:
+ *   pi_loss_j, v_loss_j   bit for bit the two losses syn_train_gradients_device reports (chained mode, f32) for the block's rows as a
+ *                         minibatch of rows_j: the learner's forward, log_softmax and kl_div chain for chain, then bm * (kl_0 + kl_1 +
+ *                         ...) in row order with bm = 1.0f / rows_j — through the learners' parity the oracle's train_gradients /
+ *                         convtrain_gradients losses. policy_weight and value_weight do not enter, as they do not enter those losses.
+ *   pi_hit_j              rows whose arg-max of the nine policy logits over the LEGAL columns equals the arg-max of the target pi.
+ *                         Column c is legal when its top cell (bit 6 + 7 c of my | op) is free; a row without a legal column is a miss.
+ *   v_hit_j               rows whose arg-max of the three value logits equals the arg-max of the target v.
+ *   In all four arg-maxes the first maximum wins: the best is the first (legal) entry, and a later entry replaces it only when it
+ *   compares greater. An all-zero target row has KL 0 and arg-max 0.
+ * The totals, in an order that depends on n_rows alone (never on the grid):
+ *   chunk c = the blocks [256 c, 256 c + 256):  S_c = 0.0, then S_c = S_c + (double)rows_j * (double)loss_j in ascending j (the product
+ *   is exact in f64);  sum = 0.0, then sum = sum + S_c in ascending c;  mean = sum / (double)n_rows. The hit counts are integer sums.
+ * Outputs, each of which may be NULL: *out (below; `grid` = workgroups of the blocks launch); block_losses[n_blocks][2] = (pi_loss_j,
+ * v_loss_j); row_logits[n_rows][12] = the nine policy and three value logits of every row; row_kl[n_rows][2] = every row's two KL
+ * values (= the losses of the row as a minibatch of one). max_workgroups = 0 lets the library choose the grid, any other value caps it
+ * (the results do not depend on it). n_rows = 0 is SYN_OK with an all-zero *out and nothing launched. syn_last_timing reports the device
+ * time of the call's two launches (blocks, reduce).
+ * Refused, with everything unchanged: an unknown `which`, a negative max_workgroups, no data set (`which` is empty or was never set), a
+ * row range outside the set, a blob whose n_floats is neither network's (all SYN_ERR_INVALID_ARGUMENT); blob == NULL before
+ * syn_trainer_init* (SYN_ERR_NO_WEIGHTS).
+ * Out of scope: evaluation in the f16x2 arithmetic or in the conv learner's bf16 precision. A conv trainer in SYN_TRAIN_BF16 is
+ * evaluated in f32 like any other parameters. */
+typedef struct syn_dataset_metrics {
+    double mean_pi, mean_v;    /* sum_pi / rows, sum_v / rows (0 when rows = 0) */
+    double sum_pi, sum_v;      /* the two f64 sums defined above */
+    uint64_t rows, blocks;
+    uint64_t pi_hits, v_hits;
+    uint32_t grid, reserved;
+} syn_dataset_metrics;
+enum { SYN_DATASET_TRAIN = 0, SYN_DATASET_EVAL = 1 };
+int syn_dataset_set(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* target_pi, const float* target_v, size_t n);
+int syn_dataset_get(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity, size_t* n);
+int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int max_workgroups,
+                         syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl);
+
+/* ---- Holding games out (opt-in; csrc/replay_kernels.cuh). syn_replay_set_holdout sets a key and a threshold (at most 2^32, else
+ * SYN_ERR_INVALID_ARGUMENT); with sm as in "Device-side epoch sampler" above and all arithmetic unsigned 64-bit, game gid (its 64-bit
+ * pattern) is HELD OUT iff
+ *   (sm(sm(key ^ HOLDOUT_TAG, (uint32)(gid >> 32)), (uint32)gid) >> 32) < threshold,        HOLDOUT_TAG = 0x401D0075E7C0FFEE
+ * so about threshold / 2^32 of the games are, by game and never by position (the positions of one game are correlated), and a game
+ * keeps its side for as long as it stays in the buffer. threshold = 0, the default, switches it off: every call then does exactly
+ * what it did without this section.
+ * With a threshold above 0, syn_replay_deduplicate_to_trainer[_symmetric] split the buffer into the subsequence of the positions whose
+ * game is not held out and the subsequence of those whose game is (buffer order kept inside both: a flag kernel, a scan and a scatter),
+ * and run the de-duplication on either: the first result becomes the learner's data set and is what the call's counts describe, the
+ * second becomes the evaluation set. Both are bit for bit what syn_replay_deduplicate[_symmetric] returns for the two subsequences,
+ * except for the order of the evaluation set's rows: Connect4 openings recur across games, so a held-out state can also be in the
+ * learner's data set. A row is SEEN when its state — in the symmetric form: its canonical form — is among the learner's (canonical)
+ * rows, and the evaluation set is stored UNSEEN ROWS FIRST: the unseen rows in the order the de-duplication returned them, then the
+ * seen rows in that order (a stable partition; one binary search per row). syn_dataset_counts returns the set's size and the number of
+ * unseen rows, rows [0, n_unseen) (after syn_dataset_set: both its n), so that first_row / n_rows of syn_dataset_evaluate select
+ * either range. No game held out leaves an empty evaluation set. A threshold that holds out every game of the buffer is refused
+ * (SYN_ERR_INVALID_ARGUMENT) with both data sets unchanged: the learner would have nothing to train on. */
+int syn_replay_set_holdout(syn_engine* h, uint64_t key, uint64_t threshold);
+int syn_dataset_counts(syn_engine* h, size_t* n_eval, size_t* n_unseen);
+
 /* Timing of the last syn_selfplay_run / syn_mcts_search / *_device call on this handle, measured with HIP events on
  * the engine stream: kernel_ms = device time of the dominant kernel launch(es), n_launches = how many. */
 int syn_last_timing(const syn_engine* h, float* kernel_ms, int* n_launches);

@@ -39,6 +39,7 @@
 #include "train_conv.cuh"
 #include "train_conv_mfma.cuh"
 #include "train_micro.cuh"
+#include "dataset_eval.cuh"
 #include "lane_instances.h"
 #include "launch_plan.hpp"
 #include "free_kernel.cuh"
@@ -220,6 +221,15 @@ struct syn_engine {
         float* d_micro_rows = nullptr;  // the block buffer: row j = [g_j][l_j] of micro-batch j (MicroPlan::row_stride); grown on demand
         size_t micro_rows_bytes = 0;
     } learner;
+    // The evaluation set (syn_dataset_set / syn_dataset_get / syn_dataset_evaluate): a second data set in the learner's TrainSections
+    // layout that no trainer call reads or writes, and the image buffer a syn_dataset_evaluate with a blob of its own builds into.
+    struct EvalSet {
+        void* d_data = nullptr;
+        size_t cap = 0, n = 0;
+        size_t n_unseen = 0;      // rows [0, n_unseen): states that are not in the learner's data set (syn_dataset_counts); syn_dataset_set: n
+        uint64_t holdout_key = 0, holdout_threshold = 0;   // syn_replay_set_holdout; threshold 0 = nothing is held out
+        float* d_img = nullptr;   // sized for the larger of Connect4Net's f32 image and Connect4ConvNet's parameters; allocated on first use
+    } evalset;
 };
 
 // The learner's eleven device buffers: the one description used to allocate them (alloc_trainer_buffers: all of them or none) and to
@@ -637,6 +647,8 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_vw);
     hipFree(h->learner.d_train_data);
     hipFree(h->learner.d_micro_rows);
+    hipFree(h->evalset.d_data);
+    hipFree(h->evalset.d_img);
     hipFree(h->d_replay);
     hipFree(h->d_replay_alt);
     hipFree(h->d_cache);
@@ -2689,6 +2701,20 @@ static int ensure_train_data(syn_engine* h, size_t need, size_t grow_to) {
     return SYN_OK;
 }
 
+// the same for the evaluation set (syn_engine::EvalSet)
+static int ensure_eval_data(syn_engine* h, size_t need, size_t grow_to) {
+    auto& E = h->evalset;
+    if (need <= E.cap) return SYN_OK;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    (void)hipFree(E.d_data);
+    E.d_data = nullptr;
+    E.cap = 0;
+    E.n = E.n_unseen = 0;
+    HIP_TRY(h, hipMalloc(&E.d_data, grow_to * 64));
+    E.cap = grow_to;
+    return SYN_OK;
+}
+
 // SYN_TRAIN_BATCH_MICRO's refusals, before anything is staged or launched: the learner is left as it was
 static_assert(PLAN_MICRO_BLOCK == MICRO_BLOCK && PLAN_MICRO_MAX_BLOCKS == MICRO_MAX_BLOCKS && PLAN_MLP_NUM_PARAMS == TrainGeom::NUM_PARAMS &&
                   PLAN_CONV_NUM_PARAMS == ConvGeom::NUM_PARAMS && PLAN_MICRO_MLP_LDS == (size_t)TrainGeom::WL_OFF * 4 &&
@@ -3773,6 +3799,114 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
     return SYN_OK;
 }
 
+// syn_replay_deduplicate_to_trainer[_symmetric] with games held out (syn_replay_set_holdout; replay_kernels.cuh "holding games out"):
+// the buffer is stably partitioned by the games' flag into a second set of sections, the de-duplication core runs on either part, the
+// part that is not held out becomes the learner's data set and the held-out part, its unseen rows first, the evaluation set. Scratch:
+//   [the partitioned rows: my | op | pi | v of n][flags of 2n][ranks of 2n][cub temp][the core's work area, sized for the larger part]
+// (the caller has checked the trainer, n >= 1 and the symmetric form's bound)
+static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_canonical, size_t* n_unique) {
+    auto& E = h->evalset;
+    const size_t n = h->replay_n;
+    const int ni = (int)n;
+    const size_t rows_max = mirror ? 2 * n : n;   // rows of a de-duplicated part
+    size_t tmp_scan = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, (int)rows_max, h->stream));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
+    const size_t o_part = take(n * 64), o_flag = take(rows_max * 4), o_rank = take(rows_max * 4), o_tmp = take(tmp_scan);
+    const size_t o_work = off;
+    int rc = ensure_scratch(h, o_work + 4096);
+    if (rc != SYN_OK) return rc;
+    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    auto U = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
+    auto W = [](void* p) { return reinterpret_cast<unsigned*>(p); };
+    // ---- the split by game: flags and their ranks (enqueued; run again if the scratch buffer has to grow for the work area)
+    auto flags_and_ranks = [&]() -> int {
+        char* b = static_cast<char*>(h->d_scratch);
+        hipLaunchKernelGGL(replay_holdout_flags_kernel, dim3((ni + 255) / 256), dim3(256), 0, h->stream, cur.gid, ni,
+                           (unsigned long long)(E.holdout_key ^ HOLDOUT_TAG), (unsigned long long)E.holdout_threshold,
+                           reinterpret_cast<unsigned*>(b + o_flag));
+        HIP_TRY(h, hipGetLastError());
+        size_t t = tmp_scan;
+        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(b + o_tmp, t, reinterpret_cast<unsigned*>(b + o_flag), reinterpret_cast<unsigned*>(b + o_rank), ni,
+                                                    h->stream));
+        return SYN_OK;
+    };
+    rc = flags_and_ranks();
+    if (rc != SYN_OK) return rc;
+    unsigned last[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(&last[0], static_cast<char*>(h->d_scratch) + o_rank + (size_t)(ni - 1) * 4, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last[1], static_cast<char*>(h->d_scratch) + o_flag + (size_t)(ni - 1) * 4, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t n_held = (size_t)last[0] + last[1];
+    if (n_held > n) return fail(h, SYN_ERR_HIP, "internal: %zu of %zu positions held out", n_held, n);
+    const size_t n_train = n - n_held;
+    if (n_train == 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "the holdout threshold holds out every game of the buffer: the learner would have no data set");
+    size_t tmp_t = 0, work_t = 0, tmp_h = 0, work_h = 0;
+    rc = dedup_work_bytes(h, n_train, &tmp_t, &work_t, mirror);
+    if (rc == SYN_OK && n_held > 0) rc = dedup_work_bytes(h, n_held, &tmp_h, &work_h, mirror);
+    if (rc != SYN_OK) return rc;
+    const size_t need = o_work + (work_t > work_h ? work_t : work_h) + 4096;
+    if (need > h->scratch_bytes) {
+        rc = ensure_scratch(h, need);
+        if (rc == SYN_OK) rc = flags_and_ranks();
+        if (rc != SYN_OK) return rc;
+    }
+    char* sc = static_cast<char*>(h->d_scratch);
+    unsigned* d_flag = reinterpret_cast<unsigned*>(sc + o_flag);
+    unsigned* d_rank = reinterpret_cast<unsigned*>(sc + o_rank);
+    const TrainSections part = train_sections(sc + o_part, n);
+    hipLaunchKernelGGL(replay_partition_scatter_kernel, dim3((unsigned)((n * 9 + 255) / 256), 4), dim3(256), 0, h->stream, d_flag, d_rank, ni,
+                       (unsigned)n_train, U(cur.my), U(cur.op), U(cur.pi), U(cur.v), W(part.my), W(part.op), W(part.pi), W(part.v));
+    HIP_TRY(h, hipGetLastError());
+    // ---- the learner's data set: the part that is not held out
+    DedupOut o;
+    rc = dedup_device_core(h, sc + o_work, tmp_t, part.my, part.op, part.pi, part.v, n_train, &o, mirror);
+    if (rc != SYN_OK) return rc;
+    const size_t m = (size_t)o.total, m_canonical = (size_t)o.m;
+    if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n_train);
+    rc = ensure_train_data(h, m, m + m / 4);
+    if (rc != SYN_OK) return rc;
+    const TrainSections tr = train_sections(h->learner.d_train_data, m);
+    rc = train_copy(h, tr, TrainSource{o.my, o.op, o.pi, o.v}, m, hipMemcpyDeviceToDevice);
+    if (rc != SYN_OK) return rc;
+    h->learner.train_data_n = m;
+    if (n_unique) *n_unique = m;
+    if (n_canonical) *n_canonical = m_canonical;
+    // ---- the evaluation set: the held-out part, its unseen rows first
+    E.n = E.n_unseen = 0;
+    if (n_held == 0) return SYN_OK;
+    DedupOut e;
+    rc = dedup_device_core(h, sc + o_work, tmp_h, part.my + n_train, part.op + n_train, part.pi + n_train * 9, part.v + n_train * 3, n_held, &e,
+                           mirror);
+    if (rc != SYN_OK) return rc;
+    const size_t me = (size_t)e.total;
+    if (me == 0 || me > rows_max) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu held-out positions reported %zu rows", n_held, me);
+    rc = ensure_eval_data(h, me, me + me / 4);
+    if (rc != SYN_OK) return rc;
+    // seen = the state (symmetric: its canonical form) is among the learner's rows [0, m_canonical): sorted ascending by (my, op)
+    const int mei = (int)me;
+    hipLaunchKernelGGL(replay_seen_flags_kernel, dim3((mei + 255) / 256), dim3(256), 0, h->stream, e.my, e.op, mei, tr.my, tr.op,
+                       (int)m_canonical, mirror ? 1 : 0, d_flag);
+    HIP_TRY(h, hipGetLastError());
+    size_t t1 = tmp_scan;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(sc + o_tmp, t1, d_flag, d_rank, mei, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last[0], d_rank + (mei - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last[1], d_flag + (mei - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t n_seen = (size_t)last[0] + last[1];
+    if (n_seen > me) return fail(h, SYN_ERR_HIP, "internal: %zu of %zu held-out rows seen", n_seen, me);
+    const TrainSections ev = train_sections(E.d_data, me);
+    hipLaunchKernelGGL(replay_partition_scatter_kernel, dim3((unsigned)((me * 9 + 255) / 256), 4), dim3(256), 0, h->stream, d_flag, d_rank, mei,
+                       (unsigned)(me - n_seen), U(e.my), U(e.op), U(e.pi), U(e.v), W(ev.my), W(ev.op), W(ev.pi), W(ev.v));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    E.n = me;
+    E.n_unseen = me - n_seen;
+    return SYN_OK;
+}
+
 // (the entry points have selected the engine's device)
 static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_canonical, size_t* n_unique) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
@@ -3783,6 +3917,7 @@ static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_c
     if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "the replay buffer is empty");
     if (mirror && n > DEDUP_MIRROR_MAX_N)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "the symmetric de-duplication takes at most %zu positions", DEDUP_MIRROR_MAX_N);
+    if (h->evalset.holdout_threshold != 0) return replay_deduplicate_holdout(h, mirror, n_canonical, n_unique);
     size_t tmp = 0, work = 0;
     int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
     if (rc != SYN_OK) return rc;
@@ -3803,6 +3938,15 @@ static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_c
     h->learner.train_data_n = m;
     if (n_unique) *n_unique = m;
     if (n_canonical) *n_canonical = (size_t)o.m;
+    return SYN_OK;
+}
+
+int syn_replay_set_holdout(syn_engine* h, uint64_t key, uint64_t threshold) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (threshold > (1ull << 32)) return fail(h, SYN_ERR_INVALID_ARGUMENT, "the holdout threshold is at most 2^32 (got %llu)", (unsigned long long)threshold);
+    HIP_TRY(h, hipSetDevice(h->device));   // (as every entry point that belongs to a device: the next call's kernels read these two words)
+    h->evalset.holdout_key = key;
+    h->evalset.holdout_threshold = threshold;
     return SYN_OK;
 }
 
@@ -3833,6 +3977,166 @@ int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* t
     if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, data.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
     if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, data.v, m * 12, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ held-out evaluation
+// (dataset_eval.cuh; include/synthesis_amd.h "Held-out evaluation")
+static_assert(sizeof(DsBlockRecord) == 32 && sizeof(DsChunkSum) == 40 && sizeof(DsTotals) == 40, "dataset_eval.cuh's records");
+static_assert((size_t)ConvGeom::NUM_PARAMS <= (size_t)MlpGeom::IMG_FLOATS, "the evaluation's image buffer holds either network");
+
+int syn_dataset_set(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const float* target_pi, const float* target_v, size_t n) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n > 0x7FFFFFFFu || (n > 0 && (!my_bb || !op_bb || !target_pi || !target_v)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_dataset_set");
+    HIP_TRY(h, hipSetDevice(h->device));
+    auto& E = h->evalset;
+    if (n == 0) {
+        E.n = E.n_unseen = 0;
+        return SYN_OK;
+    }
+    int rc = ensure_eval_data(h, n, n);
+    if (rc != SYN_OK) return rc;
+    E.n = E.n_unseen = 0;
+    rc = train_copy(h, train_sections(E.d_data, n), train_source(my_bb, op_bb, target_pi, target_v), n, hipMemcpyHostToDevice);
+    if (rc != SYN_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    E.n = E.n_unseen = n;
+    return SYN_OK;
+}
+
+int syn_dataset_counts(syn_engine* h, size_t* n_eval, size_t* n_unseen) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (n_eval) *n_eval = h->evalset.n;
+    if (n_unseen) *n_unseen = h->evalset.n_unseen;
+    return SYN_OK;
+}
+
+int syn_dataset_get(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity, size_t* n) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    const size_t m = h->evalset.n;
+    if (n) *n = m;
+    if (m > capacity) return fail(h, SYN_ERR_CAPACITY, "the evaluation set has %zu rows, the caller's arrays %zu", m, capacity);
+    if (m == 0) return SYN_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const TrainSections data = train_sections(h->evalset.d_data, m);
+    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, data.my, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, data.op, m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, data.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
+    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, data.v, m * 12, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
+}
+
+int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int max_workgroups,
+                         syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (which != SYN_DATASET_TRAIN && which != SYN_DATASET_EVAL) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown data set %d", which);
+    if (max_workgroups < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "max_workgroups is negative (%d); 0 lets the library choose", max_workgroups);
+    auto& L = h->learner;
+    const size_t set_n = which == SYN_DATASET_TRAIN ? L.train_data_n : h->evalset.n;
+    void* set_base = which == SYN_DATASET_TRAIN ? L.d_train_data : h->evalset.d_data;
+    if (set_n == 0 || !set_base)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "%s", which == SYN_DATASET_TRAIN ? "the learner has no data set" : "there is no evaluation set");
+    if (first_row > set_n || n_rows > set_n - first_row)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "rows [%zu, %zu + %zu) are outside the data set's %zu rows", first_row, first_row, n_rows, set_n);
+    int kind;
+    if (blob) {
+        if (n_floats == (size_t)MlpGeom::NUM_PARAMS) kind = 0;
+        else if (n_floats == (size_t)ConvGeom::NUM_PARAMS) kind = 1;
+        else
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "Connect4Net has %d parameters, Connect4ConvNet %d, got %zu", MlpGeom::NUM_PARAMS,
+                        ConvGeom::NUM_PARAMS, n_floats);
+    } else {
+        if (!L.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "blob is NULL (the trainer's weights): call syn_trainer_init first");
+        kind = L.trainer_kind;
+    }
+    syn_dataset_metrics m;
+    std::memset(&m, 0, sizeof(m));
+    h->last_kernel_ms = 0.0f;
+    h->last_launches = 0;
+    if (n_rows == 0) {
+        if (out) *out = m;
+        return SYN_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t nb = (n_rows + DS_BLOCK - 1) / DS_BLOCK, nch = (nb + DS_CHUNK_BLOCKS - 1) / DS_CHUNK_BLOCKS;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
+    const size_t o_rec = take(nb * sizeof(DsBlockRecord)), o_chunk = take(nch * sizeof(DsChunkSum)), o_tot = take(sizeof(DsTotals));
+    const size_t o_bl = take(block_losses ? nb * 8 : 0), o_lg = take(row_logits ? n_rows * 48 : 0), o_kl = take(row_kl ? n_rows * 8 : 0);
+    int rc = ensure_scratch(h, off + 256);
+    if (rc != SYN_OK) return rc;
+    char* sc = static_cast<char*>(h->d_scratch);
+    // the parameters: the trainer's own buffers (read only), or the caller's blob built into the evaluation's own image buffer
+    HostImage im;
+    const float* d_w;
+    if (blob) {
+        auto& E = h->evalset;
+        if (!E.d_img) HIP_TRY(h, hipMalloc(&E.d_img, (size_t)MlpGeom::IMG_FLOATS * 4));
+        if (kind == 0) {
+            rc = build_host_image(h, 0, blob, false, im);
+            if (rc == SYN_OK) rc = enqueue_image_upload(h, im, E.d_img);
+            if (rc != SYN_OK) return rc;
+        } else {
+            HIP_TRY(h, hipMemcpyAsync(E.d_img, blob, (size_t)ConvGeom::NUM_PARAMS * 4, hipMemcpyHostToDevice, h->stream));
+        }
+        d_w = E.d_img;
+    } else {
+        d_w = kind == 0 ? L.d_twimg : L.d_tw;
+    }
+    const TrainSections s = train_sections(set_base, set_n);
+    DsArgs A;
+    A.my_bb = s.my + first_row;
+    A.op_bb = s.op + first_row;
+    A.tpi = s.pi + first_row * 9;
+    A.tv = s.v + first_row * 3;
+    A.n = (long long)n_rows;
+    A.n_blocks = (long long)nb;
+    A.records = reinterpret_cast<DsBlockRecord*>(sc + o_rec);
+    A.block_losses = block_losses ? reinterpret_cast<float*>(sc + o_bl) : nullptr;
+    A.row_logits = row_logits ? reinterpret_cast<float*>(sc + o_lg) : nullptr;
+    A.row_kl = row_kl ? reinterpret_cast<float*>(sc + o_kl) : nullptr;
+    // the library's choice: two workgroups of either kernel are resident on a CU (8 waves each at 4 waves per SIMD);
+    // Connect4Net gets exactly those, Connect4ConvNet twice as many, the second half taking the CUs as the first drains
+    const size_t fit = (size_t)h->num_cus * (kind == 0 ? 2 : 4);
+    const size_t cap = max_workgroups > 0 ? (size_t)max_workgroups : fit;
+    const unsigned grid = (unsigned)(nb < cap ? nb : cap);
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    if (kind == 0) {
+        const size_t lds = (size_t)DsMlpGeom::LDS_FLOATS * 4;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dataset_eval_blocks_kernel, dim3(grid), dim3(DS_MLP_THREADS), lds, h->stream, d_w, A);
+    } else {
+        const size_t lds = (size_t)DsConvGeom::LDS_FLOATS * 4;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dataset_eval_blocks_conv_kernel, dim3(grid), dim3(CONV_TRAIN_THREADS), lds, h->stream, d_w, A);
+    }
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(dataset_eval_reduce_kernel, dim3(1), dim3(DS_REDUCE_THREADS), 0, h->stream, A.records, A.n_blocks,
+                       reinterpret_cast<DsChunkSum*>(sc + o_chunk), reinterpret_cast<DsTotals*>(sc + o_tot));
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    DsTotals t;
+    HIP_TRY(h, hipMemcpyAsync(&t, sc + o_tot, sizeof(t), hipMemcpyDeviceToHost, h->stream));
+    if (block_losses) HIP_TRY(h, hipMemcpyAsync(block_losses, sc + o_bl, nb * 8, hipMemcpyDeviceToHost, h->stream));
+    if (row_logits) HIP_TRY(h, hipMemcpyAsync(row_logits, sc + o_lg, n_rows * 48, hipMemcpyDeviceToHost, h->stream));
+    if (row_kl) HIP_TRY(h, hipMemcpyAsync(row_kl, sc + o_kl, n_rows * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
+    h->last_launches = 2;
+    if (t.rows != (unsigned long long)n_rows) return fail(h, SYN_ERR_HIP, "internal: the block records cover %llu rows of %zu", t.rows, n_rows);
+    m.rows = (uint64_t)n_rows;
+    m.blocks = (uint64_t)nb;
+    m.mean_pi = t.sum_pi / (double)n_rows;
+    m.mean_v = t.sum_v / (double)n_rows;
+    m.sum_pi = t.sum_pi;
+    m.sum_v = t.sum_v;
+    m.pi_hits = t.pi_hits;
+    m.v_hits = t.v_hits;
+    m.grid = grid;
+    if (out) *out = m;
     return SYN_OK;
 }
 

@@ -7,6 +7,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "noise.cuh"
+
 namespace syn {
 
 constexpr int REPLAY_T = 63;  // Connect4::MAX_TURNS: slots per game in syn_selfplay_run's outputs
@@ -64,6 +66,67 @@ __global__ void replay_keep_scatter_kernel(const unsigned* __restrict__ keep, co
     const unsigned* s = sec == 0 ? s_my : sec == 1 ? s_op : sec == 2 ? s_gid : sec == 3 ? s_pi : s_v;
     unsigned* d = sec == 0 ? d_my : sec == 1 ? d_op : sec == 2 ? d_gid : sec == 3 ? d_pi : d_v;
     d[(size_t)dst[i] * W + c] = s[t];
+}
+
+// ---------------------------------------------------------------------------------------------- holding games out
+// syn_replay_set_holdout (include/synthesis_amd.h "Holding games out"): game gid is held out iff
+//     (sm(sm(key ^ HOLDOUT_TAG, (uint32)(gid >> 32)), (uint32)gid) >> 32) < threshold,     sm = noise_splitmix64
+// — by game, not by position: the positions of one game are correlated. Step 1: held[i] = 1 where position i's game is held out.
+constexpr unsigned long long HOLDOUT_TAG = 0x401D0075E7C0FFEEull;
+__global__ void replay_holdout_flags_kernel(const long long* __restrict__ gid, int n, unsigned long long tagged_key,
+                                            unsigned long long threshold, unsigned* __restrict__ held) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long g = (unsigned long long)gid[i];
+    const unsigned long long hash = noise_splitmix64(noise_splitmix64(tagged_key, (uint32_t)(g >> 32)), (uint32_t)g) >> 32;
+    held[i] = hash < threshold ? 1u : 0u;
+}
+
+// Stable two-way partition of n rows of four sections (my u64 | op u64 | pi [9] f32 | v [3] f32), step 2 after the exclusive sum `rank`
+// of the flags: a row with flag 0 moves to its rank among the flag-0 rows (i - rank[i]), a row with flag 1 to n_first + rank[i], where
+// n_first = the number of flag-0 rows. Order is kept inside both parts. blockIdx.y = section, a thread moves one dword (as
+// replay_keep_scatter_kernel). Destination indices are bounded by n: a corrupt rank must not write outside the sections.
+__global__ void replay_partition_scatter_kernel(const unsigned* __restrict__ flag, const unsigned* __restrict__ rank, int n, unsigned n_first,
+                                                const unsigned* __restrict__ s_my, const unsigned* __restrict__ s_op,
+                                                const unsigned* __restrict__ s_pi, const unsigned* __restrict__ s_v,
+                                                unsigned* __restrict__ d_my, unsigned* __restrict__ d_op, unsigned* __restrict__ d_pi,
+                                                unsigned* __restrict__ d_v) {
+    const int sec = blockIdx.y;
+    const int W = sec < 2 ? 2 : (sec == 2 ? 9 : 3);
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)n * W) return;
+    const unsigned i = (unsigned)(t / W), c = (unsigned)(t % W);
+    const unsigned to = flag[i] ? n_first + rank[i] : i - rank[i];
+    if (to >= (unsigned)n) return;
+    const unsigned* s = sec == 0 ? s_my : sec == 1 ? s_op : sec == 2 ? s_pi : s_v;
+    unsigned* d = sec == 0 ? d_my : sec == 1 ? d_op : sec == 2 ? d_pi : d_v;
+    d[(size_t)to * W + c] = s[t];
+}
+
+__device__ __forceinline__ unsigned long long mirror_bb(unsigned long long b);
+// seen[i] = 1 where row i's state — with `mirror` its canonical form (the smaller of the pair and its mirror image, my first) — is
+// among the n_t rows (t_my, t_op), which are sorted ascending by (my, op): one binary search per row.
+__global__ void replay_seen_flags_kernel(const unsigned long long* __restrict__ my, const unsigned long long* __restrict__ op, int n,
+                                         const unsigned long long* __restrict__ t_my, const unsigned long long* __restrict__ t_op, int n_t,
+                                         int mirror, unsigned* __restrict__ seen) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    unsigned long long a = my[i], b = op[i];
+    if (mirror) {
+        const unsigned long long ma = mirror_bb(a), mb = mirror_bb(b);
+        if (ma < a || (ma == a && mb < b)) {
+            a = ma;
+            b = mb;
+        }
+    }
+    int lo = 0, hi = n_t;   // first row not below (a, b)
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        const unsigned long long x = t_my[mid], y = t_op[mid];
+        if (x < a || (x == a && y < b)) lo = mid + 1;
+        else hi = mid;
+    }
+    seen[i] = (lo < n_t && t_my[lo] == a && t_op[lo] == b) ? 1u : 0u;
 }
 
 // ---------------------------------------------------------------------------------------------- mirror symmetry

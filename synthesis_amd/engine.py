@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
     "syn_match_run", "syn_match_run_sides", "syn_tournament_run", "syn_debug_tournament_regroup",
     "syn_train_epochs_sampled", "syn_debug_sampler",
+    "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_replay_set_holdout", "syn_dataset_counts",
 ]
 TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
@@ -83,6 +84,15 @@ class CTrainConfig(C.Structure):  # struct syn_train_config
 
 class CSamplerConfig(C.Structure):  # struct syn_sampler_config
     _fields_ = [("key", C.c_uint64), ("first_epoch", C.c_uint32), ("flip", C.c_int32)]
+
+
+class CDatasetMetrics(C.Structure):  # struct syn_dataset_metrics
+    _fields_ = [("mean_pi", C.c_double), ("mean_v", C.c_double), ("sum_pi", C.c_double), ("sum_v", C.c_double),
+                ("rows", C.c_uint64), ("blocks", C.c_uint64), ("pi_hits", C.c_uint64), ("v_hits", C.c_uint64),
+                ("grid", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DATASETS = {"train": 0, "eval": 1}   # SYN_DATASET_*
 
 
 class CCounters(C.Structure):  # struct syn_counters
@@ -222,6 +232,16 @@ def load_library():
     lib.syn_replay_deduplicate_symmetric.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t] + [C.c_void_p] * 5 + [
         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     lib.syn_replay_deduplicate_to_trainer_symmetric.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    # held-out evaluation: the in-tree library has these (a missing one raises here); an older build of the ABI that SYNTHESIS_AMD_LIB
+    # names for an A/B arm may not
+    for name, argtypes in (("syn_dataset_set", [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t]),
+                           ("syn_dataset_get", [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(C.c_size_t)]),
+                           ("syn_dataset_evaluate", [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                                     C.POINTER(CDatasetMetrics), C.c_void_p, C.c_void_p, C.c_void_p]),
+                           ("syn_replay_set_holdout", [C.c_void_p, C.c_uint64, C.c_uint64]),
+                           ("syn_dataset_counts", [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])):
+        if hasattr(lib, name) or not os.environ.get("SYNTHESIS_AMD_LIB"):
+            getattr(lib, name).argtypes = argtypes
     _lib = lib
     return lib
 
@@ -955,6 +975,73 @@ class Engine:
         o = dict(my_bb=np.zeros(n, np.uint64), op_bb=np.zeros(n, np.uint64), pis=np.zeros((n, 9), np.float32), vs=np.zeros((n, 3), np.float32))
         self._check(self._lib.syn_train_get_data(self._h, _p(o["my_bb"]), _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), n, None))
         return o
+
+    # ---- held-out evaluation (include/synthesis_amd.h "Held-out evaluation")
+    def dataset_set(self, my_bb, op_bb, target_pi, target_v):
+        """Uploads the evaluation set: a second data set beside the learner's that no trainer call touches; needs no trainer."""
+        my = np.ascontiguousarray(my_bb, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(op_bb, dtype=np.uint64).ravel()
+        if op.size != my.size:
+            raise ValueError("my_bb and op_bb must have the same length")
+        tpi = np.ascontiguousarray(target_pi, dtype=np.float32).reshape(my.size, 9)
+        tv = np.ascontiguousarray(target_v, dtype=np.float32).reshape(my.size, 3)
+        self._check(self._lib.syn_dataset_set(self._h, _p(my), _p(op), _p(tpi), _p(tv), int(my.size)))
+
+    def dataset_get(self):
+        """The evaluation set as host arrays: dict(my_bb, op_bb, pis [n, 9], vs [n, 3]) — train_get_data's keys."""
+        n = C.c_size_t()
+        self._check(self._lib.syn_dataset_get(self._h, None, None, None, None, 1 << 62, C.byref(n)))
+        n = int(n.value)
+        o = dict(my_bb=np.zeros(n, np.uint64), op_bb=np.zeros(n, np.uint64), pis=np.zeros((n, 9), np.float32), vs=np.zeros((n, 3), np.float32))
+        self._check(self._lib.syn_dataset_get(self._h, _p(o["my_bb"]), _p(o["op_bb"]), _p(o["pis"]), _p(o["vs"]), n, None))
+        return o
+
+    def replay_set_holdout(self, key, threshold):
+        """syn_replay_set_holdout: with threshold > 0 (of 2^32), replay_deduplicate_to_trainer hands the games whose hash under `key` falls
+        below it to the evaluation set instead of the learner (include/synthesis_amd.h "Holding games out"); 0 switches it off."""
+        self._check(self._lib.syn_replay_set_holdout(self._h, int(key) & 0xFFFFFFFFFFFFFFFF, int(threshold)))
+
+    def dataset_counts(self):
+        """(rows of the evaluation set, how many of them — the leading ones — are states the learner's data set does not contain)"""
+        n, u = C.c_size_t(), C.c_size_t()
+        self._check(self._lib.syn_dataset_counts(self._h, C.byref(n), C.byref(u)))
+        return int(n.value), int(u.value)
+
+    def dataset_evaluate(self, which="eval", first_row=0, n_rows=None, blob=None, max_workgroups=0, blocks=False, rows=False):
+        """syn_dataset_evaluate: the f32 learner's losses of `blob` (None: the trainer's current weights) on the rows
+        [first_row, first_row + n_rows) of the learner's data set (which="train") or the evaluation set ("eval"); n_rows=None = to the
+        end of the set. Forward only: nothing of the trainer or the engine changes. Returns dict(mean_pi, mean_v, sum_pi, sum_v (f64),
+        rows, blocks, pi_hits, v_hits, pi_acc, v_acc, grid); blocks=True adds block_losses [n_blocks, 2], rows=True row_logits
+        [n_rows, 12] and row_kl [n_rows, 2]."""
+        if which not in DATASETS:
+            raise ValueError(f"which must be 'train' or 'eval', got {which!r}")
+        if n_rows is None:
+            size = C.c_size_t(0)
+            if which == "train":
+                if self._lib.syn_train_get_data(self._h, None, None, None, None, 1 << 62, C.byref(size)) != 0:
+                    size = C.c_size_t(0)   # (no trainer: no data set, which the call below reports)
+            else:
+                self._check(self._lib.syn_dataset_get(self._h, None, None, None, None, 1 << 62, C.byref(size)))
+            n_rows = max(int(size.value) - int(first_row), 0)
+        n_rows = int(n_rows)
+        nb = (n_rows + 31) // 32
+        if blob is not None:
+            blob = np.ascontiguousarray(blob, dtype=np.float32).ravel()
+        bl = np.zeros((nb, 2), np.float32) if blocks else None
+        lg = np.zeros((n_rows, 12), np.float32) if rows else None
+        kl = np.zeros((n_rows, 2), np.float32) if rows else None
+        m = CDatasetMetrics()
+        self._check(self._lib.syn_dataset_evaluate(self._h, DATASETS[which], int(first_row), n_rows, _p(blob), 0 if blob is None else int(blob.size),
+                                                   int(max_workgroups), C.byref(m), _p(bl), _p(lg), _p(kl)))
+        out = dict(mean_pi=float(m.mean_pi), mean_v=float(m.mean_v), sum_pi=float(m.sum_pi), sum_v=float(m.sum_v), rows=int(m.rows),
+                   blocks=int(m.blocks), pi_hits=int(m.pi_hits), v_hits=int(m.v_hits), grid=int(m.grid),
+                   pi_acc=m.pi_hits / m.rows if m.rows else 0.0, v_acc=m.v_hits / m.rows if m.rows else 0.0)
+        if blocks:
+            out["block_losses"] = bl
+        if rows:
+            out["row_logits"] = lg
+            out["row_kl"] = kl
+        return out
 
     # ---- parity probes
     def debug_stdrng_u32(self, seed, n):

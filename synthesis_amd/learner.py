@@ -46,6 +46,36 @@ def _sampler_key(seed, i_iter):
     return ((int(seed) & 0xFFFFFFFF) << 32) | (int(i_iter) & 0xFFFFFFFF)
 
 
+_M64 = (1 << 64) - 1
+HOLDOUT_TAG = 0x401D0075E7C0FFEE   # include/synthesis_amd.h "Holding games out"
+
+
+def _holdout_key(seed):
+    """holdout > 0: the key of the run's split of games — (seed mod 2^32) * 2^32, the high half of every _sampler_key of the run (the
+    two hashes carry different tags)"""
+    return (int(seed) & 0xFFFFFFFF) << 32
+
+
+def _sm(seed, idx):
+    """csrc/noise.cuh noise_splitmix64 on numpy uint64 arrays (include/synthesis_amd.h "Device-side epoch sampler"): idx + 1 in 32 bits"""
+    with np.errstate(over="ignore"):
+        z = np.asarray(seed, np.uint64) + ((np.asarray(idx, np.uint64) + np.uint64(1)) & np.uint64(0xFFFFFFFF)) * np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def holdout_flags(key, threshold, gid):
+    """Which game ids are held out under (key, threshold): the header's definition on the host (replay="host"; the device applies it in
+    replay_holdout_flags_kernel)."""
+    g = np.asarray(gid, np.int64).astype(np.uint64)
+    h = _sm(_sm(np.uint64((int(key) & _M64) ^ HOLDOUT_TAG), g >> np.uint64(32)), g & np.uint64(0xFFFFFFFF)) >> np.uint64(32)
+    return h < np.uint64(int(threshold))
+
+
+_METRIC_KEYS = ("rows", "mean_pi", "mean_v", "pi_acc", "v_acc")
+
+
 class LearningLoop:
     """alpha_zero.rs:16-118 with self-play on every rank and the learner on rank 0 (see the module docstring).
 
@@ -80,13 +110,22 @@ class LearningLoop:
                  replay_deduplicate_to_trainer(symmetry="mirror"); DESIGN.md "Mirror-symmetric de-duplication"): `unique` counts the
                  canonical states and their mirror images, the record gains `unique_canonical`, latest_*.npy hold the augmented set.
                  Self-play, the buffer and the network are untouched. Both replay modes, same bits.
+    holdout      0.0 (default: nothing is held out, every bit and every record as without the argument) | a fraction of GAMES in (0, 1):
+                 the games whose hash under `_holdout_key(seed)` falls below floor(holdout * 2^32) (include/synthesis_amd.h "Holding games
+                 out") never reach the learner; their de-duplicated positions are the engine's evaluation set, unseen states first. The
+                 record gains `holdout_rows`, `holdout_unseen` and `holdout_before` / `holdout_after`: the f32 learner's losses and
+                 arg-max accuracies (Engine.dataset_evaluate) of the weights before and after the iteration's epochs, each as
+                 dict(all=..., unseen=...) over all held-out rows and over those whose state the learner's data set does not contain.
+                 Both replay modes, same bits. An iteration whose buffer has no game left for the learner raises.
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, **hyper):
+                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0, **hyper):
+        if isinstance(holdout, bool) or not isinstance(holdout, (int, float, np.floating, np.integer)) or not 0.0 <= float(holdout) < 1.0:
+            raise ValueError(f"holdout must be a fraction of games in [0, 1), got {holdout!r}")
         if sampler not in ("numpy", "torch", "device"):
             raise ValueError(f"sampler must be 'numpy', 'torch' or 'device', got {sampler!r}")
         if flip and sampler != "device":
@@ -135,6 +174,10 @@ class LearningLoop:
         self.sampler = sampler
         self.flip = bool(flip)
         self._torch_gen = torch.Generator().manual_seed(self.seed) if sampler == "torch" else None
+        self.holdout = float(holdout)
+        self._holdout_threshold = int(np.floor(self.holdout * 4294967296.0))
+        if self._holdout_threshold and self.rank == 0 and replay == "device":
+            engine.replay_set_holdout(_holdout_key(self.seed), self._holdout_threshold)
         self.logs_dir = logs_dir if self.rank == 0 else None
         if self.logs_dir:
             self._save_model(0)
@@ -297,11 +340,16 @@ class LearningLoop:
             else:
                 n_unique = self.engine.replay_deduplicate_to_trainer()
             t_dedup = time.perf_counter() - t2
+            if self._holdout_threshold:
+                held = self.engine.dataset_counts()
+                before = self._holdout_metrics(*held)
             t3 = time.perf_counter()
             steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=steps_in_buffer, unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
+            if self._holdout_threshold:
+                rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = n_canonical
             if self.logs_dir:
@@ -315,6 +363,40 @@ class LearningLoop:
                 np.save(os.path.join(self.logs_dir, "latest_vs.npy"), D["vs"])
         self._finish_iteration(rec, t0, t_play, t_gather, t_dedup, t_train)
         return rec
+
+    def _holdout_metrics(self, n_eval, n_unseen):
+        """The trainer's current weights on the evaluation set: dict(all=..., unseen=...) of dict(rows, mean_pi, mean_v, pi_acc, v_acc)"""
+        out = {}
+        for name, n in (("all", n_eval), ("unseen", n_unseen)):
+            m = self.engine.dataset_evaluate("eval", 0, n) if n_eval else dict.fromkeys(_METRIC_KEYS, 0.0)
+            out[name] = {k: (int(m[k]) if k == "rows" else float(m[k])) for k in _METRIC_KEYS}
+        return out
+
+    def _holdout_split_host(self):
+        """replay="host": the device path's split on the host arrays: (the learner's part of self.R, the held-out part), buffer order kept"""
+        held = holdout_flags(_holdout_key(self.seed), self._holdout_threshold, self.R["gid"])
+        if held.all():
+            raise ValueError("the holdout threshold holds out every game of the buffer: the learner would have no data set")
+        return {k: a[~held] for k, a in self.R.items()}, {k: a[held] for k, a in self.R.items()}
+
+    def _holdout_set_host(self, H, D):
+        """De-duplicates the held-out positions H and uploads them as the evaluation set, unseen rows first (seen: the state, with
+        symmetry="mirror" its canonical form, is among the learner's (canonical) rows of D). Returns (rows, unseen rows)."""
+        if H["my"].size == 0:
+            self.engine.dataset_set(H["my"], H["op"], H["pi"], H["v"])
+            return 0, 0
+        E = self.engine.replay_deduplicate(H["my"], H["op"], H["pi"], H["v"], symmetry=self.symmetry)
+        my, op = E["my_bb"], E["op_bb"]
+        n_train = D["canonical"] if self.symmetry == "mirror" else int(D["my_bb"].size)
+        if self.symmetry == "mirror":
+            mmy, mop = self.engine.positions_mirror(my, op)
+            flipped = (mmy < my) | ((mmy == my) & (mop < op))
+            my, op = np.where(flipped, mmy, my), np.where(flipped, mop, op)
+        train = set(zip(D["my_bb"][:n_train].tolist(), D["op_bb"][:n_train].tolist()))
+        seen = np.fromiter((k in train for k in zip(my.tolist(), op.tolist())), bool, count=my.size)
+        order = np.concatenate([np.flatnonzero(~seen), np.flatnonzero(seen)])
+        self.engine.dataset_set(E["my_bb"][order], E["op_bb"][order], E["pis"][order], E["vs"][order])
+        return int(order.size), int((~seen).sum())
 
     def _epochs(self, it, epochs, batch_size, lr, n_unique):
         """Iteration `it`'s epochs of optimiser steps over the learner's data set of n_unique rows (alpha_zero.rs:72-94), both replay
@@ -383,19 +465,26 @@ class LearningLoop:
             self.R = {k: a[keep] for k, a in R.items()}
             # ---- deduplicate on the GPU (data.rs:196-235)
             t2 = time.perf_counter()
+            T, H = self._holdout_split_host() if self._holdout_threshold else (self.R, None)   # the learner's part, the held-out part
             if self.symmetry == "mirror":
-                D = self.engine.replay_deduplicate(self.R["my"], self.R["op"], self.R["pi"], self.R["v"], symmetry="mirror")
+                D = self.engine.replay_deduplicate(T["my"], T["op"], T["pi"], T["v"], symmetry="mirror")
             else:
-                D = self.engine.replay_deduplicate(self.R["my"], self.R["op"], self.R["pi"], self.R["v"])
+                D = self.engine.replay_deduplicate(T["my"], T["op"], T["pi"], T["v"])
+            if self._holdout_threshold:
+                held = self._holdout_set_host(H, D)
             t_dedup = time.perf_counter() - t2
             n_unique = int(D["num"].size)
             # ---- epochs of optimiser steps (alpha_zero.rs:72-94): one upload, one persistent kernel launch per epoch
             t3 = time.perf_counter()
             self.engine.train_set_data(D["my_bb"], D["op_bb"], D["pis"], D["vs"])
+            if self._holdout_threshold:
+                before = self._holdout_metrics(*held)
             steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=int(self.R["my"].size), unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
+            if self._holdout_threshold:
+                rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = D["canonical"]
             if self.logs_dir:   # alpha_zero.rs:97-100
