@@ -88,7 +88,19 @@ def main():
     ap.add_argument("--holdout", type=float, default=0.0, help="fraction of GAMES kept away from the learner: their positions become the "
                     "engine's evaluation set and every iteration's record gains the held-out losses and accuracies of the weights before "
                     "and after its epochs, on all held-out rows and on the unseen ones (0 = off; learning loop only)")
+    ap.add_argument("--reanalyse", type=float, default=0.0, help="fraction of the stored positions of OLDER games that every iteration "
+                    "searches again with the current network before it trains; their pi targets are overwritten (0 = off; learning "
+                    "loop only; whether it trains a stronger player is not measured)")
+    ap.add_argument("--reanalyse-explores", type=int, default=None, help="explores of a reanalysis search (default: --explores)")
+    ap.add_argument("--reanalyse-value-mix", type=float, default=0.0, help="w in [0, 1]: a reanalysed row's v becomes v * (1 - w) + the new "
+                    "search's target_q * w (0 = v is left alone)")
     args = ap.parse_args()
+    if args.reanalyse and args.data_parallel:
+        raise SystemExit("--reanalyse belongs to the learning loop")
+    if not 0.0 <= args.reanalyse <= 1.0 or not 0.0 <= args.reanalyse_value_mix <= 1.0:
+        raise SystemExit("--reanalyse and --reanalyse-value-mix are fractions in [0, 1]")
+    if args.reanalyse_explores is not None and not 0 <= args.reanalyse_explores <= args.explores:
+        raise SystemExit("--reanalyse-explores must be in 0 .. --explores (the engine's node pool is sized for --explores)")
     if args.holdout and args.data_parallel:
         raise SystemExit("--holdout belongs to the learning loop: --data-parallel hands every position to the learner")
     if not 0.0 <= args.holdout < 1.0:
@@ -141,7 +153,8 @@ def main():
         loop = LearningLoop(eng, args.net, blob, dist=dist, device=local_rank, lr_schedule=lr_schedule, seed=args.seed,
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
-                            batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, **hyper)
+                            batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, reanalyse=args.reanalyse,
+                            reanalyse_explores=args.reanalyse_explores, reanalyse_value_mix=args.reanalyse_value_mix, **hyper)
     log = []
     eval_eng = None
     for it in range(args.iterations):

@@ -739,6 +739,60 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
 int syn_replay_set_holdout(syn_engine* h, uint64_t key, uint64_t threshold);
 int syn_dataset_counts(syn_engine* h, size_t* n_eval, size_t* n_unseen);
 
+/* ---- Reanalyse (opt-in; csrc/reanalyse_kernels.cuh; not in the reference): stored positions of the replay buffer are
+ * searched again with the engine's installed network and their pi / v targets overwritten, without the positions or the results leaving
+ * the device. A stored target is the product of the network of the iteration that played its game; this call relabels it with the
+ * newest one.
+ * Selection. With sm as in "Device-side epoch sampler" above and all arithmetic unsigned 64-bit, row i of the buffer with (gid, my, op)
+ * (their 64-bit patterns; hi32(x) = (uint32)(x >> 32), lo32(x) = (uint32)x) has
+ *   h = key ^ REANALYSE_TAG;  h = sm(h, hi32(gid));  h = sm(h, lo32(gid));  h = sm(h, hi32(my));  h = sm(h, lo32(my));
+ *   h = sm(h, hi32(op));  h = sm(h, lo32(op))                                                REANALYSE_TAG = 0x2EA7A1F5E5EA2C40
+ * and is SELECTED iff gid < before_gid (signed; INT64_MAX: every game), (h >> 32) < threshold (at most 2^32: about threshold / 2^32 of
+ * the eligible rows), and the position is searchable: syn_mcts_search's check of a root (disjoint boards inside the 63 cells, every
+ * column filled from the bottom, a free column) and neither side has four in a row. The row index does not enter, so a row keeps its
+ * fate when a keep-window shifts it. A row that passes the first two tests but is not searchable — only a caller's own
+ * syn_replay_append can have put it there — counts as `skipped` and is left alone. selected_rows (may be NULL) receives the selected row
+ * indices in ascending order; with `capacity` smaller than their number the call is SYN_ERR_CAPACITY, refused before anything changes.
+ * Search. The j-th selected row, in buffer order, is searched exactly as root j of syn_mcts_search(h, mcts, ..., explores,
+ * action_selection): the engine's installed network, its current arithmetic and its policy cache; its SYN_FPU_NORMAL / SYN_NOISE_DIRICHLET
+ * draws come from stream stream_base + j (stream_base = 0: that call's own numbering). The selected rows are searched in chunks of
+ * chunk_roots roots (0 = the larger of 65,536 and the engine's concurrent games); a chunk that starts at job c0 is launched on streams
+ * stream_base + c0 onwards, so the results never depend on the chunking.
+ * Write-back. pi[row] = the new search's target_pi. With q = its target_q and w = value_mix: w == 0 leaves v[row] untouched bit for bit,
+ * w == 1 stores q, otherwise v[k] = v_old[k] * (1.0f - w) + q[k] * w — three f32 operations in that order, nothing fused. A root that a
+ * syn_cancel kept from being searched (num_nodes == 0) writes nothing. `moved` = selected rows whose arg-max column of pi (the first
+ * maximum wins, as in "Held-out evaluation") differs between the old and the new pi. Everything else is unchanged: my, op, gid, the
+ * unselected rows, the row order, the trainer, both data sets and the engine's network.
+ * Device work: a flags kernel, an exclusive sum, a compaction into job arrays and one read-back of the counts; then per chunk the search
+ * launch and a write-back kernel, and the chunk's error word read back; finally a sum of the moved flags. The write-back runs per
+ * completed chunk and not at all for a chunk whose search reported an error: after SYN_ERR_CANCELLED (returned when a syn_cancel left
+ * selected rows unsearched) or SYN_ERR_CAPACITY from a tree, every row is wholly old or wholly new. stats (may be NULL): rows = the
+ * buffer's size, chunks = search launches, launches = all kernel launches of the call. syn_last_timing reports the summed device time of
+ * the search launches and the count of all launches, syn_last_cache_stats the sums over the chunks.
+ * An empty buffer or threshold = 0 is SYN_OK with all-zero stats and nothing launched; a call that selects nothing is SYN_OK with
+ * selected = moved = chunks = 0, launches no search and changes nothing.
+ * Refused, with the buffer bit for bit as it was: mcts or cfg NULL, threshold > 2^32, value_mix outside [0, 1] or NaN, a negative
+ * chunk_roots, explores / action_selection / mcts as syn_mcts_search refuses them (SYN_FPU_FUNC: SYN_ERR_UNSUPPORTED), no weights
+ * (SYN_ERR_NO_WEIGHTS), no replay buffer reserved (SYN_ERR_INVALID_ARGUMENT).
+ * Not measured: whether training on reanalysed targets gives a stronger player (tools/arena.py and syn_dataset_evaluate are the
+ * instruments). Out of scope: a network other than the installed one, de-duplicating states before the search. */
+typedef struct syn_reanalyse_config {
+    uint64_t key;            /* selection key */
+    uint64_t threshold;      /* 0 .. 2^32: about threshold / 2^32 of the eligible rows are selected */
+    int64_t  before_gid;     /* only rows with gid < before_gid are eligible (INT64_MAX: all) */
+    uint64_t stream_base;    /* noise stream of the j-th selected row = stream_base + j */
+    int32_t  explores;       /* 0 .. engine max_explores */
+    int32_t  action_selection;
+    float    value_mix;      /* w in [0, 1] */
+    int32_t  chunk_roots;    /* 0 = library's choice; results never depend on it */
+} syn_reanalyse_config;
+typedef struct syn_reanalyse_stats {
+    uint64_t rows, selected, skipped, moved;
+    uint32_t chunks, launches;
+} syn_reanalyse_stats;
+int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_reanalyse_config* cfg,
+                         syn_reanalyse_stats* out /*may be NULL*/, int64_t* selected_rows /*may be NULL*/, size_t capacity);
+
 /* Timing of the last syn_selfplay_run / syn_mcts_search / *_device call on this handle, measured with HIP events on
  * the engine stream: kernel_ms = device time of the dominant kernel launch(es), n_launches = how many. */
 int syn_last_timing(const syn_engine* h, float* kernel_ms, int* n_launches);

@@ -28,6 +28,7 @@
 #include "frozen_kernel.cuh"
 #include "train_kernels.cuh"
 #include "replay_kernels.cuh"
+#include "reanalyse_kernels.cuh"
 #include "sampler_kernels.cuh"
 #include "match_kernels.cuh"
 #include "tournament_kernels.cuh"
@@ -3796,6 +3797,200 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
     int rc = replay_copy(h, dst, replay_sections(h->d_replay, h->replay_cap), h->replay_n, hipMemcpyDeviceToHost);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return SYN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ reanalyse
+// syn_replay_reanalyse (include/synthesis_amd.h "Reanalyse"; kernels in reanalyse_kernels.cuh): the selected rows of the buffer are
+// compacted into job arrays, searched in chunks by the MODE_SEARCH kernels (as match_run_impl drives them: roots and results stay on
+// the device) and rewritten by the write-back kernel. Scratch, each section 256-byte aligned:
+//   [sel n][skip n][dst n][job_my n][job_op n][job_row n][moved n][done n][counts: skipped, moved, done][cub temp][results of one chunk]
+// (the job arrays are sized for every row: the scratch is laid out before the number of selected rows is known)
+struct ReanalyseLayout {
+    size_t sel, skip, dst, job_my, job_op, job_row, moved, done, counts, tmp, results, total;
+};
+static ReanalyseLayout reanalyse_layout(size_t n, size_t tmp_bytes, size_t chunk) {
+    ReanalyseLayout L{};
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    L.sel = take(n * 4); L.skip = take(n * 4); L.dst = take(n * 4);
+    L.job_my = take(n * 8); L.job_op = take(n * 8); L.job_row = take(n * 4);
+    L.moved = take(n * 4); L.done = take(n * 4);
+    L.counts = take(16);
+    L.tmp = take(tmp_bytes);
+    L.results = take(chunk * sizeof(DevSearchResult));
+    L.total = at;
+    return L;
+}
+
+int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_reanalyse_config* cfg, syn_reanalyse_stats* out,
+                         int64_t* selected_rows, size_t capacity) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine: the refusals follow)
+    if (out) std::memset(out, 0, sizeof(*out));
+    // ---- everything that can refuse the call, before anything of the engine or the device changes
+    if (!mcts || !cfg) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_reanalyse: mcts or cfg is NULL");
+    if (cfg->threshold > (1ull << 32))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_reanalyse: threshold %llu exceeds 2^32", (unsigned long long)cfg->threshold);
+    if (!(cfg->value_mix >= 0.0f && cfg->value_mix <= 1.0f))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_reanalyse: value_mix must be in [0, 1], got %g", (double)cfg->value_mix);
+    if (cfg->chunk_roots < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_reanalyse: chunk_roots must be >= 0, got %d", cfg->chunk_roots);
+    if (cfg->action_selection != SYN_ACTION_Q && cfg->action_selection != SYN_ACTION_NUM_VISITS)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown action selection %d", cfg->action_selection);
+    DevMctsCfg m{};
+    int rc = convert_mcts(h, mcts, m);
+    if (rc != SYN_OK) return rc;
+    EngineParams P;
+    rc = common_params(h, P, cfg->explores);
+    if (rc != SYN_OK) return rc;
+    P.mcts = m;
+    if ((rc = check_lane_only(h, P.mcts)) != SYN_OK) return rc;
+    if (!h->d_replay || h->replay_cap == 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_reanalyse: no replay buffer is reserved (syn_replay_reserve)");
+    const size_t n = h->replay_n;
+    if (n == 0 || cfg->threshold == 0) return SYN_OK;
+
+    // ---- selection: flags, scan, the counts to the host
+    const int ni = (int)n;
+    const size_t chunk_max = cfg->chunk_roots > 0 ? (size_t)cfg->chunk_roots : std::max((size_t)65536, (size_t)h->slots);
+    const size_t chunk_rows = std::min(chunk_max, n);
+    size_t tmp_scan = 0, tmp_sum = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(nullptr, tmp_sum, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    const size_t tmp_bytes = std::max(tmp_scan, tmp_sum);
+    const ReanalyseLayout L = reanalyse_layout(n, tmp_bytes, chunk_rows);
+    rc = ensure_scratch(h, L.total);
+    if (rc != SYN_OK) return rc;
+    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
+    const auto u32_at = [base](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
+    const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
+    unsigned* const d_sel = u32_at(L.sel);
+    unsigned* const d_skip = u32_at(L.skip);
+    unsigned* const d_dst = u32_at(L.dst);
+    unsigned long long* const d_job_my = u64_at(L.job_my);
+    unsigned long long* const d_job_op = u64_at(L.job_op);
+    unsigned* const d_job_row = u32_at(L.job_row);
+    unsigned* const d_moved = u32_at(L.moved);
+    unsigned* const d_done = u32_at(L.done);
+    unsigned* const d_counts = u32_at(L.counts);
+    void* const d_tmp = base + L.tmp;
+    DevSearchResult* const d_res = reinterpret_cast<DevSearchResult*>(base + L.results);
+    const ReplaySections R = replay_sections(h->d_replay, h->replay_cap);   // the sections syn_replay_read reads
+    const dim3 block(256), grid_rows((unsigned)((n + 255) / 256));
+    int launches = 0;
+    hipLaunchKernelGGL(reanalyse_flags_kernel, grid_rows, block, 0, h->stream, R.gid, R.my, R.op, ni, (unsigned long long)cfg->key ^ REANALYSE_TAG,
+                       (unsigned long long)cfg->threshold, (long long)cfg->before_gid, d_sel, d_skip);
+    HIP_TRY(h, hipGetLastError());
+    launches++;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_scan, d_sel, d_dst, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_skip, d_counts, ni, h->stream));
+    unsigned head[3] = {0, 0, 0};   // dst[n-1], sel[n-1], skipped
+    HIP_TRY(h, hipMemcpyAsync(&head[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&head[1], d_sel + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&head[2], d_counts, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t sel_n = (size_t)head[0] + head[1];
+    if (sel_n > n) return fail(h, SYN_ERR_HIP, "syn_replay_reanalyse: %zu rows selected out of %zu", sel_n, n);
+    if (selected_rows && sel_n > capacity)
+        return fail(h, SYN_ERR_CAPACITY, "syn_replay_reanalyse: %zu rows are selected, selected_rows has room for %zu", sel_n, capacity);
+    h->last_kernel_ms = 0.0f;
+    h->last_launches = launches;
+    h->last_cache_hits = h->last_cache_misses = 0;
+    if (out) {
+        out->rows = n;
+        out->skipped = head[2];
+        out->launches = (uint32_t)launches;
+    }
+    if (sel_n == 0) return SYN_OK;
+    hipLaunchKernelGGL(reanalyse_compact_kernel, grid_rows, block, 0, h->stream, d_sel, d_dst, ni, (unsigned)n, R.my, R.op, d_job_my, d_job_op,
+                       d_job_row);
+    HIP_TRY(h, hipGetLastError());
+    launches++;
+    HIP_TRY(h, hipMemsetAsync(d_moved, 0, sel_n * 4, h->stream));
+    HIP_TRY(h, hipMemsetAsync(d_done, 0, sel_n * 4, h->stream));
+    std::vector<unsigned> rows32;
+    if (selected_rows) {
+        rows32.resize(sel_n);
+        HIP_TRY(h, hipMemcpyAsync(rows32.data(), d_job_row, sel_n * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        for (size_t j = 0; j < sel_n; j++) selected_rows[j] = (int64_t)rows32[j];
+    }
+
+    // ---- per chunk: the search on job_my + c0 / job_op + c0, the write-back, the error word
+    const int v_mode = cfg->value_mix == 0.0f ? REANALYSE_V_KEEP : (cfg->value_mix == 1.0f ? REANALYSE_V_STORE : REANALYSE_V_MIX);
+    P.roll.num_explores = cfg->explores;
+    P.action_selection = cfg->action_selection;
+    P.first_game = 0;
+    P.results = d_res;
+    CallScope scope(h, (int)std::min(sel_n, chunk_rows));
+    float kernel_ms = 0.0f;
+    unsigned long long hits = 0, misses = 0;
+    uint32_t chunks = 0;
+    int status = SYN_OK;
+    for (size_t c0 = 0; c0 < sel_n; c0 += chunk_rows) {
+        const int jobs = (int)std::min(chunk_rows, sel_n - c0);
+        // (a syn_cancel's word does not survive the next chunk's reset: the loop itself stops at the first chunk that ends after it)
+        HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));
+        if (c0 == 0) HIP_TRY(h, scope.armed());
+        HIP_TRY(h, hipMemsetAsync(h->d_cache_stats, 0, 16, h->stream));
+        // a root that syn_cancel kept from being searched reads as all zeros: the write-back leaves its row alone
+        HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)jobs * sizeof(DevSearchResult), h->stream));
+        EngineParams Q = P;
+        Q.n_jobs = jobs;
+        Q.in_my = d_job_my + c0;
+        Q.in_op = d_job_op + c0;
+        Q.base_seed = cfg->stream_base + (unsigned long long)c0;
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        if (const int lrc = launch_engine(h, Q, jobs, MODE_SEARCH, false, false)) return lrc;
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        hipLaunchKernelGGL(reanalyse_writeback_kernel, dim3((unsigned)(((size_t)jobs * 16 + 255) / 256)), block, 0, h->stream,
+                           reinterpret_cast<const unsigned*>(d_res), jobs, d_job_row + c0, (unsigned)n, v_mode, cfg->value_mix,
+                           h->d_job_next + 8, R.pi, R.v, d_moved + c0, d_done + c0);
+        HIP_TRY(h, hipGetLastError());
+        int kerr = 0;
+        unsigned long long cstats[2] = {0, 0};
+        HIP_TRY(h, hipMemcpyAsync(&kerr, h->d_job_next + 8, 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(cstats, h->d_cache_stats, 16, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        float ms = 0.0f;
+        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        kernel_ms += ms;
+        launches += 2;   // the search and the write-back
+        chunks++;
+        hits += cstats[0];
+        misses += cstats[1];
+        h->last_kernel_ms = kernel_ms;
+        h->last_launches = launches;
+        h->last_cache_hits = hits;
+        h->last_cache_misses = misses;
+        if (kerr == 2)
+            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d); "
+                                             "the rows of this chunk and of the later ones keep their old targets", h->cap / 4, h->max_explores);
+        if (kerr) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+        if (scope.cancelled()) {
+            status = SYN_ERR_CANCELLED;
+            break;
+        }
+    }
+    // ---- the counts: moved flags, and after a cancel the rows that were searched
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_moved, d_counts + 1, (int)sel_n, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_done, d_counts + 2, (int)sel_n, h->stream));
+    unsigned tail[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(tail, d_counts + 1, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (out) {
+        out->selected = sel_n;
+        out->moved = tail[0];
+        out->chunks = chunks;
+        out->launches = (uint32_t)launches;
+    }
+    if (status == SYN_ERR_CANCELLED && (size_t)tail[1] < sel_n)
+        return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel: %zu of %zu selected rows were not searched and keep their old targets",
+                    sel_n - (size_t)tail[1], sel_n);
     return SYN_OK;
 }
 

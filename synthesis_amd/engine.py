@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "syn_match_run", "syn_match_run_sides", "syn_tournament_run", "syn_debug_tournament_regroup",
     "syn_train_epochs_sampled", "syn_debug_sampler",
     "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_replay_set_holdout", "syn_dataset_counts",
+    "syn_replay_reanalyse",
 ]
 TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
@@ -93,6 +94,16 @@ class CDatasetMetrics(C.Structure):  # struct syn_dataset_metrics
 
 
 DATASETS = {"train": 0, "eval": 1}   # SYN_DATASET_*
+
+
+class CReanalyseConfig(C.Structure):  # struct syn_reanalyse_config
+    _fields_ = [("key", C.c_uint64), ("threshold", C.c_uint64), ("before_gid", C.c_int64), ("stream_base", C.c_uint64),
+                ("explores", C.c_int32), ("action_selection", C.c_int32), ("value_mix", C.c_float), ("chunk_roots", C.c_int32)]
+
+
+class CReanalyseStats(C.Structure):  # struct syn_reanalyse_stats
+    _fields_ = [("rows", C.c_uint64), ("selected", C.c_uint64), ("skipped", C.c_uint64), ("moved", C.c_uint64),
+                ("chunks", C.c_uint32), ("launches", C.c_uint32)]
 
 
 class CCounters(C.Structure):  # struct syn_counters
@@ -239,7 +250,9 @@ def load_library():
                            ("syn_dataset_evaluate", [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                                      C.POINTER(CDatasetMetrics), C.c_void_p, C.c_void_p, C.c_void_p]),
                            ("syn_replay_set_holdout", [C.c_void_p, C.c_uint64, C.c_uint64]),
-                           ("syn_dataset_counts", [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])):
+                           ("syn_dataset_counts", [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+                           ("syn_replay_reanalyse", [C.c_void_p, C.POINTER(CMctsConfig), C.POINTER(CReanalyseConfig),
+                                                     C.POINTER(CReanalyseStats), C.c_void_p, C.c_size_t])):
         if hasattr(lib, name) or not os.environ.get("SYNTHESIS_AMD_LIB"):
             getattr(lib, name).argtypes = argtypes
     _lib = lib
@@ -954,6 +967,34 @@ class Engine:
         got = C.c_size_t()
         self._check(self._lib.syn_replay_read(self._h, _p(o["my"]), _p(o["op"]), _p(o["gid"]), _p(o["pi"]), _p(o["v"]), n, C.byref(got)))
         return o
+
+    def replay_reanalyse(self, mcts_cfg: MCTSConfig, explores, key, fraction=None, threshold=None, before_gid=None, stream_base=0,
+                         action_selection=1, value_mix=0.0, chunk_roots=0, rows=False):
+        """syn_replay_reanalyse (include/synthesis_amd.h "Reanalyse"): the rows of the buffer that the hash of (key, gid, my, op) selects —
+        about `fraction` (= threshold floor(fraction * 2^32), as holdout) of those with gid < before_gid (None: every game) — are searched
+        again with the engine's network as roots of mcts_search(mcts_cfg, ..., explores, action_selection), the j-th on noise stream
+        stream_base + j, and their pi (and, with value_mix > 0, v = v * (1 - value_mix) + target_q * value_mix) overwritten on the device.
+        Returns dict(rows, selected, skipped, moved, chunks, launches); rows=True adds selected_rows (ascending row indices)."""
+        if (fraction is None) == (threshold is None):
+            raise ValueError("give exactly one of fraction and threshold")
+        if threshold is None:
+            if not 0.0 <= float(fraction) <= 1.0:
+                raise ValueError(f"fraction must be in [0, 1], got {fraction!r}")
+            threshold = int(np.floor(float(fraction) * 4294967296.0))
+        if int(threshold) < 0 or int(stream_base) < 0:
+            raise ValueError("threshold and stream_base must be >= 0")
+        c = mcts_cfg.to_c() if mcts_cfg is not None else None
+        r = CReanalyseConfig(int(key) & 0xFFFFFFFFFFFFFFFF, int(threshold), (1 << 63) - 1 if before_gid is None else int(before_gid),
+                             int(stream_base) & 0xFFFFFFFFFFFFFFFF, int(explores), int(action_selection), float(value_mix), int(chunk_roots))
+        sel = np.zeros(self.replay_size(), np.int64) if rows else None
+        st = CReanalyseStats()
+        self._check(self._lib.syn_replay_reanalyse(self._h, None if c is None else C.byref(c), C.byref(r), C.byref(st), _p(sel),
+                                                   0 if sel is None else int(sel.size)))
+        out = dict(rows=int(st.rows), selected=int(st.selected), skipped=int(st.skipped), moved=int(st.moved), chunks=int(st.chunks),
+                   launches=int(st.launches))
+        if rows:
+            out["selected_rows"] = sel[: out["selected"]]
+        return out
 
     def replay_deduplicate_to_trainer(self, symmetry="none"):
         """De-duplicates the buffer on the device and makes the unique set the learner's data set (what replay_deduplicate +

@@ -73,6 +73,52 @@ def holdout_flags(key, threshold, gid):
     return h < np.uint64(int(threshold))
 
 
+REANALYSE_TAG = 0x2EA7A1F5E5EA2C40   # include/synthesis_amd.h "Reanalyse"
+
+
+def _reanalyse_key(seed, i_iter):
+    """reanalyse > 0: the selection key of iteration i_iter's reanalysis (0-based) — _sampler_key's number; the hashes carry different
+    tags, so the two uses of it are independent"""
+    return _sampler_key(seed, i_iter)
+
+
+def searchable_positions(my, op):
+    """The positions a search takes as a root: Engine.mcts_search's check (disjoint boards inside the 63 cells — bit index row + 7 * col —
+    every column filled from the bottom without holes, at least one free column) and neither side with four in a row (connect4.rs:70-83:
+    the four anchored line directions at bit distances 1, 7, 6 and 8)."""
+    my = np.asarray(my, np.uint64)
+    op = np.asarray(op, np.uint64)
+    u = np.uint64
+    occ = my | op
+    ok = ((my & op) == u(0)) & ((occ >> u(63)) == u(0))
+    any_free = np.zeros(occ.shape, bool)
+    for c in range(9):
+        col = (occ >> u(7 * c)) & u(0x7F)
+        ok &= (col & (col + u(1))) == u(0)
+        any_free |= col != u(0x7F)
+    rows = lambda lo, hi: sum(1 << (r + 7 * c) for r in range(lo, hi + 1) for c in range(9))
+    cols0to5 = sum(1 << (r + 7 * c) for r in range(7) for c in range(6))
+
+    def won(bb):
+        out = np.zeros(bb.shape, bool)
+        for shift, mask in ((6, cols0to5 & rows(3, 6)), (8, cols0to5 & rows(0, 3)), (7, cols0to5), (1, rows(0, 3))):
+            out |= (bb & (bb >> u(shift)) & (bb >> u(2 * shift)) & (bb >> u(3 * shift)) & u(mask)) != u(0)
+        return out
+
+    return ok & any_free & ~won(my) & ~won(op)
+
+
+def reanalyse_flags(key, threshold, before_gid, gid, my, op):
+    """Which rows (gid, my, op) a reanalysis under (key, threshold, before_gid) selects: the header's definition on the host
+    (replay="host"; the device applies it in reanalyse_flags_kernel), the searchable test included."""
+    g = np.asarray(gid, np.int64)
+    h = np.uint64((int(key) & _M64) ^ REANALYSE_TAG)
+    for word in (g.astype(np.uint64), np.asarray(my, np.uint64), np.asarray(op, np.uint64)):
+        h = _sm(_sm(h, word >> np.uint64(32)), word & np.uint64(0xFFFFFFFF))
+    drawn = (g < (int(before_gid) if before_gid is not None else (1 << 63) - 1)) & ((h >> np.uint64(32)) < np.uint64(int(threshold)))
+    return drawn & searchable_positions(my, op)
+
+
 _METRIC_KEYS = ("rows", "mean_pi", "mean_v", "pi_acc", "v_acc")
 
 
@@ -117,13 +163,32 @@ class LearningLoop:
                  arg-max accuracies (Engine.dataset_evaluate) of the weights before and after the iteration's epochs, each as
                  dict(all=..., unseen=...) over all held-out rows and over those whose state the learner's data set does not contain.
                  Both replay modes, same bits. An iteration whose buffer has no game left for the learner raises.
+    reanalyse    0.0 (default: every bit and every record as without the argument) | a fraction of ROWS in (0, 1]: after the keep-window
+                 and before the de-duplication of every iteration the learner's rank searches that fraction of the stored positions of
+                 OLDER games (gid below this iteration's first game; the hash of `_reanalyse_key(seed, iteration)`, the game id and the
+                 position selects them: include/synthesis_amd.h "Reanalyse") again with the engine's current network, the iteration's
+                 cfg.mcts_cfg and `reanalyse_explores or cfg.num_explores` explores, and overwrites their pi with the new target_pi and
+                 their v with v * (1 - reanalyse_value_mix) + target_q * reanalyse_value_mix (0.0: v stays). replay="device":
+                 Engine.replay_reanalyse, nothing leaves the device; replay="host": reanalyse_flags + one Engine.mcts_search over the
+                 selected rows + assignment into the host buffer — same bits. The record gains `reanalysed`, `reanalyse_moved` (rows whose
+                 arg-max column of pi changed) and a `reanalyse` phase time. Not measured: any training run with reanalysis, and more than
+                 one rank (the other ranks idle during the learner's reanalysis).
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
     """
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
-                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0, **hyper):
+                 network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0,
+                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, **hyper):
+        _real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
+        if not _real(reanalyse) or not 0.0 <= float(reanalyse) <= 1.0:
+            raise ValueError(f"reanalyse must be a fraction of rows in [0, 1], got {reanalyse!r}")
+        if reanalyse_explores is not None and (isinstance(reanalyse_explores, bool) or not isinstance(reanalyse_explores, (int, np.integer))
+                                               or int(reanalyse_explores) < 0):
+            raise ValueError(f"reanalyse_explores must be None or an integer >= 0, got {reanalyse_explores!r}")
+        if not _real(reanalyse_value_mix) or not 0.0 <= float(reanalyse_value_mix) <= 1.0:
+            raise ValueError(f"reanalyse_value_mix must be in [0, 1], got {reanalyse_value_mix!r}")
         if isinstance(holdout, bool) or not isinstance(holdout, (int, float, np.floating, np.integer)) or not 0.0 <= float(holdout) < 1.0:
             raise ValueError(f"holdout must be a fraction of games in [0, 1), got {holdout!r}")
         if sampler not in ("numpy", "torch", "device"):
@@ -178,6 +243,10 @@ class LearningLoop:
         self._holdout_threshold = int(np.floor(self.holdout * 4294967296.0))
         if self._holdout_threshold and self.rank == 0 and replay == "device":
             engine.replay_set_holdout(_holdout_key(self.seed), self._holdout_threshold)
+        self.reanalyse = float(reanalyse)
+        self._reanalyse_threshold = int(np.floor(self.reanalyse * 4294967296.0))
+        self.reanalyse_explores = None if reanalyse_explores is None else int(reanalyse_explores)
+        self.reanalyse_value_mix = float(reanalyse_value_mix)
         self.logs_dir = logs_dir if self.rank == 0 else None
         if self.logs_dir:
             self._save_model(0)
@@ -333,6 +402,10 @@ class LearningLoop:
         if self.rank == 0:
             self.engine.replay_keep_games_from(self.games_played - games_to_keep)   # keep_last_n_games (data.rs:160-194)
             steps_in_buffer = self.engine.replay_size()
+            if self._reanalyse_threshold:
+                t_re = time.perf_counter()
+                reanalysed = self._reanalyse_device(cfg, it, it * games_per_train)
+                t_re = time.perf_counter() - t_re
             # ---- deduplicate into the learner's data set (data.rs:196-235 + alpha_zero.rs:52-58), all on the device
             t2 = time.perf_counter()
             if self.symmetry == "mirror":
@@ -352,6 +425,8 @@ class LearningLoop:
                 rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = n_canonical
+            if self._reanalyse_threshold:
+                rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
             if self.logs_dir:
                 import os
 
@@ -362,6 +437,8 @@ class LearningLoop:
                 np.save(os.path.join(self.logs_dir, "latest_pis.npy"), D["pis"])
                 np.save(os.path.join(self.logs_dir, "latest_vs.npy"), D["vs"])
         self._finish_iteration(rec, t0, t_play, t_gather, t_dedup, t_train)
+        if self.rank == 0 and self._reanalyse_threshold:
+            rec["seconds"]["reanalyse"] = round(t_re, 4)
         return rec
 
     def _holdout_metrics(self, n_eval, n_unseen):
@@ -397,6 +474,33 @@ class LearningLoop:
         order = np.concatenate([np.flatnonzero(~seen), np.flatnonzero(seen)])
         self.engine.dataset_set(E["my_bb"][order], E["op_bb"][order], E["pis"][order], E["vs"][order])
         return int(order.size), int((~seen).sum())
+
+    def _reanalyse_device(self, cfg, it, before_gid):
+        """replay="device": iteration `it`'s reanalysis in the engine's buffer. Returns (rows reanalysed, rows whose arg-max moved)."""
+        st = self.engine.replay_reanalyse(cfg.mcts_cfg, self.reanalyse_explores or cfg.num_explores, _reanalyse_key(self.seed, it),
+                                          threshold=self._reanalyse_threshold, before_gid=before_gid, action_selection=cfg.action,
+                                          value_mix=self.reanalyse_value_mix)
+        return st["selected"], st["moved"]
+
+    def _reanalyse_host(self, cfg, it, before_gid):
+        """replay="host": the same on self.R — reanalyse_flags, ONE Engine.mcts_search over the selected rows (root j on stream j), the
+        write-back as numpy f32 operations in the device's order."""
+        R = self.R
+        rows = np.flatnonzero(reanalyse_flags(_reanalyse_key(self.seed, it), self._reanalyse_threshold, before_gid, R["gid"], R["my"], R["op"]))
+        if rows.size == 0:
+            return 0, 0
+        res = self.engine.mcts_search(cfg.mcts_cfg, R["my"][rows], R["op"][rows], self.reanalyse_explores or cfg.num_explores,
+                                      action_selection=cfg.action)
+        pi = np.asarray(res["target_pi"], np.float32).reshape(-1, 9)
+        q = np.asarray(res["target_q"], np.float32).reshape(-1, 3)
+        moved = int((R["pi"][rows].argmax(axis=1) != pi.argmax(axis=1)).sum())
+        R["pi"][rows] = pi
+        w = np.float32(self.reanalyse_value_mix)
+        if w == np.float32(1.0):
+            R["v"][rows] = q
+        elif w != np.float32(0.0):
+            R["v"][rows] = R["v"][rows] * (np.float32(1.0) - w) + q * w
+        return int(rows.size), moved
 
     def _epochs(self, it, epochs, batch_size, lr, n_unique):
         """Iteration `it`'s epochs of optimiser steps over the learner's data set of n_unique rows (alpha_zero.rs:72-94), both replay
@@ -463,6 +567,10 @@ class LearningLoop:
             R = {k: np.concatenate([self.R[k], new[k]]) for k in self.R}
             keep = R["gid"] >= self.games_played - games_to_keep   # keep_last_n_games (data.rs:160-194)
             self.R = {k: a[keep] for k, a in R.items()}
+            if self._reanalyse_threshold:
+                t_re = time.perf_counter()
+                reanalysed = self._reanalyse_host(cfg, it, it * games_per_train)
+                t_re = time.perf_counter() - t_re
             # ---- deduplicate on the GPU (data.rs:196-235)
             t2 = time.perf_counter()
             T, H = self._holdout_split_host() if self._holdout_threshold else (self.R, None)   # the learner's part, the held-out part
@@ -487,6 +595,8 @@ class LearningLoop:
                 rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = D["canonical"]
+            if self._reanalyse_threshold:
+                rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
             if self.logs_dir:   # alpha_zero.rs:97-100
                 import os
 
@@ -510,6 +620,8 @@ class LearningLoop:
         rec["seconds"] = dict(selfplay=round(t_play, 4), wait_for_ranks=round(self._last_gather_wait, 4), gather=round(t_gather, 4),
                               dedup=round(t_dedup, 4), train=round(t_train, 4),
                               broadcast=round(t_bcast, 4), total=round(time.perf_counter() - t0, 4))
+        if self.rank == 0 and self._reanalyse_threshold:
+            rec["seconds"]["reanalyse"] = round(t_re, 4)
         return rec
 
 
