@@ -345,9 +345,10 @@ typedef struct syn_match_player {
  * job index, which changes as games end). explores above max_explores is SYN_ERR_CAPACITY. A start position must pass
  * syn_mcts_search's check and neither side may have four in a row there (SYN_ERR_INVALID_ARGUMENT). Every refusal happens before
  * anything changes. n_games may exceed concurrent_games (the searches queue as in syn_mcts_search); n_games == 0 is SYN_OK.
- * Per ply the host launches the search, two small kernels and a scan and reads back one word (the number of games that go on);
- * nothing is uploaded after the first launch. syn_last_timing: the summed device time of all plies and the number of launches (three
- * per ply: search, advance, compaction). syn_cancel: the call returns SYN_ERR_CANCELLED after the ply in flight and the outputs are
+ * Per ply the host launches the search, three small kernels and a scan and reads back four words (where the games of either mover
+ * start in the live arrays, how many go on, and the ply's error word: the loop is syn_tournament_run's with two players); nothing is
+ * uploaded after the first launch. syn_last_timing: the summed device time of all plies and the number of launches (four per ply:
+ * search, advance, and the regroup's count and scatter). syn_cancel: the call returns SYN_ERR_CANCELLED after the ply in flight and the outputs are
  * unspecified; syn_progress reports the current ply's search. */
 int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
                   const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
@@ -380,11 +381,11 @@ typedef struct syn_match_side {
  *   ended (0 for every game when neither side is a baseline). seeds may be NULL only when neither side is a baseline.
  *   player.mcts_cfg must be Exploration::Uct + Fpu::Const (else SYN_ERR_UNSUPPORTED); player.explores is bounded by the node pool as
  *   in the baseline search (SYN_ERR_CAPACITY), not by max_explores; blob and n_floats are ignored and no weights are needed. The
- *   generator's state stays on the device and follows its game through the compaction; a stream position past 0xC0000000 (the
+ *   generator's state stays on the device and follows its game through the regroup; a stream position past 0xC0000000 (the
  *   baseline search's supported length) is detected on the device after the ply that reached it and ends the call with
  *   SYN_ERR_CAPACITY: it is never wrapped.
  * An unknown kind or arithmetic is SYN_ERR_INVALID_ARGUMENT. Everything else — start positions, the other outputs, refusals before
- * anything changes, n_games beyond the engine's slots, n_games == 0, one word read back per ply and nothing uploaded after the first
+ * anything changes, n_games beyond the engine's slots, n_games == 0, four words read back per ply and nothing uploaded after the first
  * launch, the timing summed over plies, cancellation after the ply in flight — is as documented for syn_match_run. Both kinds of
  * search use the engine's node pool and alternate on one stream. */
 int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,

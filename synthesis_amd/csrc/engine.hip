@@ -100,8 +100,7 @@ struct syn_engine {
     hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;  // syn_progress / syn_cancel: independent of the launch stream
     int* h_pin = nullptr;              // 512 pinned bytes for their transfers: [0..1] syn_progress, [8] syn_cancel's word, [9] its pre-read;
-                                       // [12] (the launch stream's, not theirs) syn_match_run's live-game count; [16 .. 16 + K + 2)
-                                       // (likewise) syn_tournament_run's group starts and error word
+                                       // [16 .. 16 + K + 2) (the launch stream's, not theirs) the game loop's group starts and error word
     // The call in flight (syn_selfplay_run / syn_mcts_search* / syn_frozen_search_rollout) as syn_progress / syn_cancel see it.
     // call_mu orders their state changes and serialises the users of aux_stream and h_pin.
     std::mutex call_mu;
@@ -139,18 +138,15 @@ struct syn_engine {
         // the image the current arithmetic evaluates
         const float* image() const { return f16x2() ? reinterpret_cast<const float*>(d_wimg16) : d_wimg; }
     } net;
-    // syn_match_run's own device memory: the two players' network images (never the engine's: a match leaves `net` and the policy
-    // cache as they were) and one allocation for the live-game arrays, the per-ply results and the per-game outputs (MatchLayout)
-    struct Match {
-        void* d_img[2] = {nullptr, nullptr};   // each sized for the largest image of either network in either arithmetic
+    // The game loop's own device memory (run_games: syn_match_run, syn_match_run_sides, syn_tournament_run): one network image per
+    // network player of the call, a match's in entries 0 and 1 (never the engine's: a call leaves `net` and the policy cache as they
+    // were), and one allocation for the live-game arrays, the per-ply results and the per-game outputs (GamesLayout), laid out
+    // afresh by every call
+    struct Games {
+        void* d_img[SYN_TOURNAMENT_MAX_PLAYERS] = {};   // allocated on demand, each sized for the largest image of either network in either arithmetic
         unsigned char* d_buf = nullptr;
         size_t buf_bytes = 0;
-    } match;
-    // syn_tournament_run's network images, one per network player of the call (the live-game arrays share match.d_buf: a call lays
-    // it out afresh)
-    struct Tournament {
-        void* d_img[SYN_TOURNAMENT_MAX_PLAYERS] = {};
-    } tour;
+    } games;
     int* d_job_next = nullptr;
     uint4* d_cache = nullptr;      // PolicyWithCache table (policy_cache_log2 > 0)
     int cache_log2 = 0;
@@ -285,6 +281,27 @@ static int ensure_scratch(syn_engine* h, size_t bytes) {
     HIP_TRY(h, hipMalloc(&h->d_scratch, want));
     h->scratch_bytes = want;
     return SYN_OK;
+}
+
+// One device allocation carved into sections, each 256-byte aligned: take() returns the next section's byte offset, `at` ends as the total.
+static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += align256(bytes);
+        return o;
+    }
+};
+
+// The search kernels' error word (EngineParams::error) as a call's refusal: 0 = none (SYN_OK), 2 = a tree's node blocks ran out, anything
+// else = a bounded spin gave up. `suffix` is appended to the capacity message.
+static int fail_search_error(syn_engine* h, int kerr, const char* suffix = "") {
+    if (kerr == 0) return SYN_OK;
+    if (kerr == 2)
+        return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)%s",
+                    h->cap / 4, h->max_explores, suffix);
+    return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
 }
 
 // ------------------------------------------------------------------------------------------------ weight image
@@ -639,10 +656,8 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_stat);
     hipFree(h->net.d_wimg);
     hipFree(h->net.d_wimg16);
-    hipFree(h->match.d_img[0]);
-    hipFree(h->match.d_img[1]);
-    hipFree(h->match.d_buf);
-    for (void* img : h->tour.d_img) hipFree(img);
+    for (void* img : h->games.d_img) hipFree(img);
+    hipFree(h->games.d_buf);
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
@@ -1438,10 +1453,7 @@ static int mcts_search_impl(syn_engine* h, const syn_mcts_config* cfg, const uin
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->last_cache_hits = cstats[0];
     h->last_cache_misses = cstats[1];
-    if (kerr == 2)
-        return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)",
-                    h->cap / 4, h->max_explores);
-    if (kerr) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+    if (const int rc = fail_search_error(h, kerr)) return rc;
     HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
     h->last_launches = 1;
     if (scope.cancelled()) {
@@ -1522,42 +1534,19 @@ static int launch_frozen(syn_engine* h, const FrozenPartition& part, const syn_m
     return SYN_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ device-resident matches
-// syn_match_run / syn_match_run_sides (match_kernels.cuh): every game of the call is searched, stepped and retired on the device. Per
-// ply the host enqueues the mover's search over the live games' roots — one MODE_SEARCH launch with the mover's image in the mover's
-// arithmetic, or one frozen_rollout_kernel launch on the re-partitioned pool for a baseline side — then the advance kernel, the scan
-// and the compaction, and reads ONE word back: how many games go on. Nothing is uploaded inside the loop; the outputs come back once,
-// after the last ply. Both kinds of search use the engine's node pool and alternate on one stream: nothing runs concurrently.
+// ------------------------------------------------------------------------------------------------ device-resident games
+// syn_match_run / syn_match_run_sides / syn_tournament_run (match_kernels.cuh, tournament_kernels.cuh): ONE loop, run_games, in which
+// every game of a schedule between K players is searched, stepped and retired on the device. A match is the schedule of two players
+// with player 0 first in every game. The live games are kept grouped by mover; per ply every non-empty group gets its player's search
+// over its range of the arrays — one MODE_SEARCH launch with the player's image in the player's arithmetic, or one
+// frozen_rollout_kernel launch on the re-partitioned pool for a baseline player — and the advance kernel, then one stable regroup by
+// next mover (count, scan, scatter), and the host reads the groups' starts and the error word back: K + 2 words. All games of a match
+// share their mover, so its ply has one group: four launches. Nothing is uploaded inside the loop; the outputs come back once, after
+// the last ply. Both kinds of search use the engine's node pool and alternate on one stream: nothing runs concurrently. The job
+// counter is reset before every search launch; the search kernels' error word sits in the same 64-byte block and is reset once per ply
+// only, so what the first group raised is still there after the last.
 // The searches never touch the policy cache (P.cache = nullptr): its entries are keyed by position alone and belong to the engine's own
-// network, so a match neither reads another network's evaluations nor leaves its own behind.
-struct MatchLayout {   // byte offsets into syn_engine::Match::d_buf, each section 256-byte aligned
-    size_t my[2], op[2], id[2], seed[2], word[2];   // the live games, two sets: a ply's compaction reads one and writes the other
-    size_t keep, dst, scan;       // survivor flags, their exclusive sum, the scan's temporary storage
-    size_t results;               // DevSearchResult or FrozenResult per live job of the current ply
-    size_t explores[2];           // a baseline side's explores per root (frozen_rollout_kernel takes them from an array): filled once per call
-    size_t rewards, plies, moves, final_bb, rng_words;   // MatchOut, per game
-    size_t live;                  // [0] the word the host reads per ply, [1] the advance kernel's stream-position flag
-    size_t total;
-};
-static MatchLayout match_layout(size_t n, size_t scan_bytes) {
-    MatchLayout L{};
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    for (int k = 0; k < 2; k++) {
-        L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); L.seed[k] = take(n * 8); L.word[k] = take(n * 8);
-    }
-    L.keep = take(n * 4); L.dst = take(n * 4); L.scan = take(scan_bytes);
-    L.results = take(n * (sizeof(DevSearchResult) > sizeof(FrozenResult) ? sizeof(DevSearchResult) : sizeof(FrozenResult)));
-    for (int k = 0; k < 2; k++) L.explores[k] = take(n * 4);
-    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16); L.rng_words = take(n * 8);
-    L.live = take(8);
-    L.total = at;
-    return L;
-}
+// network, so a call neither reads another network's evaluations nor leaves its own behind.
 
 // c4::won (device_common.cuh, device code) for the host's check of the start positions: the same four anchored lines, its masks
 static bool host_won(uint64_t bb) {
@@ -1566,6 +1555,15 @@ static bool host_won(uint64_t bb) {
     const uint64_t hz = bb & (bb >> 7) & (bb >> 14) & (bb >> 21) & c4::H_MASK;
     const uint64_t vt = bb & (bb >> 1) & (bb >> 2) & (bb >> 3) & c4::V_MASK;
     return (d1 | d2 | hz | vt) != 0;
+}
+// a game's start: a position the first search can take as its root, and not a finished game
+static int check_start(syn_engine* h, int g, uint64_t my, uint64_t op) {
+    if (!valid_root(my, op))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is not a searchable Connect4 position "
+                    "(overlapping / floating stones, bit 63 set, or no free column)", g);
+    if (host_won(my) || host_won(op))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is a finished game: one side has four in a row", g);
+    return SYN_OK;
 }
 
 // a network side of a match: its configuration must be one whose search is a function of the root alone
@@ -1583,7 +1581,7 @@ static int check_match_player(syn_engine* h, const char* who, const syn_match_pl
     return convert_mcts(h, &p->mcts_cfg, m);
 }
 
-// One side of a match as the loop uses it: a network side's MODE_SEARCH parameters and the arithmetic of its image, or a baseline
+// One player as the loop uses it: a network side's MODE_SEARCH parameters, its blob and the arithmetic of its image, or a baseline
 // side's partition of the pool.
 struct MatchSide {
     bool baseline = false;
@@ -1592,6 +1590,7 @@ struct MatchSide {
     EngineParams P;                  // network
     FrozenPartition part;            // baseline
     const syn_match_player* player = nullptr;
+    const float* blob = nullptr;     // network
 };
 
 // ---- everything that can refuse a side, before anything of the engine or the device changes
@@ -1613,6 +1612,7 @@ static int check_match_side(syn_engine* h, const char* who, const syn_match_side
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s side's kind %d is unknown", who, s->kind);
     if (s->arithmetic != SYN_MATCH_ARITH_ENGINE && s->arithmetic != SYN_MATCH_ARITH_F32 && s->arithmetic != SYN_MATCH_ARITH_F16X2)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s side's arithmetic %d is unknown", who, s->arithmetic);
+    out.blob = s->blob;
     static_assert(SYN_MATCH_ARITH_ENGINE == PLAN_ARITH_ENGINE && SYN_MATCH_ARITH_F32 == PLAN_ARITH_F32 && SYN_MATCH_ARITH_F16X2 == PLAN_ARITH_F16X2,
                   "launch_plan.hpp restates the header's SYN_MATCH_ARITH_*");
     out.arith = s->arithmetic;
@@ -1630,190 +1630,6 @@ static int check_match_side(syn_engine* h, const char* who, const syn_match_side
     return SYN_OK;
 }
 
-static int match_run_impl(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
-                          const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
-                          uint64_t* final_bb, uint64_t* rng_words) {
-    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
-    // ---- everything that can refuse the call, before anything of the engine or the device changes
-    const syn_match_side* const sides[2] = {first, second};
-    const int kind = h->net.kind;
-    MatchSide S[2];
-    for (int s = 0; s < 2; s++)
-        if (const int rc = check_match_side(h, s == 0 ? "first" : "second", sides[s], seeds != nullptr, S[s])) return rc;
-    if (n_games == 0) return SYN_OK;
-    for (int g = 0; g < n_games; g++) {
-        if (!valid_root(start_my[g], start_op[g]))
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is not a searchable Connect4 position "
-                        "(overlapping / floating stones, bit 63 set, or no free column)", g);
-        if (host_won(start_my[g]) || host_won(start_op[g]))
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is a finished game: one side has four in a row", g);
-    }
-    HostImage im[2];
-    for (int s = 0; s < 2; s++) {
-        if (S[s].baseline) continue;
-        const int rc = build_host_image(h, kind, sides[s]->blob, S[s].f16, im[s]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
-        if (rc != SYN_OK) return rc;
-    }
-    // ---- the match's own device memory (the entry point has selected the engine's device)
-    const size_t n = (size_t)n_games;
-    size_t scan_bytes = 0;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, n_games, h->stream));
-    const MatchLayout L = match_layout(n, scan_bytes);
-    for (int s = 0; s < 2; s++)
-        if (!S[s].baseline && !h->match.d_img[s]) HIP_TRY(h, hipMalloc(&h->match.d_img[s], NET_IMAGE_MAX_BYTES));
-    HIP_TRY(h, ensure_device_buffer(h->match.d_buf, h->match.buf_bytes, L.total));
-    for (int s = 0; s < 2; s++)
-        if (S[s].baseline)
-            if (const int rc = ensure_frozen_path(h, S[s].part, n_games)) return rc;
-    unsigned char* const base = h->match.d_buf;
-    const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
-    MatchLive live_set[2];
-    for (int k = 0; k < 2; k++)
-        live_set[k] = MatchLive{u64_at(L.my[k]), u64_at(L.op[k]), reinterpret_cast<int*>(base + L.id[k]), u64_at(L.seed[k]), u64_at(L.word[k])};
-    unsigned* const d_keep = reinterpret_cast<unsigned*>(base + L.keep);
-    unsigned* const d_dst = reinterpret_cast<unsigned*>(base + L.dst);
-    void* const d_res = base + L.results;
-    int* const d_expl[2] = {reinterpret_cast<int*>(base + L.explores[0]), reinterpret_cast<int*>(base + L.explores[1])};
-    int* const d_live = reinterpret_cast<int*>(base + L.live);
-    int* const d_stream_error = d_live + 1;
-    MatchOut out;
-    out.rewards = reinterpret_cast<float*>(base + L.rewards);
-    out.plies = reinterpret_cast<int*>(base + L.plies);
-    out.moves = base + L.moves;
-    out.final_bb = u64_at(L.final_bb);
-    out.rng_words = u64_at(L.rng_words);
-
-    CallScope scope(h, n_games);
-    std::vector<int> iota(n);
-    for (size_t g = 0; g < n; g++) iota[g] = (int)g;
-    std::vector<int> expl[2];
-    for (int s = 0; s < 2; s++) {
-        if (S[s].baseline) {
-            expl[s].assign(n, S[s].player->explores);
-            HIP_TRY(h, hipMemcpyAsync(d_expl[s], expl[s].data(), n * 4, hipMemcpyHostToDevice, h->stream));
-            continue;
-        }
-        const int rc = enqueue_image_upload(h, im[s], h->match.d_img[s]);
-        if (rc != SYN_OK) return rc;
-        S[s].P.wimg = static_cast<const float*>(h->match.d_img[s]);
-    }
-    HIP_TRY(h, hipMemcpyAsync(live_set[0].my, start_my, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(live_set[0].op, start_op, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(live_set[0].id, iota.data(), n * 4, hipMemcpyHostToDevice, h->stream));
-    if (seeds) HIP_TRY(h, hipMemcpyAsync(live_set[0].seed, seeds, n * 8, hipMemcpyHostToDevice, h->stream));
-    else HIP_TRY(h, hipMemsetAsync(live_set[0].seed, 0, n * 8, h->stream));
-    HIP_TRY(h, hipMemsetAsync(live_set[0].word, 0, n * 8, h->stream));   // every game's generator starts at output word 0
-    HIP_TRY(h, hipMemsetAsync(base + L.rewards, 0, L.moves - L.rewards, h->stream));   // rewards and plies
-    HIP_TRY(h, hipMemsetAsync(out.moves, MATCH_NO_MOVE, n * MATCH_T, h->stream));
-    HIP_TRY(h, hipMemsetAsync(out.final_bb, 0, n * 16, h->stream));
-    HIP_TRY(h, hipMemsetAsync(out.rng_words, 0, n * 8, h->stream));
-    HIP_TRY(h, hipMemsetAsync(d_live, 0, 8, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));   // the last upload from host memory: the loop below only launches and reads one word
-
-    float kernel_ms = 0.0f;
-    int launches = 0, live = n_games, ply = 0;
-    for (; live > 0 && ply < MATCH_T; ply++) {
-        const int s = ply & 1, cur = ply & 1, nxt = cur ^ 1;
-        const MatchLive& A = live_set[cur];
-        // (a syn_cancel's word does not survive the next ply's reset: the loop itself stops at the first ply that ends after it)
-        HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 64, h->stream));
-        if (ply == 0) HIP_TRY(h, scope.armed());
-        const dim3 grid((unsigned)((live + 255) / 256)), block(256);
-        if (S[s].baseline) {
-            HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(FrozenResult), h->stream));
-            FrozenParams F{};
-            F.in_my = A.my; F.in_op = A.op; F.seeds = A.seed; F.rng_words = A.word; F.explores = d_expl[s];
-            F.n_roots = live;
-            F.results = static_cast<FrozenResult*>(d_res);
-            HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-            if (const int rc = launch_frozen(h, S[s].part, &S[s].player->mcts_cfg, S[s].player->action, F)) return rc;
-            hipLaunchKernelGGL(match_advance_kernel<FrozenResult>, grid, block, 0, h->stream, static_cast<const FrozenResult*>(d_res), live, ply,
-                               A.my, A.op, A.id, A.word, d_keep, d_stream_error, out);
-        } else {
-            // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
-            HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)live * sizeof(DevSearchResult), h->stream));
-            EngineParams Q = S[s].P;
-            Q.n_jobs = live;
-            Q.in_my = A.my;
-            Q.in_op = A.op;
-            Q.results = static_cast<DevSearchResult*>(d_res);
-            HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-            if (const int rc = launch_engine(h, Q, live, MODE_SEARCH, false, false, S[s].arith)) return rc;
-            hipLaunchKernelGGL(match_advance_kernel<DevSearchResult>, grid, block, 0, h->stream, static_cast<const DevSearchResult*>(d_res), live,
-                               ply, A.my, A.op, A.id, A.word, d_keep, d_stream_error, out);
-        }
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(base + L.scan, scan_bytes, d_keep, d_dst, live, h->stream));
-        hipLaunchKernelGGL(match_compact_kernel, grid, block, 0, h->stream, d_keep, d_dst, live, A, live_set[nxt], h->d_job_next + 8,
-                           d_stream_error, d_live);
-        HIP_TRY(h, hipGetLastError());
-        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(h->h_pin + 12, d_live, 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        float ms = 0.0f;
-        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-        kernel_ms += ms;
-        launches += 3;   // the search, the advance and the compaction (the scan between them is the library's)
-        h->last_kernel_ms = kernel_ms;
-        h->last_launches = launches;
-        if (scope.cancelled())
-            return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the match: the outputs are unspecified", ply);
-        const int now = h->h_pin[12];
-        if (now == -MATCH_ERR_STREAM)
-            return fail(h, SYN_ERR_CAPACITY, "a game's rollout generator passed output word 0xC0000000 at ply %d of the match: the baseline "
-                                             "search supports no longer stream", ply);
-        if (now < 0 && S[s].baseline) return fail(h, SYN_ERR_CAPACITY, "a baseline tree ran out of node records");
-        if (now == -2)
-            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)",
-                        h->cap / 4, h->max_explores);
-        if (now < 0) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
-        if (now > live) return fail(h, SYN_ERR_HIP, "syn_match_run: %d games survived a ply that %d entered", now, live);
-        live = now;
-    }
-    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_match_run: %d games are unfinished after %d plies", live, MATCH_T);
-    HIP_TRY(h, hipMemcpyAsync(rewards, out.rewards, n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
-    if (final_bb) HIP_TRY(h, hipMemcpyAsync(final_bb, out.final_bb, n * 16, hipMemcpyDeviceToHost, h->stream));
-    if (rng_words) HIP_TRY(h, hipMemcpyAsync(rng_words, out.rng_words, n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->last_cache_hits = h->last_cache_misses = 0;   // a match does not use the policy cache
-    return SYN_OK;
-}
-
-int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
-                        const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
-                        uint64_t* final_bb, uint64_t* rng_words) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine: the refusals come first in match_run_impl)
-    return match_run_impl(h, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words);
-}
-
-// two network sides in the engine's arithmetic
-int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
-                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
-                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
-    const syn_match_player* const players[2] = {first, second};
-    const float* const blobs[2] = {blob_first, blob_second};
-    syn_match_side sides[2];
-    for (int s = 0; s < 2; s++) {
-        if (!players[s]) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", s == 0 ? "first" : "second");
-        sides[s] = syn_match_side{SYN_MATCH_SIDE_NETWORK, SYN_MATCH_ARITH_ENGINE, *players[s], blobs[s], n_floats};
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    return match_run_impl(h, &sides[0], &sides[1], start_my, start_op, nullptr, n_games, rewards, plies, moves, final_bb, nullptr);
-}
-
-// ------------------------------------------------------------------------------------------------ device-resident tournaments
-// syn_tournament_run (tournament_kernels.cuh): the match loop for a schedule of games between K players. The live games are kept
-// grouped by mover; per ply every non-empty group gets its player's search over its range of the arrays (the match's two kinds of
-// launch, on the player's image or partition) and the advance kernel, then one stable regroup by next mover, and the host reads the
-// groups' starts and the error word back. The job counter is reset before every search launch; the search kernels' error word sits in
-// the same 64-byte block and is reset once per ply only, so what the first group raised is still there after the last.
 struct RegroupBuffers {   // device
     unsigned* counts;   // [n_keys + 1][n_blocks]
     unsigned* base;     // their exclusive sum
@@ -1835,72 +1651,50 @@ static int enqueue_regroup(syn_engine* h, const int* key, int n_live, int n_keys
     return SYN_OK;
 }
 
-struct TournamentLayout {   // byte offsets into syn_engine::Match::d_buf, each section 256-byte aligned
-    size_t my[2], op[2], id[2], seed[2], word[2];   // the live games, two sets
+struct GamesLayout {   // byte offsets into syn_engine::Games::d_buf
+    size_t my[2], op[2], id[2], seed[2], word[2];   // the live games, two sets: a ply's regroup reads one and writes the other
     size_t key, counts, base, scan;                 // the regroup's
-    size_t results;                                 // TOURNAMENT_RESULT_STRIDE bytes per live job: group [lo, hi) owns the bytes from lo * stride
+    size_t results;                                 // GAMES_RESULT_STRIDE bytes per live job: group [lo, hi) owns the bytes from lo * stride
     size_t explores;                                // baseline players' explores per root: player p's run starts at its own offset
     size_t first, second;                           // the schedule, per game
-    size_t rewards, plies, moves, final_bb, rng_words;
+    size_t rewards, plies, moves, final_bb, rng_words;   // MatchOut, per game
     size_t seg;                                     // [0 .. K] group starts, [K + 1] error word, [K + 2] the advance kernels' stream-position flag
     size_t total;
 };
-constexpr size_t TOURNAMENT_RESULT_STRIDE =
+constexpr size_t GAMES_RESULT_STRIDE =
     ((sizeof(DevSearchResult) > sizeof(FrozenResult) ? sizeof(DevSearchResult) : sizeof(FrozenResult)) + 15) & ~(size_t)15;
-static TournamentLayout tournament_layout(size_t n, int n_players, size_t cells, size_t scan_bytes, size_t n_explores) {
-    TournamentLayout L{};
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
+static GamesLayout games_layout(size_t n, int n_players, size_t cells, size_t scan_bytes, size_t n_explores) {
+    GamesLayout L{};
+    Carve c;
     for (int k = 0; k < 2; k++) {
-        L.my[k] = take(n * 8); L.op[k] = take(n * 8); L.id[k] = take(n * 4); L.seed[k] = take(n * 8); L.word[k] = take(n * 8);
+        L.my[k] = c.take(n * 8); L.op[k] = c.take(n * 8); L.id[k] = c.take(n * 4); L.seed[k] = c.take(n * 8); L.word[k] = c.take(n * 8);
     }
-    L.key = take(n * 4); L.counts = take(cells * 4); L.base = take(cells * 4); L.scan = take(scan_bytes);
-    L.results = take(n * TOURNAMENT_RESULT_STRIDE);
-    L.explores = take(n_explores * 4);
-    L.first = take(n * 4); L.second = take(n * 4);
-    L.rewards = take(n * 4); L.plies = take(n * 4); L.moves = take(n * MATCH_T); L.final_bb = take(n * 16); L.rng_words = take(n * 8);
-    L.seg = take((size_t)(n_players + 3) * 4);
-    L.total = at;
+    L.key = c.take(n * 4); L.counts = c.take(cells * 4); L.base = c.take(cells * 4); L.scan = c.take(scan_bytes);
+    L.results = c.take(n * GAMES_RESULT_STRIDE);
+    L.explores = c.take(n_explores * 4);
+    L.first = c.take(n * 4); L.second = c.take(n * 4);
+    L.rewards = c.take(n * 4); L.plies = c.take(n * 4); L.moves = c.take(n * MATCH_T); L.final_bb = c.take(n * 16); L.rng_words = c.take(n * 8);
+    L.seg = c.take((size_t)(n_players + 3) * 4);
+    L.total = c.at;
     return L;
 }
 
-int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
-                       const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards,
-                       int32_t* plies, uint8_t* moves, uint64_t* final_bb, uint64_t* rng_words) {
-    if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    if (n_games < 0 || (n_games > 0 && (!first || !second || !start_my || !start_op || !rewards || !plies)))
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_tournament_run");
-    if (n_players < 1 || n_players > SYN_TOURNAMENT_MAX_PLAYERS)
-        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: n_players %d is outside 1 .. %d", n_players, SYN_TOURNAMENT_MAX_PLAYERS);
-    if (!players) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: players is NULL");
-    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine)
-    // ---- everything that can refuse the call, before anything of the engine or the device changes
-    const int K = n_players;
-    const int kind = h->net.kind;
-    std::vector<MatchSide> S((size_t)K);
-    for (int p = 0; p < K; p++) {
-        char who[24];
-        std::snprintf(who, sizeof(who), "tournament's #%d", p);
-        if (const int rc = check_match_side(h, who, &players[p], seeds != nullptr, S[p])) return rc;
-    }
+// The loop. S: the call's K checked players; first / second: the schedule (host). `noun` names the call in messages ("match",
+// "tournament"). Everything that can still refuse the call — the schedule, the starts, an image without a plan — comes before anything
+// of the engine or the device changes; the entry point has selected the engine's device.
+static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, const int32_t* second, const uint64_t* start_my,
+                     const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                     uint64_t* final_bb, uint64_t* rng_words, const char* noun) {
     for (int g = 0; g < n_games; g++) {
         if (first[g] < 0 || first[g] >= K || second[g] < 0 || second[g] >= K)
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: game %d names players %d and %d; there are %d", g, first[g],
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_%s_run: game %d names players %d and %d; there are %d", noun, g, first[g],
                         second[g], K);
-        if (!valid_root(start_my[g], start_op[g]))
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is not a searchable Connect4 position "
-                        "(overlapping / floating stones, bit 63 set, or no free column)", g);
-        if (host_won(start_my[g]) || host_won(start_op[g]))
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "start %d is a finished game: one side has four in a row", g);
+        if (const int rc = check_start(h, g, start_my[g], start_op[g])) return rc;
     }
     std::vector<HostImage> im((size_t)K);
     for (int p = 0; p < K; p++) {
         if (S[p].baseline) continue;
-        const int rc = build_host_image(h, kind, players[p].blob, S[p].f16, im[p]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
+        const int rc = build_host_image(h, h->net.kind, S[p].blob, S[p].f16, im[p]);   // (f16x2: SYN_ERR_UNSUPPORTED for a blob without a plan)
         if (rc != SYN_OK) return rc;
     }
     if (n_games == 0) return SYN_OK;
@@ -1926,14 +1720,14 @@ int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_playe
     const size_t cells = regroup_cells(n, K);
     size_t scan_bytes = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cells, h->stream));
-    const TournamentLayout L = tournament_layout(n, K, cells, scan_bytes, n_explores);
+    const GamesLayout L = games_layout(n, K, cells, scan_bytes, n_explores);
     for (int p = 0; p < K; p++)
-        if (!S[p].baseline && !h->tour.d_img[p]) HIP_TRY(h, hipMalloc(&h->tour.d_img[p], NET_IMAGE_MAX_BYTES));
-    HIP_TRY(h, ensure_device_buffer(h->match.d_buf, h->match.buf_bytes, L.total));
+        if (!S[p].baseline && !h->games.d_img[p]) HIP_TRY(h, hipMalloc(&h->games.d_img[p], NET_IMAGE_MAX_BYTES));
+    HIP_TRY(h, ensure_device_buffer(h->games.d_buf, h->games.buf_bytes, L.total));
     for (int p = 0; p < K; p++)
         if (S[p].baseline && appears[p] > 0)
             if (const int rc = ensure_frozen_path(h, S[p].part, appears[p])) return rc;
-    unsigned char* const base = h->match.d_buf;
+    unsigned char* const base = h->games.d_buf;
     const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     MatchLive live_set[2];
     for (int k = 0; k < 2; k++)
@@ -1966,9 +1760,9 @@ int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_playe
             std::fill(expl.begin() + (ptrdiff_t)expl_at[p], expl.begin() + (ptrdiff_t)(expl_at[p] + (size_t)appears[p]), S[p].player->explores);
             continue;
         }
-        const int rc = enqueue_image_upload(h, im[p], h->tour.d_img[p]);
+        const int rc = enqueue_image_upload(h, im[p], h->games.d_img[p]);
         if (rc != SYN_OK) return rc;
-        S[p].P.wimg = static_cast<const float*>(h->tour.d_img[p]);
+        S[p].P.wimg = static_cast<const float*>(h->games.d_img[p]);
     }
     if (n_explores) HIP_TRY(h, hipMemcpyAsync(d_expl, expl.data(), n_explores * 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(live_set[0].my, s_my.data(), n * 8, hipMemcpyHostToDevice, h->stream));
@@ -2002,7 +1796,7 @@ int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_playe
             if (any_launch) HIP_TRY(h, hipMemsetAsync(h->d_job_next, 0, 32, h->stream));   // the counters alone: the error word stays
             any_launch = true;
             const dim3 grid((unsigned)((cnt + 255) / 256)), block(256);
-            unsigned char* const res = d_res + (size_t)lo * TOURNAMENT_RESULT_STRIDE;
+            unsigned char* const res = d_res + (size_t)lo * GAMES_RESULT_STRIDE;
             // a root that syn_cancel kept from being searched reads as all zeros: the advance kernel drops it
             if (S[p].baseline) {
                 any_baseline = true;
@@ -2041,32 +1835,91 @@ int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_playe
         h->last_kernel_ms = kernel_ms;
         h->last_launches = launches;
         if (scope.cancelled())
-            return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the tournament: the outputs are unspecified", ply);
+            return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel at ply %d of the %s: the outputs are unspecified", ply, noun);
         const int err = h_seg[K + 1];
         if (err == -MATCH_ERR_STREAM)
-            return fail(h, SYN_ERR_CAPACITY, "a game's rollout generator passed output word 0xC0000000 at ply %d of the tournament: the "
-                                             "baseline search supports no longer stream", ply);
+            return fail(h, SYN_ERR_CAPACITY, "a game's rollout generator passed output word 0xC0000000 at ply %d of the %s: the "
+                                             "baseline search supports no longer stream", ply, noun);
         if (err < 0 && any_baseline && !any_network) return fail(h, SYN_ERR_CAPACITY, "a baseline tree ran out of node records");
-        if (err == -2)
-            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks or records (lane-per-tree kernel: %u blocks per tree for "
-                                             "max_explores %d; baseline trees: their partition of the pool)", h->cap / 4, h->max_explores);
-        if (err < 0) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+        // (both kinds of search raise 2 for a full tree: after a ply of both it may have been a baseline player's)
+        if (const int rc = fail_search_error(h, -err, any_baseline ? "; or a baseline tree of the same ply ran out of node records" : "")) return rc;
         bool sane = h_seg[0] == 0 && h_seg[K] <= live;
         for (int p = 0; p < K && sane; p++) sane = h_seg[p] <= h_seg[p + 1];
-        if (!sane) return fail(h, SYN_ERR_HIP, "syn_tournament_run: the regroup of ply %d returned group starts that are no partition of "
-                                               "at most %d games", ply, live);
+        if (!sane) return fail(h, SYN_ERR_HIP, "syn_%s_run: the regroup of ply %d returned group starts that are no partition of "
+                                               "at most %d games", noun, ply, live);
         for (int p = 0; p <= K; p++) seg[p] = h_seg[p];
         live = seg[K];
     }
-    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_tournament_run: %d games are unfinished after %d plies", live, MATCH_T);
+    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_%s_run: %d games are unfinished after %d plies", noun, live, MATCH_T);
     HIP_TRY(h, hipMemcpyAsync(rewards, out.rewards, n * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
     if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
     if (final_bb) HIP_TRY(h, hipMemcpyAsync(final_bb, out.final_bb, n * 16, hipMemcpyDeviceToHost, h->stream));
     if (rng_words) HIP_TRY(h, hipMemcpyAsync(rng_words, out.rng_words, n * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->last_cache_hits = h->last_cache_misses = 0;   // a tournament does not use the policy cache
+    h->last_cache_hits = h->last_cache_misses = 0;   // the game loop does not use the policy cache
     return SYN_OK;
+}
+
+// A match: two players, `first` moving first in every game. (n_games == 0 is answered here, once the sides have passed.)
+static int match_run_impl(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
+                          const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                          uint64_t* final_bb, uint64_t* rng_words) {
+    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
+    MatchSide S[2];
+    if (const int rc = check_match_side(h, "first", first, seeds != nullptr, S[0])) return rc;
+    if (const int rc = check_match_side(h, "second", second, seeds != nullptr, S[1])) return rc;
+    if (n_games == 0) return SYN_OK;
+    const std::vector<int32_t> zeros((size_t)n_games, 0), ones((size_t)n_games, 1);
+    return run_games(h, S, 2, zeros.data(), ones.data(), start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words, "match");
+}
+
+int syn_match_run_sides(syn_engine* h, const syn_match_side* first, const syn_match_side* second, const uint64_t* start_my,
+                        const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
+                        uint64_t* final_bb, uint64_t* rng_words) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine: the refusals come first in match_run_impl)
+    return match_run_impl(h, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words);
+}
+
+// two network sides in the engine's arithmetic
+int syn_match_run(syn_engine* h, const syn_match_player* first, const syn_match_player* second, const float* blob_first,
+                  const float* blob_second, size_t n_floats, const uint64_t* start_my, const uint64_t* start_op, int n_games,
+                  float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_games < 0 || (n_games > 0 && (!start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_match_run");
+    const syn_match_player* const players[2] = {first, second};
+    const float* const blobs[2] = {blob_first, blob_second};
+    syn_match_side sides[2];
+    for (int s = 0; s < 2; s++) {
+        if (!players[s]) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_match_run: the %s player is NULL", s == 0 ? "first" : "second");
+        sides[s] = syn_match_side{SYN_MATCH_SIDE_NETWORK, SYN_MATCH_ARITH_ENGINE, *players[s], blobs[s], n_floats};
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    return match_run_impl(h, &sides[0], &sides[1], start_my, start_op, nullptr, n_games, rewards, plies, moves, final_bb, nullptr);
+}
+
+int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
+                       const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards,
+                       int32_t* plies, uint8_t* moves, uint64_t* final_bb, uint64_t* rng_words) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (n_games < 0 || (n_games > 0 && (!first || !second || !start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_tournament_run");
+    if (n_players < 1 || n_players > SYN_TOURNAMENT_MAX_PLAYERS)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: n_players %d is outside 1 .. %d", n_players, SYN_TOURNAMENT_MAX_PLAYERS);
+    if (!players) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_tournament_run: players is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine)
+    // ---- everything that can refuse the call, before anything of the engine or the device changes
+    const int K = n_players;
+    std::vector<MatchSide> S((size_t)K);
+    for (int p = 0; p < K; p++) {
+        char who[24];
+        std::snprintf(who, sizeof(who), "tournament's #%d", p);
+        if (const int rc = check_match_side(h, who, &players[p], seeds != nullptr, S[p])) return rc;
+    }
+    return run_games(h, S.data(), K, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words, "tournament");
 }
 
 int syn_debug_tournament_regroup(syn_engine* h, const int32_t* keys, int n, int n_keys, int32_t* perm_out, int32_t* seg_out) {
@@ -2082,10 +1935,10 @@ int syn_debug_tournament_regroup(syn_engine* h, const int32_t* keys, int n, int 
     const size_t nb = (size_t)n, cells = regroup_cells(nb, n_keys);
     size_t scan_bytes = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cells, h->stream));
-    const auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_key = 0, o_in = o_key + pad(nb * 4), o_out = o_in + pad(nb * 4), o_counts = o_out + pad(nb * 4),
-                 o_base = o_counts + pad(cells * 4), o_seg = o_base + pad(cells * 4), o_scan = o_seg + pad((size_t)(n_keys + 2) * 4);
-    if (const int rc = ensure_scratch(h, o_scan + pad(scan_bytes))) return rc;
+    Carve c;
+    const size_t o_key = c.take(nb * 4), o_in = c.take(nb * 4), o_out = c.take(nb * 4), o_counts = c.take(cells * 4),
+                 o_base = c.take(cells * 4), o_seg = c.take((size_t)(n_keys + 2) * 4), o_scan = c.take(scan_bytes);
+    if (const int rc = ensure_scratch(h, c.at)) return rc;
     unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
     int* const d_key = reinterpret_cast<int*>(base + o_key);
     int* const d_seg = reinterpret_cast<int*>(base + o_seg);
@@ -2368,10 +2221,7 @@ int syn_selfplay_run(syn_engine* h, const syn_rollout_config* cfg, uint64_t base
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     h->last_cache_hits = cstats[0];
     h->last_cache_misses = cstats[1];
-    if (kerr == 2)
-        return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d)",
-                    h->cap / 4, h->max_explores);
-    if (kerr) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+    if (const int rc = fail_search_error(h, kerr)) return rc;
     HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
     h->last_launches = 1;
     h->last_selfplay_games = n_games;
@@ -3222,17 +3072,16 @@ struct SamplerBuffers {
     void* tmp;
     size_t tmp_bytes;
 };
-static size_t sampler_pad(size_t b) { return (b + 255) & ~(size_t)255; }
 static int sampler_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total) {
     *tmp_bytes = 0;
     HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(nullptr, *tmp_bytes, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
                                                   (const int*)nullptr, (int*)nullptr, (int)n, 0, 64, h->stream));
-    *total = 2 * sampler_pad(n * 8) + 2 * sampler_pad(n * 4) + sampler_pad(*tmp_bytes);
+    *total = 2 * align256(n * 8) + 2 * align256(n * 4) + align256(*tmp_bytes);
     return SYN_OK;
 }
 static SamplerBuffers sampler_buffers_at(void* base, size_t n, size_t tmp_bytes) {
     unsigned char* b = static_cast<unsigned char*>(base);
-    const size_t k = sampler_pad(n * 8), i = sampler_pad(n * 4);
+    const size_t k = align256(n * 8), i = align256(n * 4);
     return {reinterpret_cast<unsigned long long*>(b), reinterpret_cast<unsigned long long*>(b + k), reinterpret_cast<int*>(b + 2 * k),
             reinterpret_cast<int*>(b + 2 * k + i), b + 2 * k + 2 * i, tmp_bytes};
 }
@@ -3271,7 +3120,7 @@ int syn_train_epochs_sampled(syn_engine* h, const syn_sampler_config* cfg, int n
     size_t tmp_bytes = 0, sort_bytes = 0;
     rc = sampler_bytes(h, n, &tmp_bytes, &sort_bytes);
     if (rc != SYN_OK) return rc;
-    const size_t o_sort = sampler_pad(lay.bytes());
+    const size_t o_sort = align256(lay.bytes());
     rc = ensure_scratch(h, o_sort + sort_bytes + 256);
     if (rc != SYN_OK) return rc;
     EpochStage st = epoch_stage_at(h->d_scratch, lay, ni);
@@ -3299,7 +3148,7 @@ int syn_debug_sampler(syn_engine* h, const syn_sampler_config* cfg, uint32_t epo
     size_t tmp_bytes = 0, sort_bytes = 0;
     int rc = sampler_bytes(h, n, &tmp_bytes, &sort_bytes);
     if (rc != SYN_OK) return rc;
-    rc = ensure_scratch(h, sort_bytes + sampler_pad(n) + 256);
+    rc = ensure_scratch(h, sort_bytes + align256(n) + 256);
     if (rc != SYN_OK) return rc;
     const SamplerBuffers B = sampler_buffers_at(h->d_scratch, n, tmp_bytes);
     unsigned char* d_flip = static_cast<unsigned char*>(h->d_scratch) + sort_bytes;
@@ -3351,7 +3200,6 @@ struct DedupOut {
     int m = 0;       // unique (with mirror: canonical) states, rows [0, m)
     int total = 0;   // rows in all: m, with mirror m + the mirror images of the classes that are not self-symmetric
 };
-static size_t dedup_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total, bool mirror = false) {
     const int ni = (int)n;
     size_t tmp_sort = 0, tmp_scan = 0;
@@ -3362,16 +3210,16 @@ static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* 
                                                 h->stream));
     *tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
     // sort keys/values (double buffers) | heads | scan | seg_start | outputs | cub temp
-    *total = 2 * dedup_align(n * 8) + 2 * dedup_align(n * 4) + 3 * dedup_align(n * 4) + 2 * dedup_align(n * 8) + dedup_align(n * 36) +
-             dedup_align(n * 12) + dedup_align(n * 4) + dedup_align(*tmp_bytes);
+    *total = 2 * align256(n * 8) + 2 * align256(n * 4) + 3 * align256(n * 4) + 2 * align256(n * 8) + align256(n * 36) +
+             align256(n * 12) + align256(n * 4) + align256(*tmp_bytes);
     if (mirror) {
         // the symmetric form (replay_kernels.cuh): outputs of 2n rows instead of n | canonical keys | flip | expand flags | their scan
         size_t tmp_excl = 0;
         HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_excl, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
         if (tmp_excl > *tmp_bytes) *tmp_bytes = tmp_excl;
         const size_t r = 2 * n;
-        *total = 2 * dedup_align(n * 8) + 2 * dedup_align(n * 4) + 3 * dedup_align(n * 4) + 2 * dedup_align(r * 8) + dedup_align(r * 36) +
-                 dedup_align(r * 12) + dedup_align(r * 4) + dedup_align(*tmp_bytes) + 2 * dedup_align(n * 8) + 3 * dedup_align(n * 4);
+        *total = 2 * align256(n * 8) + 2 * align256(n * 4) + 3 * align256(n * 4) + 2 * align256(r * 8) + align256(r * 36) +
+                 align256(r * 12) + align256(r * 4) + align256(*tmp_bytes) + 2 * align256(n * 8) + 3 * align256(n * 4);
     }
     return SYN_OK;
 }
@@ -3379,14 +3227,13 @@ static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsign
                              const float* d_pi, const float* d_v, size_t n, DedupOut* out, bool mirror = false) {
     const int ni = (int)n;
     const size_t rows = mirror ? 2 * n : n;   // (dedup_work_bytes' layout)
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
-    size_t o_k0 = take(n * 8), o_k1 = take(n * 8), o_i0 = take(n * 4), o_i1 = take(n * 4);
-    size_t o_head = take(n * 4), o_scan = take(n * 4), o_start = take(n * 4);
-    size_t o_omy = take(rows * 8), o_oop = take(rows * 8), o_opi = take(rows * 36), o_ov = take(rows * 12), o_on = take(rows * 4);
-    size_t o_tmp = take(tmp);
+    Carve c;
+    size_t o_k0 = c.take(n * 8), o_k1 = c.take(n * 8), o_i0 = c.take(n * 4), o_i1 = c.take(n * 4);
+    size_t o_head = c.take(n * 4), o_scan = c.take(n * 4), o_start = c.take(n * 4);
+    size_t o_omy = c.take(rows * 8), o_oop = c.take(rows * 8), o_opi = c.take(rows * 36), o_ov = c.take(rows * 12), o_on = c.take(rows * 4);
+    size_t o_tmp = c.take(tmp);
     size_t o_cmy = 0, o_cop = 0, o_flip = 0, o_exp = 0, o_dst = 0;
-    if (mirror) { o_cmy = take(n * 8); o_cop = take(n * 8); o_flip = take(n * 4); o_exp = take(n * 4); o_dst = take(n * 4); }
+    if (mirror) { o_cmy = c.take(n * 8); o_cop = c.take(n * 8); o_flip = c.take(n * 4); o_exp = c.take(n * 4); o_dst = c.take(n * 4); }
     char* base = work;
     auto P8 = [&](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     auto P4 = [&](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
@@ -3475,8 +3322,8 @@ static int replay_deduplicate_host(syn_engine* h, const char* who, bool mirror, 
     size_t tmp = 0, work = 0;
     int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
     if (rc != SYN_OK) return rc;
-    const size_t o_my = 0, o_op = o_my + dedup_align(n * 8), o_pi = o_op + dedup_align(n * 8), o_v = o_pi + dedup_align(n * 36);
-    const size_t o_work = o_v + dedup_align(n * 12);
+    const size_t o_my = 0, o_op = o_my + align256(n * 8), o_pi = o_op + align256(n * 8), o_v = o_pi + align256(n * 36);
+    const size_t o_work = o_v + align256(n * 12);
     rc = ensure_scratch(h, o_work + work + 256);
     if (rc != SYN_OK) return rc;
     char* base = static_cast<char*>(h->d_scratch);
@@ -3530,7 +3377,7 @@ int syn_positions_mirror(syn_engine* h, const uint64_t* my_bb, const uint64_t* o
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_positions_mirror");
     HIP_TRY(h, hipSetDevice(h->device));
     // device layout: my | op | pi | mirrored my | op | pi
-    const size_t s8 = dedup_align(n * 8), s36 = pis ? dedup_align(n * 36) : 0;
+    const size_t s8 = align256(n * 8), s36 = pis ? align256(n * 36) : 0;
     int rc = ensure_scratch(h, 4 * s8 + 2 * s36 + 256);
     if (rc != SYN_OK) return rc;
     char* base = static_cast<char*>(h->d_scratch);
@@ -3802,7 +3649,7 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
 
 // ------------------------------------------------------------------------------------------------ reanalyse
 // syn_replay_reanalyse (include/synthesis_amd.h "Reanalyse"; kernels in reanalyse_kernels.cuh): the selected rows of the buffer are
-// compacted into job arrays, searched in chunks by the MODE_SEARCH kernels (as match_run_impl drives them: roots and results stay on
+// compacted into job arrays, searched in chunks by the MODE_SEARCH kernels (as run_games drives them: roots and results stay on
 // the device) and rewritten by the write-back kernel. Scratch, each section 256-byte aligned:
 //   [sel n][skip n][dst n][job_my n][job_op n][job_row n][moved n][done n][counts: skipped, moved, done][cub temp][results of one chunk]
 // (the job arrays are sized for every row: the scratch is laid out before the number of selected rows is known)
@@ -3811,19 +3658,14 @@ struct ReanalyseLayout {
 };
 static ReanalyseLayout reanalyse_layout(size_t n, size_t tmp_bytes, size_t chunk) {
     ReanalyseLayout L{};
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t o = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return o;
-    };
-    L.sel = take(n * 4); L.skip = take(n * 4); L.dst = take(n * 4);
-    L.job_my = take(n * 8); L.job_op = take(n * 8); L.job_row = take(n * 4);
-    L.moved = take(n * 4); L.done = take(n * 4);
-    L.counts = take(16);
-    L.tmp = take(tmp_bytes);
-    L.results = take(chunk * sizeof(DevSearchResult));
-    L.total = at;
+    Carve c;
+    L.sel = c.take(n * 4); L.skip = c.take(n * 4); L.dst = c.take(n * 4);
+    L.job_my = c.take(n * 8); L.job_op = c.take(n * 8); L.job_row = c.take(n * 4);
+    L.moved = c.take(n * 4); L.done = c.take(n * 4);
+    L.counts = c.take(16);
+    L.tmp = c.take(tmp_bytes);
+    L.results = c.take(chunk * sizeof(DevSearchResult));
+    L.total = c.at;
     return L;
 }
 
@@ -3967,10 +3809,7 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
         h->last_launches = launches;
         h->last_cache_hits = hits;
         h->last_cache_misses = misses;
-        if (kerr == 2)
-            return fail(h, SYN_ERR_CAPACITY, "a tree ran out of node blocks (lane-per-tree kernel: %u blocks per tree for max_explores %d); "
-                                             "the rows of this chunk and of the later ones keep their old targets", h->cap / 4, h->max_explores);
-        if (kerr) return fail(h, SYN_ERR_HIP, "kernel reported a synchronisation timeout (bounded spin gave up)");
+        if (const int rc = fail_search_error(h, kerr, "; the rows of this chunk and of the later ones keep their old targets")) return rc;
         if (scope.cancelled()) {
             status = SYN_ERR_CANCELLED;
             break;
@@ -4006,10 +3845,9 @@ static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_cano
     const size_t rows_max = mirror ? 2 * n : n;   // rows of a de-duplicated part
     size_t tmp_scan = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, (int)rows_max, h->stream));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
-    const size_t o_part = take(n * 64), o_flag = take(rows_max * 4), o_rank = take(rows_max * 4), o_tmp = take(tmp_scan);
-    const size_t o_work = off;
+    Carve c;
+    const size_t o_part = c.take(n * 64), o_flag = c.take(rows_max * 4), o_rank = c.take(rows_max * 4), o_tmp = c.take(tmp_scan);
+    const size_t o_work = c.at;
     int rc = ensure_scratch(h, o_work + 4096);
     if (rc != SYN_OK) return rc;
     const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
@@ -4257,11 +4095,10 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
     }
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t nb = (n_rows + DS_BLOCK - 1) / DS_BLOCK, nch = (nb + DS_CHUNK_BLOCKS - 1) / DS_CHUNK_BLOCKS;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += dedup_align(bytes); return o; };
-    const size_t o_rec = take(nb * sizeof(DsBlockRecord)), o_chunk = take(nch * sizeof(DsChunkSum)), o_tot = take(sizeof(DsTotals));
-    const size_t o_bl = take(block_losses ? nb * 8 : 0), o_lg = take(row_logits ? n_rows * 48 : 0), o_kl = take(row_kl ? n_rows * 8 : 0);
-    int rc = ensure_scratch(h, off + 256);
+    Carve c;
+    const size_t o_rec = c.take(nb * sizeof(DsBlockRecord)), o_chunk = c.take(nch * sizeof(DsChunkSum)), o_tot = c.take(sizeof(DsTotals));
+    const size_t o_bl = c.take(block_losses ? nb * 8 : 0), o_lg = c.take(row_logits ? n_rows * 48 : 0), o_kl = c.take(row_kl ? n_rows * 8 : 0);
+    int rc = ensure_scratch(h, c.at + 256);
     if (rc != SYN_OK) return rc;
     char* sc = static_cast<char*>(h->d_scratch);
     // the parameters: the trainer's own buffers (read only), or the caller's blob built into the evaluation's own image buffer

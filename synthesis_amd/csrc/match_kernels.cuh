@@ -1,18 +1,14 @@
-// Device-resident matches (syn_match_run / syn_match_run_sides, engine.hip): what runs between two plies' search launches.
-// The live games of a match are five parallel arrays — my[i], op[i] (the position, mover's stones first: the roots of the next search
+// Device-resident games (run_games in engine.hip, behind syn_match_run / syn_match_run_sides / syn_tournament_run): the live games'
+// arrays, the per-game outputs and the rules of one game step. The loop's kernels are in tournament_kernels.cuh.
+// The live games of a call are five parallel arrays — my[i], op[i] (the position, mover's stones first: the roots of the next search
 // launch), id[i] (which game of the call job i is), seed[i] and word[i] (the game's rollout generator, StdRng::seed_from_u64(seed), and
-// its first unused output word: what a baseline side's frozen_rollout_kernel reads and advances in place) — in game order. After a
-// ply's search
-//     match_advance_kernel   plays job i's best_action on its position and writes keep[i]: 1 = the game goes on, 0 = it ended here
-//                            (its reward, ply count, final position and stream position are written to the call's outputs, indexed by
-//                            game). One template over the search's result record: DevSearchResult (a network side's MODE_SEARCH launch)
-//                            or FrozenResult (a baseline side's), of which it reads best_action and num_nodes alone.
-//     an exclusive sum of keep (hipcub, as syn_replay_keep_games_from)
-//     match_compact_kernel   moves every surviving job to its rank among the survivors, into the second set of arrays, and leaves the
-//                            number of survivors — the one word the host reads per ply
-// A game's record depends on its own position and its own generator alone, never on its job index: compaction keeps game order and
-// carries the generator with the game, and nothing here is indexed by job except the arrays it permutes. One thread per job, plain
-// loads and stores, no LDS, no atomics, and no workgroup waits for another.
+// its first unused output word: what a baseline player's frozen_rollout_kernel reads and advances in place). After a ply's search
+// match_advance_job plays job i's best_action on its position and says whether the game goes on; when it ended, its reward, ply count,
+// final position and stream position are written to the call's outputs, indexed by game. One template over the search's result
+// record: DevSearchResult (a network player's MODE_SEARCH launch) or FrozenResult (a baseline player's), of which it reads best_action
+// and num_nodes alone.
+// A game's record depends on its own position and its own generator alone, never on its job index: the loop's regroup carries the
+// generator with the game, and nothing here is indexed by job except the arrays it permutes. Plain loads and stores, no LDS, no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,7 +23,7 @@ constexpr unsigned char MATCH_NO_MOVE = 255;   // a move slot the game never rea
 // a generator's stream position beyond which the next baseline search could run past 2^32 output words (frozen_rollout_kernel keeps
 // 32 bits of it): syn_frozen_search_rollout refuses such a start, a match ends with the code below
 constexpr unsigned long long MATCH_WORD_LIMIT = 0xC0000000ull;
-constexpr int MATCH_ERR_STREAM = 0x10000;      // live_out = -MATCH_ERR_STREAM (the search kernels' own error words are 1 and 2)
+constexpr int MATCH_ERR_STREAM = 0x10000;      // the ply's error word = -MATCH_ERR_STREAM (the search kernels' own error words are 1 and 2)
 
 // The per-game outputs of a call (device), indexed by game.
 struct MatchOut {
@@ -43,8 +39,8 @@ struct MatchOut {
 // returns SYN_ERR_CANCELLED then. The column is checked before it is played: a record never comes from an illegal move.
 // word[i] is the stream position the ply's search left (a network ply leaves it alone). A position past MATCH_WORD_LIMIT raises
 // stream_error[0]: every thread that sees one stores the same 1, so the plain stores need no order among themselves.
-// The rules for ONE job (shared with tournament_advance_kernel, tournament_kernels.cuh): job i's search record is `res`, its game g.
-// Returns whether the game goes on.
+// The rules for ONE job (tournament_advance_kernel, tournament_kernels.cuh, runs them per group): job i's search record is `res`,
+// its game g. Returns whether the game goes on.
 template <class Result>
 SYN_DEV bool match_advance_job(const Result& res, int i, int g, int ply, unsigned long long* __restrict__ my,
                                unsigned long long* __restrict__ op, const unsigned long long* __restrict__ word,
@@ -75,17 +71,7 @@ SYN_DEV bool match_advance_job(const Result& res, int i, int g, int ply, unsigne
     return true;
 }
 
-template <class Result>
-__global__ void __launch_bounds__(256) match_advance_kernel(
-    const Result* __restrict__ results, int n_live, int ply, unsigned long long* __restrict__ my, unsigned long long* __restrict__ op,
-    const int* __restrict__ id, const unsigned long long* __restrict__ word, unsigned* __restrict__ keep, int* __restrict__ stream_error,
-    MatchOut out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_live) return;
-    keep[i] = match_advance_job(results[i], i, id[i], ply, my, op, word, stream_error, out) ? 1u : 0u;
-}
-
-// The live games' arrays, one set: a ply's compaction reads one set and writes the other.
+// The live games' arrays, one set: a ply's regroup reads one set and writes the other.
 struct MatchLive {
     unsigned long long* my;
     unsigned long long* op;
@@ -93,28 +79,5 @@ struct MatchLive {
     unsigned long long* seed;
     unsigned long long* word;
 };
-
-// Stable compaction: surviving job i goes to dst[i] (= its rank among the survivors) of the second arrays, its generator with it. The
-// thread of the last job also writes live_out[0]: the number of survivors, or -(the search kernel's error word) when the ply's search
-// reported one (EngineParams::error / FrozenParams::error; the host's next launch resets it), or -MATCH_ERR_STREAM when a generator
-// ran past MATCH_WORD_LIMIT (stream_error, written by the advance kernel that ran before this one on the same stream).
-__global__ void __launch_bounds__(256) match_compact_kernel(
-    const unsigned* __restrict__ keep, const unsigned* __restrict__ dst, int n_live, MatchLive from, MatchLive to,
-    const int* __restrict__ search_error, const int* __restrict__ stream_error, int* __restrict__ live_out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_live) return;
-    const unsigned k = keep[i], d = dst[i];
-    if (k && d < (unsigned)n_live) {
-        to.my[d] = from.my[i];
-        to.op[d] = from.op[i];
-        to.id[d] = from.id[i];
-        to.seed[d] = from.seed[i];
-        to.word[d] = from.word[i];
-    }
-    if (i == n_live - 1) {
-        const int err = search_error[0];
-        live_out[0] = err != 0 ? -err : (stream_error[0] != 0 ? -MATCH_ERR_STREAM : (int)(d + k));
-    }
-}
 
 }  // namespace syn

@@ -1,10 +1,11 @@
-// Device-resident tournaments (syn_tournament_run, engine.hip): what runs between two plies' search launches when the live games belong
-// to K players instead of two. The live games are match_kernels.cuh's five parallel arrays, kept GROUPED BY MOVER — group p is the range
+// Device-resident games (run_games in engine.hip, behind syn_match_run / syn_match_run_sides / syn_tournament_run): what runs between
+// two plies' search launches. The live games are match_kernels.cuh's five parallel arrays, kept GROUPED BY MOVER — group p is the range
 // [seg[p], seg[p + 1]) and holds the games player p moves in at this ply, in game order — so that a ply needs one search launch per
-// player, over that player's range, whatever pairing each of its games belongs to. After a ply's searches
-//     tournament_advance_kernel   match_advance_kernel's rules (match_advance_job) for one group's range, and key[i]: the player that
-//                                 moves next in job i's game (from device copies of the schedule, through id[i]), or n_keys when the
-//                                 game ended here or its root was not searched (dropped)
+// player, over that player's range, whatever pairing each of its games belongs to. (A match is two players with player 0 first in
+// every game: all its live games share one mover, so every ply has one group.) After a ply's searches
+//     tournament_advance_kernel   the rules of one step (match_advance_job) for one group's range, and key[i]: the player that moves
+//                                 next in job i's game (from device copies of the schedule, through id[i]), or n_keys when the game
+//                                 ended here or its root was not searched (dropped)
 //     tournament_count_kernel     per 256-job workgroup, how many of its jobs hold each key: a key-major [n_keys + 1][n_blocks] matrix
 //     an exclusive sum over that matrix (hipcub): cell (k, b) becomes the position of the first job of workgroup b with key k
 //     tournament_scatter_kernel   moves every surviving job to that position plus its rank among its workgroup's jobs of the same key,
@@ -25,8 +26,8 @@ constexpr int TOURNAMENT_MAX_KEYS = 64;                 // SYN_TOURNAMENT_MAX_PL
 constexpr int TOURNAMENT_BLOCK = 256;                   // four wave64s
 constexpr int TOURNAMENT_WAVES = TOURNAMENT_BLOCK / 64;
 
-// match_advance_kernel for the jobs [lo, lo + n) of the live arrays: `results` is that range's own record array (job lo's record
-// first). first / second: the schedule, per game.
+// match_advance_job for the jobs [lo, lo + n) of the live arrays, one thread per job: `results` is that range's own record array (job
+// lo's record first). first / second: the schedule, per game.
 template <class Result>
 __global__ void __launch_bounds__(256) tournament_advance_kernel(
     const Result* __restrict__ results, int lo, int n, int ply, unsigned long long* __restrict__ my, unsigned long long* __restrict__ op,

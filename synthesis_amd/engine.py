@@ -514,18 +514,14 @@ class Engine:
         deterministic configurations. Both blobs are of the engine's current network kind and run in its current arithmetic; the
         engine's own network and policy cache are untouched. Returns dict(rewards [n] for `first`, plies [n], moves [n, 63] (255 = no
         move), final_bb [n, 2] = (first's stones, second's stones))."""
-        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
-        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
-        if my.size != op.size:
-            raise ValueError("start_my and start_op must have the same length")
+        my, op, _ = self._match_starts(start_my, start_op)
         b1 = np.ascontiguousarray(blob_first, dtype=np.float32).ravel()
         b2 = np.ascontiguousarray(blob_second, dtype=np.float32).ravel()
         if b1.size != b2.size:
             raise ValueError("both blobs must be parameters of the same network")
         n = int(my.size)
         players = [CMatchPlayer(int(p.explores), int(p.action), p.mcts_cfg.to_c()) for p in (first, second)]
-        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
-                   final_bb=np.zeros((n, 2), np.uint64))
+        out = self._match_outputs(n, rng_words=False)
         self._check(self._lib.syn_match_run(self._h, C.byref(players[0]), C.byref(players[1]), _p(b1), _p(b2), b1.size, _p(my), _p(op), n,
                                             _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]), _p(out["final_bb"])))
         return out
@@ -565,16 +561,9 @@ class Engine:
 
     def match_run_sides_c(self, side_first, side_second, start_my, start_op, seeds=None):
         """match_run_sides on two CMatchSide structs as they are (the blobs they point to must stay alive for the call)"""
-        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
-        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
-        if my.size != op.size:
-            raise ValueError("start_my and start_op must have the same length")
+        my, op, sd = self._match_starts(start_my, start_op, seeds)
         n = int(my.size)
-        sd = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n,)))
-        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
-                   final_bb=np.zeros((n, 2), np.uint64), rng_words=np.zeros(n, np.uint64))
+        out = self._match_outputs(n)
         self._check(self._lib.syn_match_run_sides(self._h, C.byref(side_first), C.byref(side_second), _p(my), _p(op), _p(sd), n,
                                                   _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]), _p(out["final_bb"]),
                                                   _p(out["rng_words"])))
@@ -596,22 +585,37 @@ class Engine:
     def tournament_run_c(self, sides, first, second, start_my, start_op, seeds=None, n_players=None):
         """tournament_run on CMatchSide structs as they are (the blobs they point to must stay alive for the call); n_players
         overrides len(sides) (the refusal tests)"""
-        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
-        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
         fi = np.ascontiguousarray(first, dtype=np.int32).ravel()
         se = np.ascontiguousarray(second, dtype=np.int32).ravel()
-        if not (my.size == op.size == fi.size == se.size):
-            raise ValueError("first, second, start_my and start_op must have the same length")
+        my, op, sd = self._match_starts(start_my, start_op, seeds, "first, second, start_my and start_op", (fi.size, se.size))
         n = int(my.size)
-        sd = None
-        if seeds is not None:
-            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n,)))
         arr = (CMatchSide * max(len(sides), 1))(*sides)
-        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
-                   final_bb=np.zeros((n, 2), np.uint64), rng_words=np.zeros(n, np.uint64))
+        out = self._match_outputs(n)
         self._check(self._lib.syn_tournament_run(self._h, arr, len(sides) if n_players is None else int(n_players), _p(fi), _p(se), _p(my),
                                                  _p(op), _p(sd), n, _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]),
                                                  _p(out["final_bb"]), _p(out["rng_words"])))
+        return out
+
+    @staticmethod
+    def _match_starts(start_my, start_op, seeds=None, names="start_my and start_op", other_sizes=()):
+        """(my, op, seeds or None) as the game loops take them: contiguous uint64 [n], seeds broadcast to n; ValueError when the
+        lengths (other_sizes: the schedule's) differ"""
+        my = np.ascontiguousarray(start_my, dtype=np.uint64).ravel()
+        op = np.ascontiguousarray(start_op, dtype=np.uint64).ravel()
+        if any(size != my.size for size in (op.size, *other_sizes)):
+            raise ValueError(f"{names} must have the same length")
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (my.size,)))
+        return my, op, sd
+
+    @staticmethod
+    def _match_outputs(n, rng_words=True):
+        """the per-game output arrays of the game loops, as they read for a game that was never played"""
+        out = dict(rewards=np.zeros(n, np.float32), plies=np.zeros(n, np.int32), moves=np.full((n, 63), 255, np.uint8),
+                   final_bb=np.zeros((n, 2), np.uint64))
+        if rng_words:
+            out["rng_words"] = np.zeros(n, np.uint64)
         return out
 
     @staticmethod

@@ -223,6 +223,17 @@ def test_game_counts_on_a_16_slot_engine(engine16, blobs, openings, expected_ab,
     assert_games_equal(got, expected_ab, f"{n} games", n=n)
 
 
+def test_timing_counts_four_launches_per_ply(engine32, blobs, openings, expected_ab):
+    """syn_last_timing's documented count for a match: every ply has one group, so one search, one advance and the regroup's count and
+    scatter — four launches for every ply the longest game lasted"""
+    pa, pb = device_players()
+    got = engine32.match_run(pa, pb, blobs[0], blobs[1], openings[0][:17], openings[1][:17])
+    assert_games_equal(got, expected_ab, "17 games", n=17)
+    ms, launches = engine32.last_timing()
+    assert ms > 0.0
+    assert launches == 4 * int(got["plies"].max())
+
+
 def pattern_board():
     """A full 9x7 board without four in a row: cell (row, col) belongs to side (col // 2 + row) % 2 — columns alternate row by row,
     rows run in pairs, both diagonals read 0110 / 0011. Returns the two sides' bitboards."""

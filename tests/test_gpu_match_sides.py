@@ -180,6 +180,19 @@ def test_default_sides_are_match_run(engine32, engine32_f16, blobs, openings, wh
 
 
 # ---- 2
+def test_timing_counts_four_launches_per_ply_with_a_baseline_side(engine32, blobs, openings):
+    """syn_last_timing's documented count, a network side against a baseline: one group per ply whichever kind of search it launches"""
+    from synthesis_amd import match
+
+    pa, _ = net_players()
+    got = engine32.match_run_sides(replace(pa, weights=blobs[0]), match.vanilla_player(30), openings[0][:17], openings[1][:17],
+                                   seeds=np.arange(17, dtype=np.uint64))
+    ms, launches = engine32.last_timing()
+    assert ms > 0.0
+    assert got["plies"].min() >= 1
+    assert launches == 4 * int(got["plies"].max())
+
+
 @pytest.fixture(scope="module")
 def cross(oracle):
     """blob A in f32 against blob B in f16x2, A first and B first, and the same games with one arithmetic on both sides — all from the

@@ -5,7 +5,7 @@ against the host path of match.play_match on identical games, on ONE engine of O
     python tools/match_sides_ab.py --out profiles/match_sides_ab.json
 
 Arm A: match.play_match — per ply the positions, seeds and stream positions go up, one syn_frozen_result per root (or one
-syn_search_result) comes down, numpy steps the boards. Arm B: match.play_match_device — one call, one word read back per ply.
+syn_search_result) comes down, numpy steps the boards. Arm B: match.play_match_device — one call, four words read back per ply.
 Workloads, from the empty board, game g on StdRng::seed_from_u64(g):
   vanilla     VanillaMCTS800 against VanillaMCTS200 (mcts_vs_mcts), at the size tools/vanilla_bench.py uses (16,384 games)
   checkpoint  the trained golden Connect4Net checkpoint, 800 explores, parity configuration, against VanillaMCTS800

@@ -8,8 +8,13 @@ same schedule as ONE Engine.match_run_sides call per ordered pairing. Both arms 
 Workloads (sizes a user would run), 512 openings of 8 plies, 800 explores unless said otherwise:
   round_robin8   eight network players, all 56 ordered pairings: 28,672 games
   gauntlet6x2    six network players against VanillaMCTS800 and VanillaMCTS3200, both colours: 24 ordered pairings, 12,288 games
-  two_players    two network players, 4,096 openings, both colours: the tournament against match_run_sides itself (two calls) — what
-                 the general loop costs the case the match loop was written for
+  two_players    two network players, 4,096 openings, both colours: the tournament against match_run_sides itself (two calls)
+  one_match      ONE ordered pairing of two network players (player 0 always first) at 512, 4,096 and 65,536 openings: the tournament
+                 against one match_run_sides call — one group and one search launch per ply in both arms
+  one_match_vanilla  one ordered pairing, a network player first against VanillaMCTS800, 512 openings: the same with a baseline group
+The last three asked what the tournament's loop costs a match while the match had a loop of its own (profiles/tournament_ab.json,
+profiles/match_fold_ab.json). The match now runs in the tournament's loop, so with the in-tree library their two arms issue the same
+launches; against an older build named by SYNTHESIS_AMD_LIB they still compare the two loops.
 Per workload: 2 warm-up and 6 timed runs per arm, host clock around calls that end in a device synchronise; median and min-max; a gap
 counts as resolved only when the medians differ by more than the larger of the two ranges. syn_last_timing's device time and launch
 count are reported beside each arm (summed over the pairwise arm's calls)."""
@@ -47,14 +52,15 @@ def network_players(n, explores):
     return out
 
 
-def run_workload(eng, name, players, pairs, n_openings, plies, warmup, timed):
+def run_workload(eng, name, players, pairs, n_openings, plies, warmup, timed, one_colour=False):
     import numpy as np
 
     from synthesis_amd import arena
 
     my, op = arena.random_openings(n_openings, plies, seed=1)
     sch = arena.schedule(pairs, n_openings, len(players))
-    first, second, o = sch["first"], sch["second"], sch["opening"]
+    keep = sch["a_first"] if one_colour else np.ones(sch["first"].size, bool)   # one_colour: the pairs as given, never reversed
+    first, second, o = sch["first"][keep], sch["second"][keep], sch["opening"][keep]
     seeds = (np.uint64(1) + np.arange(n_openings, dtype=np.uint64))[o]
     pairings = sorted(set(zip(first.tolist(), second.tolist())))
     games_of = {pq: np.nonzero((first == pq[0]) & (second == pq[1]))[0] for pq in pairings}
@@ -109,9 +115,10 @@ def run_workload(eng, name, players, pairs, n_openings, plies, warmup, timed):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workloads", nargs="+", default=["round_robin8", "gauntlet6x2", "two_players"],
-                    choices=["round_robin8", "gauntlet6x2", "two_players"])
+                    choices=["round_robin8", "gauntlet6x2", "two_players", "one_match", "one_match_vanilla"])
     ap.add_argument("--openings", type=int, default=512)
     ap.add_argument("--two-player-openings", type=int, default=4096)
+    ap.add_argument("--one-match-openings", type=int, nargs="+", default=[512, 4096, 65536])
     ap.add_argument("--opening-plies", type=int, default=8)
     ap.add_argument("--explores", type=int, default=800)
     ap.add_argument("--warmup", type=int, default=2)
@@ -129,6 +136,10 @@ def main():
     from synthesis_amd import arena, match
 
     def workload(name):
+        if name.startswith("one_match_vanilla"):
+            return network_players(1, args.explores) + [match.vanilla_player(800)], [(0, 1)], args.openings
+        if name.startswith("one_match"):
+            return network_players(2, args.explores), [(0, 1)], int(name.rsplit("_", 1)[1])
         if name == "round_robin8":
             players = network_players(8, args.explores)
             return players, arena.round_robin_pairs(8), args.openings
@@ -137,12 +148,16 @@ def main():
             return players, arena.gauntlet_pairs(6, 2), args.openings
         return network_players(2, args.explores), [(0, 1)], args.two_player_openings
 
+    names = []
+    for name in args.workloads:   # one_match: one workload per size
+        names += [f"one_match_{n}" for n in args.one_match_openings] if name == "one_match" else [name]
     done = []
-    for name in args.workloads:
+    for name in names:
         players, pairs, n_openings = workload(name)
-        n_games = 2 * len(pairs) * n_openings
+        one_colour = name.startswith("one_match")
+        n_games = (1 if one_colour else 2) * len(pairs) * n_openings
         with sa.Engine(concurrent_games=min(n_games, 65536), max_explores=args.explores, device=args.device) as eng:
-            done.append(run_workload(eng, name, players, pairs, n_openings, args.opening_plies, args.warmup, args.timed))
+            done.append(run_workload(eng, name, players, pairs, n_openings, args.opening_plies, args.warmup, args.timed, one_colour))
         print(json.dumps(done[-1]), flush=True)
         rec = dict(tool="tools/tournament_ab.py", kernel_source_hash=bench.kernel_source_hash(), device=torch.cuda.get_device_name(args.device),
                    arms="tournament = one Engine.tournament_run for the whole schedule; pairwise = one Engine.match_run_sides per ordered "
