@@ -94,7 +94,19 @@ def main():
     ap.add_argument("--reanalyse-explores", type=int, default=None, help="explores of a reanalysis search (default: --explores)")
     ap.add_argument("--reanalyse-value-mix", type=float, default=0.0, help="w in [0, 1]: a reanalysed row's v becomes v * (1 - w) + the new "
                     "search's target_q * w (0 = v is left alone)")
+    ap.add_argument("--state", default="", help="path of the run's state file (LearningLoop.save_state: one .npz with the trainer, the "
+                    "replay buffer, the counters and their digests); written after every --save-every-th iteration and after the last")
+    ap.add_argument("--save-every", type=int, default=0, help="save --state after every K-th iteration (0 = after the last one only)")
+    ap.add_argument("--resume", default="", help="continue the run a state file was saved from (LearningLoop.restore_state): the same "
+                    "arguments (--replay may differ), --iterations is the run's total; the iterations that follow are bit for bit those "
+                    "of a run that never stopped")
+    ap.add_argument("--digests", action="store_true", help="every iteration's record gains the 64-bit fingerprints of the trainer, the "
+                    "replay buffer and the data sets (syn_state_digest): equal words in two logs = equal bits in two runs")
     args = ap.parse_args()
+    if (args.state or args.resume or args.digests or args.save_every) and args.data_parallel:
+        raise SystemExit("--state, --save-every, --resume and --digests belong to the learning loop")
+    if args.save_every < 0 or (args.save_every and not args.state):
+        raise SystemExit("--save-every K needs K >= 0 and --state PATH")
     if args.reanalyse and args.data_parallel:
         raise SystemExit("--reanalyse belongs to the learning loop")
     if not 0.0 <= args.reanalyse <= 1.0 or not 0.0 <= args.reanalyse_value_mix <= 1.0:
@@ -154,12 +166,17 @@ def main():
                             precision=args.precision, logs_dir=args.logs or None, sampler=args.sampler,
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
                             batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, reanalyse=args.reanalyse,
-                            reanalyse_explores=args.reanalyse_explores, reanalyse_value_mix=args.reanalyse_value_mix, **hyper)
+                            reanalyse_explores=args.reanalyse_explores, reanalyse_value_mix=args.reanalyse_value_mix, digests=args.digests,
+                            **hyper)
+        if args.resume:
+            loop.restore_state(args.resume)
     log = []
     eval_eng = None
-    for it in range(args.iterations):
+    for it in range(loop.iterations_done if loop is not None else 0, args.iterations):
         if loop is not None:
             rec = loop.iteration(cfg, args.games_per_train, args.games_to_keep, args.epochs, args.batch_size)
+            if args.state and (it + 1 == args.iterations or (args.save_every and (it + 1) % args.save_every == 0)):
+                loop.save_state(args.state)
             sec = rec["seconds"]
             rec["selfplay_games_per_s"] = args.games_per_train / max(sec["selfplay"], 1e-9)
             if rank == 0:

@@ -524,6 +524,16 @@ int syn_trainer_set_batch_mode(syn_engine* h, int mode, int max_workgroups);
 int syn_trainer_get_batch_mode(syn_engine* h, int* mode, int* max_workgroups, int* last_grid);
 /* Copies out parameters / Adam moments / last gradient (each may be NULL) and the optimiser step count. */
 int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long long* step, float* grads);
+/* The inverse of syn_trainer_get_state (not in the reference, whose learner lives and dies with its process): an initialised trainer of
+ * the same network (n_floats must be that network's) gets the parameters, both Adam moments and the optimiser step count set bit for
+ * bit, and every derived device image rebuilt the way syn_trainer_init* builds it (Connect4Net: the forward and the transposed fragment
+ * image and the epoch kernel's second buffer), so that the next syn_train_step, syn_train_gradients_*, syn_train_epoch (persistent,
+ * queued or micro) and syn_train_epochs_sampled continue from the new state exactly as the learner the state was read from would have.
+ * Kept as they are: precision, batch mode and workgroup cap, the hyper-parameters, the learner's data set and the evaluation set, the
+ * last gradient, the engine's network and the policy cache. Nothing is published and no start-up self-check runs again.
+ * Refused, with the trainer bit for bit as it was: before syn_trainer_init* (SYN_ERR_NO_WEIGHTS); a NULL pointer, a wrong n_floats or a
+ * negative step (SYN_ERR_INVALID_ARGUMENT). Non-finite values are accepted as they are: this call restores, it does not judge. */
+int syn_trainer_set_state(syn_engine* h, const float* blob, const float* m, const float* v, size_t n_floats, long long step);
 /* Replaces: vs.save(model_{i+1}.ot) + the workers' vs.load (alpha_zero.rs:97,194): the trained parameters become the
  * engine's policy for syn_policy_eval_batch / syn_mcts_search / syn_selfplay_run, in the arithmetic the engine is in (both learners:
  * an engine in SYN_NET_ARITH_F16X2 gets the published network's f16x2 image). Before this library's Connect4ConvNet f16x2 support,
@@ -793,6 +803,37 @@ typedef struct syn_reanalyse_stats {
 } syn_reanalyse_stats;
 int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_reanalyse_config* cfg,
                          syn_reanalyse_stats* out /*may be NULL*/, int64_t* selected_rows /*may be NULL*/, size_t capacity);
+
+/* ---- State digests (csrc/digest_kernels.cuh; not in the reference): a 64-bit fingerprint of a piece of engine state,
+ * computed where the state lives, so that "these two runs hold the same bits" is one word in a log instead of a download.
+ * Definition. A component is a sequence of 32-bit words w_0 .. w_{L-1}: its arrays, concatenated in the order given below, each read as
+ * it lies in memory (a 64-bit value is its low word followed by its high word). With finalise and sm as in "Device-side epoch sampler"
+ * above, GOLDEN = 0x9E3779B97F4A7C15, T = 0xD16E57000000AA00 + what, and all arithmetic unsigned 64-bit with wrap-around:
+ *   a_i    = finalise(T + (i + 1) * GOLDEN)                  i as a 64-bit number
+ *   h_i    = sm(a_i, w_i)                                    = finalise(a_i + ((w_i + 1) mod 2^32) * GOLDEN)
+ *   S      = (h_0 + h_1 + ... + h_{L-1}) mod 2^64            0 when L = 0
+ *   digest = sm(sm(S ^ T, hi32(L)), lo32(L))
+ * The sum is associative and commutative, so the word does not depend on how the device splits the work; the position i enters every
+ * term, so moving a word changes it. Known answers for T = 0xD16E57000000AA01: no words 0x6dc4edd735556cbf, the single word 0
+ * 0x831dcd5c179d866e, the words 0 .. 999 ascending 0x17b9ceedb8bf8015, the words 999 .. 0 descending 0x8c9cab522ff11f09.
+ * Word sequences:
+ *   SYN_DIGEST_TRAINER     w[P], m[P], v[P] as f32 words (P = 30,492 or 12,412), then the step count's low and high word. The last
+ *                          gradient is not part of it (it is scratch: every step overwrites it before reading it).
+ *   SYN_DIGEST_NETWORK     the P parameters the engine's installed network was built from, in blob order. The arithmetic and the policy
+ *                          cache are not part of it: results never depend on the cache. Computed on the HOST from the engine's own copy
+ *                          of those parameters (that is where they are; the device holds derived images only); nothing is launched.
+ *   SYN_DIGEST_REPLAY      the device replay buffer's rows [0, n): my[n], op[n], gid[n], pi[n][9], v[n][3] — 18 n words.
+ *   SYN_DIGEST_TRAIN_DATA  the learner's data set: my[n], op[n], pi[n][9], v[n][3] — 16 n words.
+ *   SYN_DIGEST_EVAL_DATA   the evaluation set, likewise.
+ * *n_words = L (either output may be NULL). An empty or never-reserved buffer or data set is SYN_OK with the digest of no words and
+ * nothing launched. On the device: one grid-stride launch that leaves a partial sum per workgroup, and a one-workgroup launch that adds
+ * them and closes the digest; no atomics. max_workgroups = 0 lets the library choose the first grid, any other value caps it (the word
+ * does not depend on it). The call is an OBSERVER in syn_dataset_evaluate's sense: everything it reads is bit for bit what it was.
+ * syn_last_timing reports the device time and the number of its launches (2, or 0 where nothing was launched).
+ * Refused, with everything unchanged: an unknown `what` or a negative max_workgroups (SYN_ERR_INVALID_ARGUMENT); SYN_DIGEST_TRAINER before
+ * syn_trainer_init*, SYN_DIGEST_NETWORK before any weights (SYN_ERR_NO_WEIGHTS). */
+enum { SYN_DIGEST_TRAINER = 1, SYN_DIGEST_NETWORK = 2, SYN_DIGEST_REPLAY = 3, SYN_DIGEST_TRAIN_DATA = 4, SYN_DIGEST_EVAL_DATA = 5 };
+int syn_state_digest(syn_engine* h, int what, int max_workgroups, uint64_t* digest, uint64_t* n_words);
 
 /* Timing of the last syn_selfplay_run / syn_mcts_search / *_device call on this handle, measured with HIP events on
  * the engine stream: kernel_ms = device time of the dominant kernel launch(es), n_launches = how many. */

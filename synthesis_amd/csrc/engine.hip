@@ -41,6 +41,7 @@
 #include "train_conv_mfma.cuh"
 #include "train_micro.cuh"
 #include "dataset_eval.cuh"
+#include "digest_kernels.cuh"
 #include "lane_instances.h"
 #include "launch_plan.hpp"
 #include "free_kernel.cuh"
@@ -2397,6 +2398,21 @@ static bool learner_self_check(syn_engine* h, const LearnerStart& start, bool* s
     return ok;
 }
 
+// The two fragment-order images the matrix-core Connect4Net learner reads its A operands from (train_mfma.cuh); adam_image_kernel
+// keeps them in step with the canonical weights afterwards. The slot table is checked by its bit patterns: a restored state may hold NaNs.
+static int build_trainer_images(syn_engine* h, const float* blob, std::vector<float>& img, std::vector<float>& timg) {
+    timg.assign((size_t)TrainImg::T_FLOATS, 0.0f);
+    build_weight_image(blob, img);
+    for (int p = 0; p < TrainGeom::NUM_PARAMS; p++) {
+        int fwd, tr;
+        train_image_slots(p, fwd, tr);
+        if (std::memcmp(&img[(size_t)fwd], &blob[p], 4) != 0)
+            return fail(h, SYN_ERR_HIP, "internal: image slot table disagrees with build_weight_image at %d", p);
+        if (tr >= 0) timg[(size_t)tr] = blob[p];
+    }
+    return SYN_OK;
+}
+
 int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const syn_train_config* cfg) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     if (!blob || !cfg) return fail(h, SYN_ERR_INVALID_ARGUMENT, "blob/cfg is NULL");
@@ -2406,16 +2422,9 @@ int syn_trainer_init(syn_engine* h, const float* blob, size_t n_floats, const sy
     int rc = alloc_trainer_buffers(h);
     if (rc != SYN_OK) return rc;
     auto& L = h->learner;
-    // the two fragment-order images the matrix-core learner reads its A operands from (train_mfma.cuh); adam_image_kernel
-    // keeps them in step with the canonical weights afterwards
-    std::vector<float> img, timg((size_t)TrainImg::T_FLOATS, 0.0f);
-    build_weight_image(blob, img);
-    for (int p = 0; p < TrainGeom::NUM_PARAMS; p++) {
-        int fwd, tr;
-        train_image_slots(p, fwd, tr);
-        if (img[(size_t)fwd] != blob[p]) return fail(h, SYN_ERR_HIP, "internal: image slot table disagrees with build_weight_image at %d", p);
-        if (tr >= 0) timg[(size_t)tr] = blob[p];
-    }
+    std::vector<float> img, timg;
+    rc = build_trainer_images(h, blob, img, timg);
+    if (rc != SYN_OK) return rc;
     const LearnerStart start{0, blob, &img, &timg};
     rc = learner_load_state(h, start);
     if (rc != SYN_OK) return rc;
@@ -3175,6 +3184,37 @@ int syn_trainer_get_state(syn_engine* h, float* blob, float* m, float* v, long l
     if (grads) HIP_TRY(h, hipMemcpyAsync(grads, L.d_tgrad, bytes, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (step) *step = L.train_step;
+    return SYN_OK;
+}
+
+// The inverse of syn_trainer_get_state: parameters, moments and step count of an initialised trainer, and the images derived from the
+// parameters as syn_trainer_init builds them. Everything is checked (and Connect4Net's images are built) before the first copy is queued.
+int syn_trainer_set_state(syn_engine* h, const float* blob, const float* m, const float* v, size_t n_floats, long long step) {
+    int rc = learner_check(h);
+    if (rc != SYN_OK) return rc;
+    auto& L = h->learner;
+    const NetDesc& d = g_net_desc[L.trainer_kind];
+    if (!blob || !m || !v) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_trainer_set_state: blob/m/v is NULL");
+    if (n_floats != (size_t)d.num_params)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "the trainer's %s has %d parameters, got %zu", d.name, d.num_params, n_floats);
+    if (step < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_trainer_set_state: step is negative (%lld)", step);
+    HIP_TRY(h, hipSetDevice(h->device));
+    std::vector<float> img, timg;
+    if (L.trainer_kind == 0) {
+        rc = build_trainer_images(h, blob, img, timg);
+        if (rc != SYN_OK) return rc;
+        HIP_TRY(h, hipMemcpyAsync(L.d_twimg, img.data(), img.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(L.d_ttimg, timg.data(), timg.size() * 4, hipMemcpyHostToDevice, h->stream));
+        // (the epoch kernel copies both into its second buffer before every launch; it is set here all the same, so that no image of
+        //  the trainer describes another network)
+        HIP_TRY(h, hipMemcpyAsync(L.d_timg2, img.data(), img.size() * 4, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(L.d_timg2 + MlpGeom::IMG_FLOATS, timg.data(), timg.size() * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(L.d_tw, blob, d.param_bytes(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(L.d_tm, m, d.param_bytes(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(L.d_tv, v, d.param_bytes(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    L.train_step = step;
     return SYN_OK;
 }
 
@@ -4169,6 +4209,105 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
     m.v_hits = t.v_hits;
     m.grid = grid;
     if (out) *out = m;
+    return SYN_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ state digests
+// syn_state_digest (include/synthesis_amd.h "State digests"; kernels in digest_kernels.cuh). The component's arrays become the
+// sections of one launch; words that live on the host (the trainer's step count) enter as their h_i sum. An observer: it reads the
+// state and writes the scratch only.
+int syn_state_digest(syn_engine* h, int what, int max_workgroups, uint64_t* digest, uint64_t* n_words) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (what < SYN_DIGEST_TRAINER || what > SYN_DIGEST_EVAL_DATA) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown digest component %d", what);
+    if (max_workgroups < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "max_workgroups is negative (%d); 0 lets the library choose", max_workgroups);
+    auto& L = h->learner;
+    if (what == SYN_DIGEST_TRAINER && !L.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "call syn_trainer_init first");
+    if (what == SYN_DIGEST_NETWORK) {
+        const int rc = require_weights(h);
+        if (rc != SYN_OK) return rc;
+    }
+    const uint64_t tag = DIGEST_TAG + (uint64_t)what;
+    DigestArgs A{};
+    A.tag = tag;
+    uint64_t total = 0, host_sum = 0;
+    const auto add = [&](const void* p, uint64_t words) {
+        A.sec[A.n_sections++] = DigestSection{static_cast<const uint32_t*>(p), words, total};
+        total += words;
+    };
+    if (what == SYN_DIGEST_TRAINER) {
+        const uint64_t P = (uint64_t)g_net_desc[L.trainer_kind].num_params;
+        add(L.d_tw, P);
+        add(L.d_tm, P);
+        add(L.d_tv, P);
+        const uint64_t step = (uint64_t)L.train_step;
+        host_sum = digest_word(tag, total, (uint32_t)step) + digest_word(tag, total + 1, (uint32_t)(step >> 32));
+        total += 2;
+    } else if (what == SYN_DIGEST_NETWORK) {
+        // the parameters are on the host (Network::host_blob: what every image of the network was built from)
+        const auto& blob = h->net.host_blob;
+        for (size_t i = 0; i < blob.size(); i++) {
+            uint32_t w;
+            std::memcpy(&w, &blob[i], 4);
+            host_sum += digest_word(tag, (uint64_t)i, w);
+        }
+        total = blob.size();
+    } else if (what == SYN_DIGEST_REPLAY) {
+        const uint64_t n = h->d_replay ? h->replay_n : 0;
+        if (n) {
+            const ReplaySections s = replay_sections(h->d_replay, h->replay_cap);
+            add(s.my, 2 * n);
+            add(s.op, 2 * n);
+            add(s.gid, 2 * n);
+            add(s.pi, 9 * n);
+            add(s.v, 3 * n);
+        }
+    } else {
+        const bool train = what == SYN_DIGEST_TRAIN_DATA;
+        void* base = train ? L.d_train_data : h->evalset.d_data;
+        const uint64_t n = base ? (train ? L.train_data_n : h->evalset.n) : 0;
+        if (n) {
+            const TrainSections s = train_sections(base, n);
+            add(s.my, 2 * n);
+            add(s.op, 2 * n);
+            add(s.pi, 9 * n);
+            add(s.v, 3 * n);
+        }
+    }
+    h->last_kernel_ms = 0.0f;
+    h->last_launches = 0;
+    if (n_words) *n_words = total;
+    if (A.n_sections == 0) {
+        if (digest) *digest = digest_close(tag, host_sum, total);
+        return SYN_OK;
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the library's choice: every lane takes 16-byte groups, eight resident workgroups of 256 threads per CU when the state is large
+    uint64_t groups = 0;
+    for (int s = 0; s < A.n_sections; s++) groups += (A.sec[s].words + 3) / 4;
+    const uint64_t want = (groups + DIGEST_THREADS - 1) / DIGEST_THREADS;
+    const uint64_t cap = max_workgroups > 0 ? (uint64_t)max_workgroups : (uint64_t)h->num_cus * 8;
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min(want, cap));
+    Carve c;
+    const size_t o_part = c.take((size_t)grid * 8), o_out = c.take(16);
+    const int rc = ensure_scratch(h, c.at + 256);
+    if (rc != SYN_OK) return rc;
+    char* sc = static_cast<char*>(h->d_scratch);
+    unsigned long long* d_part = reinterpret_cast<unsigned long long*>(sc + o_part);
+    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(sc + o_out);
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(digest_sections_kernel, dim3(grid), dim3(DIGEST_THREADS), 0, h->stream, A, d_part);
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(digest_finish_kernel, dim3(1), dim3(DIGEST_THREADS), 0, h->stream, d_part, (int)grid, (unsigned long long)host_sum,
+                       (unsigned long long)tag, (unsigned long long)total, d_out);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    unsigned long long out[2] = {0ull, 0ull};
+    HIP_TRY(h, hipMemcpyAsync(out, d_out, 16, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipEventElapsedTime(&h->last_kernel_ms, h->ev0, h->ev1));
+    h->last_launches = 2;
+    if (out[1] != total) return fail(h, SYN_ERR_HIP, "internal: the digest kernel closed %llu words of %llu", out[1], (unsigned long long)total);
+    if (digest) *digest = out[0];
     return SYN_OK;
 }
 

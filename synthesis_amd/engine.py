@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "syn_train_epochs_sampled", "syn_debug_sampler",
     "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_replay_set_holdout", "syn_dataset_counts",
     "syn_replay_reanalyse",
+    "syn_trainer_set_state", "syn_state_digest",
 ]
 TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
@@ -252,7 +253,9 @@ def load_library():
                            ("syn_replay_set_holdout", [C.c_void_p, C.c_uint64, C.c_uint64]),
                            ("syn_dataset_counts", [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
                            ("syn_replay_reanalyse", [C.c_void_p, C.POINTER(CMctsConfig), C.POINTER(CReanalyseConfig),
-                                                     C.POINTER(CReanalyseStats), C.c_void_p, C.c_size_t])):
+                                                     C.POINTER(CReanalyseStats), C.c_void_p, C.c_size_t]),
+                           ("syn_trainer_set_state", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_longlong]),
+                           ("syn_state_digest", [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])):
         if hasattr(lib, name) or not os.environ.get("SYNTHESIS_AMD_LIB"):
             getattr(lib, name).argtypes = argtypes
     _lib = lib
@@ -829,6 +832,33 @@ class Engine:
         step = C.c_longlong()
         self._check(self._lib.syn_trainer_get_state(self._h, _p(blob), _p(m), _p(v), C.byref(step), _p(g)))
         return dict(weights=blob, m=m, v=v, step=int(step.value), grads=g)
+
+    def trainer_set_state(self, weights, m, v, step):
+        """syn_trainer_set_state: the inverse of trainer_state — parameters, both Adam moments and the step count of an initialised
+        trainer of the same network, bit for bit, with every derived device image rebuilt. Modes, hyper-parameters, data sets, the last
+        gradient and the engine's network stay as they are; nothing is published."""
+        arrays = [np.ascontiguousarray(a, dtype=np.float32).ravel() for a in (weights, m, v)]
+        if len({a.size for a in arrays}) != 1:
+            raise ValueError("weights, m and v must have the same size, got " + ", ".join(str(a.size) for a in arrays))
+        self._check(self._lib.syn_trainer_set_state(self._h, _p(arrays[0]), _p(arrays[1]), _p(arrays[2]), int(arrays[0].size), int(step)))
+
+    def state_digest(self, what, max_workgroups=0):
+        """syn_state_digest: the 64-bit fingerprint (an int) of one piece of engine state, computed where it lives — `what` is
+        "trainer" (w, m, v, step), "network" (the installed network's parameters), "replay" (the device replay buffer), "train_data" or
+        "eval_data" (include/synthesis_amd.h "State digests"; synthesis_amd/digest.py is the same definition in numpy). The word does
+        not depend on max_workgroups (0 = the library's grid)."""
+        return self.state_digest_words(what, max_workgroups)[0]
+
+    def state_digest_words(self, what, max_workgroups=0):
+        """(digest, number of 32-bit words digested)"""
+        from .digest import COMPONENTS
+        if isinstance(what, str):   # (a number goes to the library as it is, which refuses the ones it does not know)
+            if what not in COMPONENTS:
+                raise ValueError(f"what must be one of {sorted(COMPONENTS)}, got {what!r}")
+            what = COMPONENTS[what]
+        d, n = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.syn_state_digest(self._h, int(what), int(max_workgroups), C.byref(d), C.byref(n)))
+        return int(d.value), int(n.value)
 
     def train_set_data(self, my_bb, op_bb, target_pi, target_v):
         """Uploads the de-duplicated buffer once; train_epoch then indexes it on the device."""

@@ -122,6 +122,135 @@ def reanalyse_flags(key, threshold, before_gid, gid, my, op):
 _METRIC_KEYS = ("rows", "mean_pi", "mean_v", "pi_acc", "v_acc")
 
 
+# ---- the state file of a LearningLoop (LearningLoop.save_state / restore_state): ONE .npz written by numpy alone, no pickling. Needs no GPU.
+STATE_FORMAT_VERSION = 1
+# what identifies a run: a loop continues a state file only when all of these agree (`replay` is deliberately not among them: the
+# buffer is stored as arrays, so a run saved with replay="host" may continue with replay="device" and the reverse)
+FINGERPRINT_FIELDS = ("net", "seed", "precision", "batch_mode", "sampler", "flip", "symmetry", "holdout", "reanalyse",
+                      "reanalyse_explores", "reanalyse_value_mix", "lr_schedule", "hyper", "network_arithmetic", "world")
+_HYPER_DEFAULTS = dict(weight_decay=1e-6, policy_weight=1.0, value_weight=1.0, beta1=0.9, beta2=0.999, eps=1e-8)   # Engine.trainer_init*
+# every array of the file: name -> (dtype, trailing shape); `torch_generator` is present only with sampler="torch"
+_STATE_ARRAYS = dict(format_version=(np.int64, ()), fingerprint=(np.uint8, (-1,)), iterations_done=(np.int64, ()), games_played=(np.int64, ()),
+                     weights=(np.float32, (-1,)), m=(np.float32, (-1,)), v=(np.float32, (-1,)), step=(np.int64, ()),
+                     replay_my=(np.uint64, (-1,)), replay_op=(np.uint64, (-1,)), replay_gid=(np.int64, (-1,)),
+                     replay_pi=(np.float32, (-1, 9)), replay_v=(np.float32, (-1, 3)),
+                     digest_trainer=(np.uint64, ()), digest_replay=(np.uint64, ()))
+_STATE_OPTIONAL = dict(torch_generator=(np.uint8, (-1,)))
+_REPLAY_KEYS = ("my", "op", "gid", "pi", "v")
+
+
+def _normal_fingerprint(fp):
+    """`fp` as it comes back from the file: through JSON (tuples become lists, numpy scalars plain numbers), every field present"""
+    import json
+
+    missing = [k for k in FINGERPRINT_FIELDS if k not in fp]
+    if missing:
+        raise ValueError(f"a run's fingerprint needs the fields {list(FINGERPRINT_FIELDS)}; missing: {missing}")
+    plain = lambda x: x.item() if isinstance(x, np.generic) else x
+    return json.loads(json.dumps({k: fp[k] for k in FINGERPRINT_FIELDS}, default=plain, sort_keys=True))
+
+
+def pack_state(state):
+    """A loop's state as the dict of arrays np.savez writes. `state` has `fingerprint` (a dict with FINGERPRINT_FIELDS),
+    `iterations_done`, `games_played`, `weights`, `m`, `v`, `step`, `replay` (dict my, op, gid, pi, v), `digest_trainer`,
+    `digest_replay` (ints below 2^64) and optionally `torch_generator` (the generator's state bytes)."""
+    import json
+
+    fp = json.dumps(_normal_fingerprint(state["fingerprint"]), sort_keys=True).encode("utf-8")
+    R = state["replay"]
+    out = dict(format_version=np.int64(STATE_FORMAT_VERSION), fingerprint=np.frombuffer(fp, np.uint8).copy(),
+               iterations_done=np.int64(state["iterations_done"]), games_played=np.int64(state["games_played"]),
+               weights=state["weights"], m=state["m"], v=state["v"], step=np.int64(state["step"]),
+               replay_my=R["my"], replay_op=R["op"], replay_gid=R["gid"], replay_pi=R["pi"], replay_v=R["v"],
+               digest_trainer=np.uint64(int(state["digest_trainer"])), digest_replay=np.uint64(int(state["digest_replay"])))
+    if state.get("torch_generator") is not None:
+        out["torch_generator"] = state["torch_generator"]
+    spec = dict(_STATE_ARRAYS, **_STATE_OPTIONAL)
+    out = {k: np.ascontiguousarray(a, dtype=spec[k][0]).reshape(spec[k][1]) for k, a in out.items()}
+    sizes = {k: out[k].shape[0] for k in ("weights", "m", "v")}
+    if len(set(sizes.values())) != 1:
+        raise ValueError(f"weights, m and v must have the same size, got {sizes}")
+    rows = {k: out["replay_" + k].shape[0] for k in _REPLAY_KEYS}
+    if len(set(rows.values())) != 1:
+        raise ValueError(f"the buffer's five arrays must have the same number of rows, got {rows}")
+    return out
+
+
+def unpack_state(arrays, where="state file"):
+    """The inverse of pack_state on what np.load returned (any mapping of arrays). Raises ValueError, naming `where`, on a foreign
+    format version, a missing array, or an array of the wrong type or shape."""
+    import json
+
+    if "format_version" not in arrays:
+        raise ValueError(f"{where}: not a LearningLoop state file (no format_version)")
+    version = int(np.asarray(arrays["format_version"]).reshape(-1)[0])
+    if version != STATE_FORMAT_VERSION:
+        raise ValueError(f"{where}: state file format version {version}; this library reads version {STATE_FORMAT_VERSION}")
+    got = {}
+    for k, (dt, shape) in list(_STATE_ARRAYS.items()) + list(_STATE_OPTIONAL.items()):
+        if k not in arrays:
+            if k in _STATE_OPTIONAL:
+                continue
+            raise ValueError(f"{where}: the array {k!r} is missing")
+        a = np.asarray(arrays[k])
+        if a.dtype != np.dtype(dt) or a.ndim != len(shape) or any(s >= 0 and s != d for s, d in zip(shape, a.shape)):
+            raise ValueError(f"{where}: the array {k!r} is {a.dtype}{list(a.shape)}, expected {np.dtype(dt)}{list(shape)}")
+        got[k] = a
+    if len({got[k].shape[0] for k in ("weights", "m", "v")}) != 1 or len({got["replay_" + k].shape[0] for k in _REPLAY_KEYS}) != 1:
+        raise ValueError(f"{where}: the trainer's or the buffer's arrays differ in length")
+    try:
+        fingerprint = _normal_fingerprint(json.loads(got["fingerprint"].tobytes().decode("utf-8")))
+    except (UnicodeDecodeError, json.JSONDecodeError, TypeError) as e:
+        raise ValueError(f"{where}: the run's fingerprint cannot be read ({e})") from None
+    return dict(fingerprint=fingerprint, iterations_done=int(got["iterations_done"]), games_played=int(got["games_played"]),
+                weights=got["weights"], m=got["m"], v=got["v"], step=int(got["step"]),
+                replay={k: got["replay_" + k] for k in _REPLAY_KEYS},
+                torch_generator=got.get("torch_generator"), digest_trainer=int(got["digest_trainer"]), digest_replay=int(got["digest_replay"]))
+
+
+def write_state_file(path, state):
+    """pack_state(state) into `path`: written under a temporary name in the same directory, then os.replace — a reader sees the old
+    file or the new one, and a failure leaves no partial file behind."""
+    import os
+    import tempfile
+
+    arrays = pack_state(state)
+    directory = os.path.dirname(os.path.abspath(path))
+    fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=directory)
+    try:
+        with os.fdopen(fd, "wb") as f:
+            np.savez(f, **arrays)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
+def read_state_file(path):
+    """unpack_state of the file at `path`. A file that is truncated or not an .npz raises ValueError; nothing is written."""
+    import zipfile
+
+    try:
+        with np.load(path, allow_pickle=False) as z:
+            arrays = {k: z[k] for k in z.files}
+    except (zipfile.BadZipFile, EOFError, OSError, ValueError, KeyError) as e:
+        if isinstance(e, FileNotFoundError):
+            raise
+        raise ValueError(f"{path}: not a complete LearningLoop state file ({type(e).__name__}: {e})") from None
+    return unpack_state(arrays, where=str(path))
+
+
+def check_fingerprint(saved, current, where="state file"):
+    """Raises ValueError naming the first field of FINGERPRINT_FIELDS in which the run that wrote the file and this loop differ."""
+    saved, current = _normal_fingerprint(saved), _normal_fingerprint(current)
+    for k in FINGERPRINT_FIELDS:
+        if saved[k] != current[k]:
+            raise ValueError(f"{where}: written by a run with {k}={saved[k]!r}, this loop has {k}={current[k]!r}")
+
+
 class LearningLoop:
     """alpha_zero.rs:16-118 with self-play on every rank and the learner on rank 0 (see the module docstring).
 
@@ -173,6 +302,22 @@ class LearningLoop:
                  selected rows + assignment into the host buffer — same bits. The record gains `reanalysed`, `reanalyse_moved` (rows whose
                  arg-max column of pi changed) and a `reanalyse` phase time. Not measured: any training run with reanalysis, and more than
                  one rank (the other ranks idle during the learner's reanalysis).
+    digests      False (default: every record as without the argument) | True: the learner's record gains `digests` = dict(trainer,
+                 replay, train_data, and with a holdout eval_data) — the 64-bit fingerprints of that state (Engine.state_digest;
+                 include/synthesis_amd.h "State digests") as 16-digit hex strings, taken after the iteration's epochs and before the
+                 publish. They are computed where the state lives; replay="host" digests its numpy buffer with synthesis_amd.digest, the
+                 same definition, so both replay modes report the same words. Two runs whose logs show the same words hold the same
+                 bits — one rank against two, host replay against device replay, a resumed run against one that never stopped.
+    save_state(path) / restore_state(path): the run can stop and continue. save_state writes ONE .npz (numpy alone, a temporary name then
+                 os.replace; only the learner's rank writes): a format version, the run's fingerprint (FINGERPRINT_FIELDS: net, seed,
+                 precision, batch_mode, sampler, flip, symmetry, holdout, reanalyse and its two parameters, lr_schedule, the hyper values,
+                 network_arithmetic, world size), iterations_done and games_played, the trainer's weights, m, v and step, the buffer's five
+                 arrays, the torch generator's state (sampler="torch") and the TRAINER and REPLAY digests. restore_state, on a freshly
+                 constructed loop with the same arguments (`replay` may differ), refuses a file of another run by naming the field, puts
+                 the trainer (Engine.trainer_set_state), the buffer, the network and the counters back, and proves it by recomputing both
+                 digests; the iterations that follow are bit for bit those of a run that never stopped. Not saved: the policy cache
+                 (results never depend on it), the last gradient (every step overwrites it) and the two data sets (every iteration
+                 rebuilds them from the buffer). Not measured: any training run continued across sessions.
     logs_dir     None, or where the learner's rank writes what the reference writes per iteration (alpha_zero.rs:37,97-100):
                  models/model_{i}.ot (Connect4Net: a VarStore archive `vs.load` reads; Connect4ConvNet: the flat blob as .npy) and
                  latest_states.npy [n, 1, 7, 9] / latest_pis.npy [n, 9] / latest_vs.npy [n, 3] of the de-duplicated buffer
@@ -180,7 +325,7 @@ class LearningLoop:
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
                  network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0,
-                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, **hyper):
+                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, digests=False, **hyper):
         _real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
         if not _real(reanalyse) or not 0.0 <= float(reanalyse) <= 1.0:
             raise ValueError(f"reanalyse must be a fraction of rows in [0, 1], got {reanalyse!r}")
@@ -232,6 +377,10 @@ class LearningLoop:
         self.games_played = 0
         self.iterations_done = 0
         self.batch_mode = batch_mode
+        self.precision = precision
+        self.network_arithmetic = network_arithmetic
+        self.hyper = dict(_HYPER_DEFAULTS, **hyper)
+        self.digests = bool(digests)
         self.replay = replay
         self.symmetry = symmetry
         self._device = int(device)
@@ -262,6 +411,133 @@ class LearningLoop:
             save_ot(self.weights, os.path.join(d, f"model_{i}.ot"))
         else:
             np.save(os.path.join(d, f"model_{i}.npy"), self.weights)
+
+    # ---- stopping and continuing a run (save_state / restore_state) and the per-iteration fingerprints (digests=True)
+    def fingerprint(self):
+        """What identifies this run (FINGERPRINT_FIELDS): restore_state continues a file only when every field agrees"""
+        return dict(net=self.net, seed=self.seed, precision=self.precision, batch_mode=self.batch_mode, sampler=self.sampler, flip=self.flip,
+                    symmetry=self.symmetry, holdout=self.holdout, reanalyse=self.reanalyse, reanalyse_explores=self.reanalyse_explores,
+                    reanalyse_value_mix=self.reanalyse_value_mix, lr_schedule=[[int(i), float(v)] for i, v in self.lr_schedule],
+                    hyper={k: float(v) for k, v in sorted(self.hyper.items())}, network_arithmetic=self.network_arithmetic, world=self.world)
+
+    def _replay_arrays(self):
+        """The learner's rank: the buffer's five arrays (my, op, gid, pi, v), from the engine (replay="device") or from self.R"""
+        if self.replay == "device":
+            return self.engine.replay_read()
+        return {k: self.R[k] for k in _REPLAY_KEYS}
+
+    def _replay_put(self, R):
+        """The learner's rank: `R` becomes the buffer — Engine.replay_reserve + replay_append (replay="device") or self.R"""
+        n = int(np.asarray(R["my"]).size)
+        if self.replay == "device":
+            self.engine.replay_clear()
+            if n > self._replay_reserved:
+                self.engine.replay_reserve(n)
+                self._replay_reserved = n
+            if n:
+                self.engine.replay_append(R["my"], R["op"], R["gid"], R["pi"], R["v"])
+        else:
+            self.R = dict(my=np.array(R["my"], np.uint64).reshape(-1), op=np.array(R["op"], np.uint64).reshape(-1),
+                          pi=np.array(R["pi"], np.float32).reshape(-1, 9), v=np.array(R["v"], np.float32).reshape(-1, 3),
+                          gid=np.array(R["gid"], np.int64).reshape(-1))
+
+    def _replay_digest(self):
+        """SYN_DIGEST_REPLAY of the buffer where it lives: on the device (replay="device"), with synthesis_amd.digest over self.R otherwise"""
+        if self.replay == "device":
+            return self.engine.state_digest("replay")
+        from .digest import replay_digest
+
+        return replay_digest(*(self.R[k] for k in _REPLAY_KEYS))
+
+    def state_digests(self):
+        """The learner's rank: the fingerprints of the run's device-resident state as 16-digit hex strings — trainer (w, m, v, step),
+        replay (the buffer; both replay modes report the same word), train_data, and eval_data with a holdout (include/synthesis_amd.h
+        "State digests")."""
+        from .digest import hex16
+
+        out = dict(trainer=hex16(self.engine.state_digest("trainer")), replay=hex16(self._replay_digest()),
+                   train_data=hex16(self.engine.state_digest("train_data")))
+        if self._holdout_threshold:
+            out["eval_data"] = hex16(self.engine.state_digest("eval_data"))
+        return out
+
+    def save_state(self, path):
+        """Writes everything the loop carries from one iteration to the next into ONE .npz at `path` (write_state_file: a temporary
+        name in the same directory, then os.replace): the run's fingerprint, iterations_done and games_played, the trainer's weights,
+        moments and step, the buffer's five arrays, the torch generator's state (sampler="torch") and the TRAINER and REPLAY digests at
+        save time. Only the learner's rank writes; the other ranks return at once. Not saved: the policy cache, the last gradient and
+        the two data sets (every iteration rebuilds them from the buffer)."""
+        if self.rank != 0:
+            return
+        T = self.engine.trainer_state()
+        state = dict(fingerprint=self.fingerprint(), iterations_done=self.iterations_done, games_played=self.games_played,
+                     weights=T["weights"], m=T["m"], v=T["v"], step=T["step"], replay=self._replay_arrays(),
+                     digest_trainer=self.engine.state_digest("trainer"), digest_replay=self._replay_digest(),
+                     torch_generator=self._torch_gen.get_state().numpy() if self._torch_gen is not None else None)
+        write_state_file(path, state)
+
+    def _restore_learner(self, path):
+        """restore_state on the learner's rank. Returns the file's state."""
+        S = read_state_file(path)
+        check_fingerprint(S["fingerprint"], self.fingerprint(), where=str(path))   # 1: before anything changes
+        if S["weights"].size != self.n_params:
+            raise ValueError(f"{path}: {S['weights'].size} parameters, net={self.net!r} has {self.n_params}")
+        if (S["torch_generator"] is not None) != (self._torch_gen is not None):
+            raise ValueError(f"{path}: the torch generator's state is {'missing' if self._torch_gen is not None else 'unexpected'}")
+        old_T, old_R, old_w = self.engine.trainer_state(), self._replay_arrays(), self.weights
+        self.engine.trainer_set_state(S["weights"], S["m"], S["v"], S["step"])               # 2
+        self._replay_put(S["replay"])                                                         # 3
+        if self._holdout_threshold and self.replay == "device":                               # 4
+            self.engine.replay_set_holdout(_holdout_key(self.seed), self._holdout_threshold)
+        self._load(S["weights"])                                                              # 5: in the engine's arithmetic
+        got = dict(trainer=self.engine.state_digest("trainer"), replay=self._replay_digest())   # 7 (the counters, 6, follow a passed check)
+        want = dict(trainer=S["digest_trainer"], replay=S["digest_replay"])
+        bad = [k for k in got if got[k] != want[k]]
+        if bad:
+            self.engine.trainer_set_state(old_T["weights"], old_T["m"], old_T["v"], old_T["step"])
+            self._replay_put(old_R)
+            self._load(old_w)
+            raise ValueError(f"{path}: the restored state does not have the file's digest: " +
+                             ", ".join(f"{k} {got[k]:016x} != {want[k]:016x}" for k in bad) + " (the file was changed after it was written)")
+        self.weights = np.array(S["weights"], np.float32)
+        if self._torch_gen is not None:
+            self._torch_gen.set_state(self._torch.from_numpy(np.array(S["torch_generator"], np.uint8)))
+        return S
+
+    def restore_state(self, path):
+        """Continues the run that save_state wrote to `path`, on a freshly constructed loop (same engine rules as the constructor). In
+        order: the file's fingerprint is checked against this loop's — a mismatch raises ValueError naming the field before anything
+        changes (`replay` is not part of it: a run saved under "host" may continue under "device" and the reverse); the trainer is set
+        (Engine.trainer_set_state); the buffer is put back; the holdout key is applied again; the weights become the engine's network in
+        the engine's arithmetic; the counters and the generator are set; and the TRAINER and REPLAY digests are computed again where the
+        state lives and compared with the file's — a difference raises ValueError with the engine's trainer, buffer and network as they
+        were before the call. With several ranks the learner's rank restores, the weights reach the others through the loop's
+        broadcast, and the others set only their counters. The iterations that follow leave the bits of a run that never stopped."""
+        t = self._torch
+        S, err = None, None
+        if self.rank == 0:
+            try:
+                S = self._restore_learner(path)
+            except Exception as e:   # (with several ranks the others must hear of it before anybody raises)
+                if self.dist is None:
+                    raise
+                err = e
+        if self.dist is not None:
+            head = t.tensor([0 if S is None else 1, S["iterations_done"] if S else 0, S["games_played"] if S else 0], dtype=t.int64,
+                            device=self._wbuf.device)
+            self.dist.broadcast(head, src=0)
+            ok, iterations_done, games_played = (int(x) for x in head.tolist())
+            if not ok:
+                raise err if err is not None else ValueError(f"{path}: the learner's rank refused the state file")
+            if self.rank == 0:
+                self._wbuf.copy_(t.from_numpy(self.weights))
+            self.dist.broadcast(self._wbuf, src=0)
+            if self.rank != 0:
+                self.weights = self._wbuf.cpu().numpy().copy()
+                self._load(self.weights)
+        else:
+            iterations_done, games_played = S["iterations_done"], S["games_played"]
+        self.iterations_done, self.games_played = iterations_done, games_played
 
     # one replay position on the wire: my_bb, op_bb (u64), gid (i64), pi[9], v[3] (f32) = 72 bytes, no pickling. A rank's buffer is
     # five contiguous sections [my | op | gid | pi | v] of `cap` positions each (five block copies to pack, views to unpack).
@@ -427,6 +703,8 @@ class LearningLoop:
                 rec["unique_canonical"] = n_canonical
             if self._reanalyse_threshold:
                 rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
+            if self.digests:
+                rec["digests"] = self.state_digests()
             if self.logs_dir:
                 import os
 
@@ -597,6 +875,8 @@ class LearningLoop:
                 rec["unique_canonical"] = D["canonical"]
             if self._reanalyse_threshold:
                 rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
+            if self.digests:
+                rec["digests"] = self.state_digests()
             if self.logs_dir:   # alpha_zero.rs:97-100
                 import os
 
