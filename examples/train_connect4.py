@@ -88,6 +88,8 @@ def main():
     ap.add_argument("--holdout", type=float, default=0.0, help="fraction of GAMES kept away from the learner: their positions become the "
                     "engine's evaluation set and every iteration's record gains the held-out losses and accuracies of the weights before "
                     "and after its epochs, on all held-out rows and on the unseen ones (0 = off; learning loop only)")
+    ap.add_argument("--holdout-arith", default="f32", help="--holdout: comma-separated arithmetics the held-out metrics are taken in (f32, "
+                    "f16x2, and bf16 for --net conv); each extra name adds holdout_before_<name> / holdout_after_<name> to the records")
     ap.add_argument("--reanalyse", type=float, default=0.0, help="fraction of the stored positions of OLDER games that every iteration "
                     "searches again with the current network before it trains; their pi targets are overwritten (0 = off; learning "
                     "loop only; whether it trains a stronger player is not measured)")
@@ -167,7 +169,7 @@ def main():
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
                             batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, reanalyse=args.reanalyse,
                             reanalyse_explores=args.reanalyse_explores, reanalyse_value_mix=args.reanalyse_value_mix, digests=args.digests,
-                            **hyper)
+                            holdout_arith=tuple(a for a in args.holdout_arith.split(",") if a), **hyper)
         if args.resume:
             loop.restore_state(args.resume)
     log = []

@@ -714,8 +714,31 @@ int syn_replay_deduplicate_to_trainer_symmetric(syn_engine* h, size_t* n_canonic
  * Refused, with everything unchanged: an unknown `which`, a negative max_workgroups, no data set (`which` is empty or was never set), a
  * row range outside the set, a blob whose n_floats is neither network's (all SYN_ERR_INVALID_ARGUMENT); blob == NULL before
  * syn_trainer_init* (SYN_ERR_NO_WEIGHTS).
- * Out of scope: evaluation in the f16x2 arithmetic or in the conv learner's bf16 precision. A conv trainer in SYN_TRAIN_BF16 is
- * evaluated in f32 like any other parameters. */
+ *
+ * syn_dataset_evaluate_arith is the same call in any arithmetic the library computes a forward pass in; syn_dataset_evaluate is this call
+ * with SYN_EVAL_ARITH_F32, and everything above is its definition. Blocks, rows_j, the hit rules, the totals, the outputs, the grid
+ * independence and the observer property are shared by all three arithmetics; only the arithmetic that produces the twelve RAW OUTPUTS of
+ * a row (what row_logits returns) changes:
+ *   SYN_EVAL_ARITH_F16X2  (both networks) the twelve raw outputs of row i are bit for bit what the engine's f16x2 inference ("Network
+ *                         arithmetic" above; syn_policy_eval_batch_device's nine logits and the three numbers its value softmax reads)
+ *                         computes for that position with these parameters. The f16x2 image is built per call on the host, from the
+ *                         blob or (blob == NULL) from a copy of the trainer's current weights, into a buffer the call owns: the engine's
+ *                         own network, arithmetic, f16x2 image, host blob and policy cache are neither read nor written, and the result
+ *                         is the same on an engine in f32 and on one in f16x2. Parameters without an f16x2 plan (non-finite values,
+ *                         scales outside the window, a bias that does not fit: syn_f16x2_plan_of_blob reports valid = 0) are refused
+ *                         with SYN_ERR_UNSUPPORTED and nothing changes.
+ *   SYN_EVAL_ARITH_BF16   (Connect4ConvNet only; Connect4Net: SYN_ERR_UNSUPPORTED, as syn_trainer_set_precision) the forward of the conv
+ *                         learner in SYN_TRAIN_BF16: the same operands rounded to bf16, the same v_mfma_f32_16x16x16_bf16 chains.
+ *                         pi_loss_j and v_loss_j are bit for bit the two losses syn_train_gradients_device reports in SYN_TRAIN_BF16,
+ *                         chained mode, for the block's rows as a minibatch of rows_j. The trainer's own precision setting is neither
+ *                         read nor changed: a trainer in SYN_TRAIN_F32 can be evaluated in bf16 and the reverse.
+ * The head is the f32 learner's in every arithmetic, applied to the raw outputs x_0..x_8 (policy) and x_9..x_11 (value) with the targets
+ * t_k, all in f32: mx = the first maximum; se = det_expf(x_k - mx) summed ascending from 0.0f; lse = mx + det_logf(se); kl = the
+ * ascending sum from 0.0f of t_k * (det_logf(t_k) - (x_k - lse)) over the k with t_k > 0; loss_j = bm * (kl_0 + kl_1 + ...) in row order
+ * with bm = 1.0f / rows_j; row_kl[i] = the row as a minibatch of one. The hits are computed from the same raw outputs.
+ * Further refusals: an arithmetic other than the three is SYN_ERR_INVALID_ARGUMENT. n_rows = 0 is SYN_OK with an all-zero *out in every
+ * arithmetic: no image is built and no plan is asked for. syn_last_timing reports the call's two launches; the host's image build of
+ * the f16x2 arithmetic is outside that time. */
 typedef struct syn_dataset_metrics {
     double mean_pi, mean_v;    /* sum_pi / rows, sum_v / rows (0 when rows = 0) */
     double sum_pi, sum_v;      /* the two f64 sums defined above */
@@ -728,6 +751,9 @@ int syn_dataset_set(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb,
 int syn_dataset_get(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity, size_t* n);
 int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int max_workgroups,
                          syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl);
+enum { SYN_EVAL_ARITH_F32 = 0, SYN_EVAL_ARITH_F16X2 = 1, SYN_EVAL_ARITH_BF16 = 2 };
+int syn_dataset_evaluate_arith(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int arithmetic,
+                               int max_workgroups, syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl);
 
 /* ---- Holding games out (opt-in; csrc/replay_kernels.cuh). syn_replay_set_holdout sets a key and a threshold (at most 2^32, else
  * SYN_ERR_INVALID_ARGUMENT); with sm as in "Device-side epoch sampler" above and all arithmetic unsigned 64-bit, game gid (its 64-bit

@@ -373,3 +373,61 @@ def host_match(engine, first, second, start_my, start_op):
         if own is not None:
             engine.set_network_arithmetic(own)
     return out
+
+
+# ---- agreement of two evaluations of one data set ---------------------------------------------------------------------------------------
+def _first_argmax(x, allowed):
+    """[n]: per row the first maximum of x [n][k] over the entries with allowed [n][k] (a later entry wins only when it compares greater);
+    k for a row without an allowed entry"""
+    n, k = x.shape
+    best = np.full(n, k, np.int64)
+    bv = np.zeros(n, np.float64)
+    for c in range(k):
+        take = allowed[:, c] & ((best == k) | (x[:, c] > bv))
+        best = np.where(take, c, best)
+        bv = np.where(take, x[:, c], bv)
+    return best
+
+
+def _masked_kl(a, b, allowed):
+    """[n]: KL(softmax(a) || softmax(b)) with both softmaxes taken over the allowed entries only, in f64; 0 for a row without one"""
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        def logp(x):
+            x = np.where(allowed, x, -np.inf)
+            mx = np.max(x, axis=1, keepdims=True)
+            mx = np.where(np.isfinite(mx), mx, 0.0)
+            z = x - mx
+            return z - np.log(np.sum(np.where(allowed, np.exp(z), 0.0), axis=1, keepdims=True))
+        la, lb = logp(a), logp(b)
+        term = np.where(allowed, np.exp(la) * (la - lb), 0.0)
+    return np.sum(np.where(np.isfinite(term), term, 0.0), axis=1)
+
+
+def dataset_agreement(rows_a, rows_b, my_bb, op_bb):
+    """How far two evaluations of the same rows are apart: rows_a, rows_b = two `row_logits` arrays [n][12] of Engine.dataset_evaluate
+    (say, arith="f32" and arith="f16x2") for the positions (my_bb, op_bb). Host code in f64 on downloaded rows. Returns a dict:
+      rows               n
+      max_abs_diff       max |a - b| over all twelve raw outputs;  mean_abs_diff: their mean
+      pi_argmax_differs  the share of rows whose arg-max of the nine policy outputs over the LEGAL columns (top cell, bit 6 + 7 c of
+                         my | op, free) differs; the first maximum wins, as in syn_dataset_evaluate's hits; a full column never counts
+      v_argmax_differs   the same for the three value outputs
+      mean_kl_pi         mean over rows of KL(softmax_a || softmax_b), both over the legal columns;  mean_kl_v: over the value triple
+    A description of two arithmetics on one data set, not a statement about playing strength."""
+    a = np.asarray(rows_a, np.float32).reshape(-1, 12).astype(np.float64)
+    b = np.asarray(rows_b, np.float32).reshape(-1, 12).astype(np.float64)
+    n = a.shape[0]
+    if b.shape[0] != n:
+        raise ValueError("rows_a and rows_b must have the same number of rows")
+    occ = np.asarray(my_bb, np.uint64).ravel() | np.asarray(op_bb, np.uint64).ravel()
+    if occ.size != n:
+        raise ValueError("my_bb / op_bb must have one entry per row")
+    if n == 0:
+        return dict(rows=0, max_abs_diff=0.0, mean_abs_diff=0.0, pi_argmax_differs=0.0, v_argmax_differs=0.0, mean_kl_pi=0.0, mean_kl_v=0.0)
+    legal = ((occ[:, None] >> (np.arange(9, dtype=np.uint64)[None, :] * _U(7) + _U(6))) & _U(1)) == 0
+    every = np.ones((n, 3), bool)
+    d = np.abs(a - b)
+    return dict(rows=int(n), max_abs_diff=float(d.max()), mean_abs_diff=float(d.mean()),
+                pi_argmax_differs=float(np.mean(_first_argmax(a[:, :9], legal) != _first_argmax(b[:, :9], legal))),
+                v_argmax_differs=float(np.mean(_first_argmax(a[:, 9:], every) != _first_argmax(b[:, 9:], every))),
+                mean_kl_pi=float(np.mean(_masked_kl(a[:, :9], b[:, :9], legal))),
+                mean_kl_v=float(np.mean(_masked_kl(a[:, 9:], b[:, 9:], every))))

@@ -227,6 +227,7 @@ struct syn_engine {
         size_t n_unseen = 0;      // rows [0, n_unseen): states that are not in the learner's data set (syn_dataset_counts); syn_dataset_set: n
         uint64_t holdout_key = 0, holdout_threshold = 0;   // syn_replay_set_holdout; threshold 0 = nothing is held out
         float* d_img = nullptr;   // sized for the larger of Connect4Net's f32 image and Connect4ConvNet's parameters; allocated on first use
+        uint32_t* d_img16 = nullptr;   // the f16x2 image a syn_dataset_evaluate_arith in SYN_EVAL_ARITH_F16X2 builds (F16Geom::IMG_WORDS); on first use
     } evalset;
 };
 
@@ -666,6 +667,7 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->learner.d_micro_rows);
     hipFree(h->evalset.d_data);
     hipFree(h->evalset.d_img);
+    hipFree(h->evalset.d_img16);
     hipFree(h->d_replay);
     hipFree(h->d_replay_alt);
     hipFree(h->d_cache);
@@ -4105,6 +4107,16 @@ int syn_dataset_get(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* targ
 int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int max_workgroups,
                          syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return syn_dataset_evaluate_arith(h, which, first_row, n_rows, blob, n_floats, SYN_EVAL_ARITH_F32, max_workgroups, out, block_losses,
+                                      row_logits, row_kl);
+}
+
+int syn_dataset_evaluate_arith(syn_engine* h, int which, size_t first_row, size_t n_rows, const float* blob, size_t n_floats, int arithmetic,
+                               int max_workgroups, syn_dataset_metrics* out, float* block_losses, float* row_logits, float* row_kl) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    if (arithmetic != SYN_EVAL_ARITH_F32 && arithmetic != SYN_EVAL_ARITH_F16X2 && arithmetic != SYN_EVAL_ARITH_BF16)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown evaluation arithmetic %d", arithmetic);
     if (which != SYN_DATASET_TRAIN && which != SYN_DATASET_EVAL) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown data set %d", which);
     if (max_workgroups < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "max_workgroups is negative (%d); 0 lets the library choose", max_workgroups);
     auto& L = h->learner;
@@ -4125,6 +4137,8 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
         if (!L.has_trainer) return fail(h, SYN_ERR_NO_WEIGHTS, "blob is NULL (the trainer's weights): call syn_trainer_init first");
         kind = L.trainer_kind;
     }
+    if (arithmetic == SYN_EVAL_ARITH_BF16 && kind != 1)
+        return fail(h, SYN_ERR_UNSUPPORTED, "the bf16 precision exists for Connect4ConvNet only (syn_trainer_set_precision)");
     syn_dataset_metrics m;
     std::memset(&m, 0, sizeof(m));
     h->last_kernel_ms = 0.0f;
@@ -4143,9 +4157,26 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
     char* sc = static_cast<char*>(h->d_scratch);
     // the parameters: the trainer's own buffers (read only), or the caller's blob built into the evaluation's own image buffer
     HostImage im;
-    const float* d_w;
-    if (blob) {
-        auto& E = h->evalset;
+    const float* d_w = nullptr;
+    auto& E = h->evalset;
+    if (arithmetic == SYN_EVAL_ARITH_F16X2) {
+        // the f16x2 image is built on the host from the canonical parameters, per call, into a buffer of the call's own: the engine's
+        // network, arithmetic, f16x2 image, host blob and policy cache do not enter. Parameters without a plan are refused here, before
+        // anything is enqueued.
+        std::vector<float> own;
+        if (!blob) {
+            own.resize((size_t)g_net_desc[kind].num_params);
+            HIP_TRY(h, hipMemcpyAsync(own.data(), L.d_tw, g_net_desc[kind].param_bytes(), hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+        }
+        im.f16x2 = true;
+        if (!g_net_desc[kind].build_f16x2(blob ? blob : own.data(), im.words))
+            return fail(h, SYN_ERR_UNSUPPORTED, "these parameters have no f16x2 plan (non-finite values, scales outside the f32-safe window or a "
+                                                "bias that does not fit; syn_f16x2_plan_of_blob): nothing was evaluated");
+        if (!E.d_img16) HIP_TRY(h, hipMalloc(&E.d_img16, (size_t)F16Geom::IMG_WORDS * 4));
+        rc = enqueue_image_upload(h, im, E.d_img16);
+        if (rc != SYN_OK) return rc;
+    } else if (blob) {
         if (!E.d_img) HIP_TRY(h, hipMalloc(&E.d_img, (size_t)MlpGeom::IMG_FLOATS * 4));
         if (kind == 0) {
             rc = build_host_image(h, 0, blob, false, im);
@@ -4172,11 +4203,28 @@ int syn_dataset_evaluate(syn_engine* h, int which, size_t first_row, size_t n_ro
     A.row_kl = row_kl ? reinterpret_cast<float*>(sc + o_kl) : nullptr;
     // the library's choice: two workgroups of either kernel are resident on a CU (8 waves each at 4 waves per SIMD);
     // Connect4Net gets exactly those, Connect4ConvNet twice as many, the second half taking the CUs as the first drains
-    const size_t fit = (size_t)h->num_cus * (kind == 0 ? 2 : 4);
+    // f16x2: the image takes most of a CU's LDS (Connect4Net: one workgroup per CU; Connect4ConvNet: LDS allows two, its 131 VGPRs one
+    // resident at a time, the second half taking the CUs as the first drains) and a workgroup has four blocks in flight, so the grid is
+    // counted in passes of four blocks
+    const bool f16 = arithmetic == SYN_EVAL_ARITH_F16X2;
+    const size_t fit = f16 ? (size_t)h->num_cus * (kind == 0 ? 1 : 2) : (size_t)h->num_cus * (kind == 0 ? 2 : 4);
     const size_t cap = max_workgroups > 0 ? (size_t)max_workgroups : fit;
-    const unsigned grid = (unsigned)(nb < cap ? nb : cap);
+    const size_t want = f16 ? (nb + DS_F16_SLOTS - 1) / DS_F16_SLOTS : nb;
+    const unsigned grid = (unsigned)(want < cap ? want : cap);
     HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-    if (kind == 0) {
+    if (f16 && kind == 0) {
+        const size_t lds = (size_t)DsF16Geom<0>::LDS_WORDS * 4;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_f16x2_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dataset_eval_blocks_f16x2_kernel<0>, dim3(grid), dim3(DS_F16_THREADS), lds, h->stream, E.d_img16, A);
+    } else if (f16) {
+        const size_t lds = (size_t)DsF16Geom<1>::LDS_WORDS * 4;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_f16x2_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dataset_eval_blocks_f16x2_kernel<1>, dim3(grid), dim3(DS_F16_THREADS), lds, h->stream, E.d_img16, A);
+    } else if (arithmetic == SYN_EVAL_ARITH_BF16) {
+        const size_t lds = (size_t)DsConvGeom::LDS_FLOATS * 4;
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_conv_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(dataset_eval_blocks_conv_bf16_kernel, dim3(grid), dim3(CONV_TRAIN_THREADS), lds, h->stream, d_w, A);
+    } else if (kind == 0) {
         const size_t lds = (size_t)DsMlpGeom::LDS_FLOATS * 4;
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(dataset_eval_blocks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(dataset_eval_blocks_kernel, dim3(grid), dim3(DS_MLP_THREADS), lds, h->stream, d_w, A);

@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "syn_positions_mirror", "syn_replay_deduplicate_symmetric", "syn_replay_deduplicate_to_trainer_symmetric",
     "syn_match_run", "syn_match_run_sides", "syn_tournament_run", "syn_debug_tournament_regroup",
     "syn_train_epochs_sampled", "syn_debug_sampler",
-    "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_replay_set_holdout", "syn_dataset_counts",
+    "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_dataset_evaluate_arith", "syn_replay_set_holdout", "syn_dataset_counts",
     "syn_replay_reanalyse",
     "syn_trainer_set_state", "syn_state_digest",
 ]
@@ -95,6 +95,7 @@ class CDatasetMetrics(C.Structure):  # struct syn_dataset_metrics
 
 
 DATASETS = {"train": 0, "eval": 1}   # SYN_DATASET_*
+EVAL_ARITHMETICS = {"f32": 0, "f16x2": 1, "bf16": 2}   # SYN_EVAL_ARITH_*
 
 
 class CReanalyseConfig(C.Structure):  # struct syn_reanalyse_config
@@ -250,6 +251,8 @@ def load_library():
                            ("syn_dataset_get", [C.c_void_p] + [C.c_void_p] * 4 + [C.c_size_t, C.POINTER(C.c_size_t)]),
                            ("syn_dataset_evaluate", [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                                      C.POINTER(CDatasetMetrics), C.c_void_p, C.c_void_p, C.c_void_p]),
+                           ("syn_dataset_evaluate_arith", [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_int,
+                                                           C.POINTER(CDatasetMetrics), C.c_void_p, C.c_void_p, C.c_void_p]),
                            ("syn_replay_set_holdout", [C.c_void_p, C.c_uint64, C.c_uint64]),
                            ("syn_dataset_counts", [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
                            ("syn_replay_reanalyse", [C.c_void_p, C.POINTER(CMctsConfig), C.POINTER(CReanalyseConfig),
@@ -1082,14 +1085,19 @@ class Engine:
         self._check(self._lib.syn_dataset_counts(self._h, C.byref(n), C.byref(u)))
         return int(n.value), int(u.value)
 
-    def dataset_evaluate(self, which="eval", first_row=0, n_rows=None, blob=None, max_workgroups=0, blocks=False, rows=False):
-        """syn_dataset_evaluate: the f32 learner's losses of `blob` (None: the trainer's current weights) on the rows
+    def dataset_evaluate(self, which="eval", first_row=0, n_rows=None, blob=None, max_workgroups=0, blocks=False, rows=False, arith="f32"):
+        """syn_dataset_evaluate_arith: the f32 learner's losses of `blob` (None: the trainer's current weights) on the rows
         [first_row, first_row + n_rows) of the learner's data set (which="train") or the evaluation set ("eval"); n_rows=None = to the
-        end of the set. Forward only: nothing of the trainer or the engine changes. Returns dict(mean_pi, mean_v, sum_pi, sum_v (f64),
-        rows, blocks, pi_hits, v_hits, pi_acc, v_acc, grid); blocks=True adds block_losses [n_blocks, 2], rows=True row_logits
-        [n_rows, 12] and row_kl [n_rows, 2]."""
+        end of the set. arith = the arithmetic that computes a row's twelve raw outputs: "f32" (the learner's), "f16x2" (the engine's
+        f16x2 inference, an image built per call; both networks) or "bf16" (the conv learner's bf16 forward; Connect4ConvNet only); an
+        int is passed through as it is. Forward only: nothing of the trainer or the engine changes. Returns dict(mean_pi, mean_v,
+        sum_pi, sum_v (f64), rows, blocks, pi_hits, v_hits, pi_acc, v_acc, grid, arith); blocks=True adds block_losses [n_blocks, 2],
+        rows=True row_logits [n_rows, 12] and row_kl [n_rows, 2]."""
         if which not in DATASETS:
             raise ValueError(f"which must be 'train' or 'eval', got {which!r}")
+        if not isinstance(arith, (int, np.integer)) and arith not in EVAL_ARITHMETICS:
+            raise ValueError(f"arith must be one of {sorted(EVAL_ARITHMETICS)}, got {arith!r}")
+        arith_code = int(arith) if isinstance(arith, (int, np.integer)) else EVAL_ARITHMETICS[arith]
         if n_rows is None:
             size = C.c_size_t(0)
             if which == "train":
@@ -1106,9 +1114,10 @@ class Engine:
         lg = np.zeros((n_rows, 12), np.float32) if rows else None
         kl = np.zeros((n_rows, 2), np.float32) if rows else None
         m = CDatasetMetrics()
-        self._check(self._lib.syn_dataset_evaluate(self._h, DATASETS[which], int(first_row), n_rows, _p(blob), 0 if blob is None else int(blob.size),
-                                                   int(max_workgroups), C.byref(m), _p(bl), _p(lg), _p(kl)))
-        out = dict(mean_pi=float(m.mean_pi), mean_v=float(m.mean_v), sum_pi=float(m.sum_pi), sum_v=float(m.sum_v), rows=int(m.rows),
+        self._check(self._lib.syn_dataset_evaluate_arith(self._h, DATASETS[which], int(first_row), n_rows, _p(blob),
+                                                         0 if blob is None else int(blob.size), arith_code, int(max_workgroups), C.byref(m),
+                                                         _p(bl), _p(lg), _p(kl)))
+        out = dict(arith=arith, mean_pi=float(m.mean_pi), mean_v=float(m.mean_v), sum_pi=float(m.sum_pi), sum_v=float(m.sum_v), rows=int(m.rows),
                    blocks=int(m.blocks), pi_hits=int(m.pi_hits), v_hits=int(m.v_hits), grid=int(m.grid),
                    pi_acc=m.pi_hits / m.rows if m.rows else 0.0, v_acc=m.v_hits / m.rows if m.rows else 0.0)
         if blocks:

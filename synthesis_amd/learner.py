@@ -120,6 +120,8 @@ def reanalyse_flags(key, threshold, before_gid, gid, my, op):
 
 
 _METRIC_KEYS = ("rows", "mean_pi", "mean_v", "pi_acc", "v_acc")
+HOLDOUT_ARITHMETICS = ("f32", "f16x2", "bf16")   # LearningLoop(holdout_arith=...): Engine.dataset_evaluate's `arith` names
+_SYN_ERR_UNSUPPORTED = -5
 
 
 # ---- the state file of a LearningLoop (LearningLoop.save_state / restore_state): ONE .npz written by numpy alone, no pickling. Needs no GPU.
@@ -292,6 +294,12 @@ class LearningLoop:
                  arg-max accuracies (Engine.dataset_evaluate) of the weights before and after the iteration's epochs, each as
                  dict(all=..., unseen=...) over all held-out rows and over those whose state the learner's data set does not contain.
                  Both replay modes, same bits. An iteration whose buffer has no game left for the learner raises.
+    holdout_arith  ("f32",) (default: no record and no bit changes) | the arithmetics the held-out metrics are taken in, names of
+                 Engine.dataset_evaluate's `arith`: "f32" stands for the keys above; "f16x2" and "bf16" (Connect4ConvNet) each add
+                 `holdout_before_<name>` / `holdout_after_<name>` of the same shape, the same weights and rows evaluated in that arithmetic
+                 (include/synthesis_amd.h syn_dataset_evaluate_arith). Weights without an f16x2 plan give None for that entry and the run
+                 goes on. An observer like `replay`: it trains nothing and is not part of the run's fingerprint. Both replay modes report
+                 identical values. Not measured: what the extra evaluations cost an iteration.
     reanalyse    0.0 (default: every bit and every record as without the argument) | a fraction of ROWS in (0, 1]: after the keep-window
                  and before the de-duplication of every iteration the learner's rank searches that fraction of the stored positions of
                  OLDER games (gid below this iteration's first game; the hash of `_reanalyse_key(seed, iteration)`, the game id and the
@@ -325,7 +333,13 @@ class LearningLoop:
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
                  network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0,
-                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, digests=False, **hyper):
+                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, digests=False, holdout_arith=("f32",), **hyper):
+        holdout_arith = (holdout_arith,) if isinstance(holdout_arith, str) else tuple(holdout_arith)
+        for a in holdout_arith:
+            if a not in HOLDOUT_ARITHMETICS:
+                raise ValueError(f"holdout_arith names must be among {list(HOLDOUT_ARITHMETICS)}, got {a!r}")
+            if a == "bf16" and net != "conv":
+                raise ValueError("holdout_arith 'bf16' exists for net='conv' only (the conv learner's bf16 precision)")
         _real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
         if not _real(reanalyse) or not 0.0 <= float(reanalyse) <= 1.0:
             raise ValueError(f"reanalyse must be a fraction of rows in [0, 1], got {reanalyse!r}")
@@ -388,6 +402,7 @@ class LearningLoop:
         self.sampler = sampler
         self.flip = bool(flip)
         self._torch_gen = torch.Generator().manual_seed(self.seed) if sampler == "torch" else None
+        self.holdout_arith = tuple(a for a in HOLDOUT_ARITHMETICS if a in holdout_arith and a != "f32")   # the extra ones, in a fixed order
         self.holdout = float(holdout)
         self._holdout_threshold = int(np.floor(self.holdout * 4294967296.0))
         if self._holdout_threshold and self.rank == 0 and replay == "device":
@@ -692,6 +707,7 @@ class LearningLoop:
             if self._holdout_threshold:
                 held = self.engine.dataset_counts()
                 before = self._holdout_metrics(*held)
+                before_arith = self._holdout_metrics_arith("holdout_before", held)
             t3 = time.perf_counter()
             steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
@@ -699,6 +715,7 @@ class LearningLoop:
             rec.update(steps_in_buffer=steps_in_buffer, unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
             if self._holdout_threshold:
                 rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
+                rec.update(before_arith, **self._holdout_metrics_arith("holdout_after", held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = n_canonical
             if self._reanalyse_threshold:
@@ -719,12 +736,27 @@ class LearningLoop:
             rec["seconds"]["reanalyse"] = round(t_re, 4)
         return rec
 
-    def _holdout_metrics(self, n_eval, n_unseen):
+    def _holdout_metrics(self, n_eval, n_unseen, arith="f32"):
         """The trainer's current weights on the evaluation set: dict(all=..., unseen=...) of dict(rows, mean_pi, mean_v, pi_acc, v_acc)"""
         out = {}
         for name, n in (("all", n_eval), ("unseen", n_unseen)):
-            m = self.engine.dataset_evaluate("eval", 0, n) if n_eval else dict.fromkeys(_METRIC_KEYS, 0.0)
+            m = self.engine.dataset_evaluate("eval", 0, n, arith=arith) if n_eval else dict.fromkeys(_METRIC_KEYS, 0.0)
             out[name] = {k: (int(m[k]) if k == "rows" else float(m[k])) for k in _METRIC_KEYS}
+        return out
+
+    def _holdout_metrics_arith(self, prefix, held):
+        """{prefix_<arith>: _holdout_metrics in that arithmetic} for every extra name of holdout_arith; None where the current weights
+        cannot be evaluated in it (no f16x2 plan: SYN_ERR_UNSUPPORTED) — the run goes on"""
+        from .engine import SynthesisAmdError
+
+        out = {}
+        for a in self.holdout_arith:
+            try:
+                out[f"{prefix}_{a}"] = self._holdout_metrics(*held, arith=a)
+            except SynthesisAmdError as e:
+                if e.code != _SYN_ERR_UNSUPPORTED:
+                    raise
+                out[f"{prefix}_{a}"] = None
         return out
 
     def _holdout_split_host(self):
@@ -865,12 +897,14 @@ class LearningLoop:
             self.engine.train_set_data(D["my_bb"], D["op_bb"], D["pis"], D["vs"])
             if self._holdout_threshold:
                 before = self._holdout_metrics(*held)
+                before_arith = self._holdout_metrics_arith("holdout_before", held)
             steps, epoch_losses = self._epochs(it, epochs, batch_size, lr, n_unique)
             t_train = time.perf_counter() - t3
             self.weights = self.engine.trainer_state()["weights"]
             rec.update(steps_in_buffer=int(self.R["my"].size), unique=n_unique, optimiser_steps=steps, epoch_losses=epoch_losses)
             if self._holdout_threshold:
                 rec.update(holdout_rows=held[0], holdout_unseen=held[1], holdout_before=before, holdout_after=self._holdout_metrics(*held))
+                rec.update(before_arith, **self._holdout_metrics_arith("holdout_after", held))
             if self.symmetry == "mirror":
                 rec["unique_canonical"] = D["canonical"]
             if self._reanalyse_threshold:

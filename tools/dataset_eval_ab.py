@@ -196,7 +196,7 @@ def main():
                timing="host clock (time.perf_counter) around one call that ends in a device synchronise (leg 2: followed by one)",
                order="leg 1: one process per run, A, B, A, B, ... per network; leg 2: one engine, arms interleaved, 2 warm-up runs",
                timed_runs=args.timed, date=time.strftime("%Y-%m-%d"),
-               not_measured=["any training run judged with the held-out metrics", "evaluation in f16x2 or bf16", "more than one GPU"])
+               not_measured=["any training run judged with the held-out metrics", "more than one GPU"])
     rec["holdout_split"] = start_child(args, "split", "mlp", "-")
     print(json.dumps(rec["holdout_split"]), flush=True)
     with tempfile.TemporaryDirectory(dir=args.scratch or None) as tmp:

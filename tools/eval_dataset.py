@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The losses and arg-max accuracies of one checkpoint on one data set (Engine.dataset_evaluate: the f32 learner's definition, forward
-only), overall and by stone count. One JSON line.
+only; --arith f16x2 / bf16: the same head on the raw outputs of that arithmetic), overall and by stone count. One JSON line.
 
     python tools/eval_dataset.py --checkpoint logs/models/model_12.ot --logs-dir logs          # latest_states / pis / vs.npy of a run
     python tools/eval_dataset.py --checkpoint tests/golden/c4conv_trained_f32.npy --games 2048  # self-play by the checkpoint itself
@@ -55,9 +55,9 @@ def by_stone_count(r, my, op, tpi, tv):
     return out
 
 
-def evaluate(eng, blob, first, n, breakdown, D):
+def evaluate(eng, blob, first, n, breakdown, D, arith="f32"):
     keys = ("rows", "mean_pi", "mean_v", "pi_acc", "v_acc")
-    r = eng.dataset_evaluate("eval", first, n, blob=blob, rows=breakdown)
+    r = eng.dataset_evaluate("eval", first, n, blob=blob, rows=breakdown, arith=arith)
     out = {k: r[k] for k in keys}
     if breakdown and n:
         sl = slice(first, first + n)
@@ -76,6 +76,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--no-breakdown", action="store_true")
+    ap.add_argument("--arith", default="f32", choices=["f32", "f16x2", "bf16"], help="the arithmetic that computes the rows' raw outputs: the f32 "
+                    "learner's, the engine's f16x2 inference, or the conv learner's bf16 forward (Connect4ConvNet only)")
     args = ap.parse_args()
     if bool(args.logs_dir) == bool(args.games):
         raise SystemExit("give exactly one data set: --logs-dir DIR or --games N")
@@ -91,7 +93,7 @@ def main():
     blob = load_checkpoint(args.checkpoint)
     if blob.size not in (NUM_PARAMS, CONV_NUM_PARAMS):
         raise SystemExit(f"{args.checkpoint} holds {blob.size} floats: neither Connect4Net ({NUM_PARAMS}) nor Connect4ConvNet ({CONV_NUM_PARAMS})")
-    out = dict(tool="tools/eval_dataset.py", checkpoint=args.checkpoint, network="Connect4ConvNet" if blob.size == CONV_NUM_PARAMS else "Connect4Net")
+    out = dict(tool="tools/eval_dataset.py", checkpoint=args.checkpoint, arith=args.arith, network="Connect4ConvNet" if blob.size == CONV_NUM_PARAMS else "Connect4Net")
     breakdown = not args.no_breakdown
     with sa.Engine(concurrent_games=max(16, min(args.games, 65536)), max_explores=max(args.explores, 8), device=args.device) as eng:
         if args.logs_dir:
@@ -119,9 +121,9 @@ def main():
             out["data_set"] = dict(games=args.games, explores=args.explores, player=args.player or args.checkpoint, seed=args.seed,
                                    positions=positions, holdout=args.holdout, learner_rows=learner_rows if threshold else 0, rows=n)
         D = eng.dataset_get()
-        out["all"] = evaluate(eng, blob, 0, n, breakdown, D)
+        out["all"] = evaluate(eng, blob, 0, n, breakdown, D, args.arith)
         if unseen is not None:
-            out["unseen"] = evaluate(eng, blob, 0, unseen, breakdown, D)
+            out["unseen"] = evaluate(eng, blob, 0, unseen, breakdown, D, args.arith)
         out["device_ms_last_call"] = eng.last_timing()[0]
     print(json.dumps(out))
 
