@@ -96,6 +96,10 @@ def main():
     ap.add_argument("--reanalyse-explores", type=int, default=None, help="explores of a reanalysis search (default: --explores)")
     ap.add_argument("--reanalyse-value-mix", type=float, default=0.0, help="w in [0, 1]: a reanalysed row's v becomes v * (1 - w) + the new "
                     "search's target_q * w (0 = v is left alone)")
+    ap.add_argument("--exploring-starts", type=float, default=0.0, help="fraction F in [0, 1) of every iteration's games, from the second "
+                    "iteration on, that start at positions drawn from the replay buffer instead of the empty board (recorded device "
+                    "games on the learner's rank, current weights; 0 = off; learning loop only; needs a deterministic search "
+                    "configuration, so not --reference-fpu; whether it trains a stronger player is not measured)")
     ap.add_argument("--state", default="", help="path of the run's state file (LearningLoop.save_state: one .npz with the trainer, the "
                     "replay buffer, the counters and their digests); written after every --save-every-th iteration and after the last")
     ap.add_argument("--save-every", type=int, default=0, help="save --state after every K-th iteration (0 = after the last one only)")
@@ -115,6 +119,10 @@ def main():
         raise SystemExit("--reanalyse and --reanalyse-value-mix are fractions in [0, 1]")
     if args.reanalyse_explores is not None and not 0 <= args.reanalyse_explores <= args.explores:
         raise SystemExit("--reanalyse-explores must be in 0 .. --explores (the engine's node pool is sized for --explores)")
+    if args.exploring_starts and (args.data_parallel or args.reference_fpu):
+        raise SystemExit("--exploring-starts belongs to the learning loop and takes deterministic searches only (no --reference-fpu)")
+    if not 0.0 <= args.exploring_starts < 1.0:
+        raise SystemExit(f"--exploring-starts is a fraction of an iteration's games in [0, 1), got {args.exploring_starts}")
     if args.holdout and args.data_parallel:
         raise SystemExit("--holdout belongs to the learning loop: --data-parallel hands every position to the learner")
     if not 0.0 <= args.holdout < 1.0:
@@ -169,7 +177,8 @@ def main():
                             network_arithmetic=args.network_arithmetic, replay=args.replay, symmetry=args.symmetry,
                             batch_mode=args.batch_mode, flip=args.flip, holdout=args.holdout, reanalyse=args.reanalyse,
                             reanalyse_explores=args.reanalyse_explores, reanalyse_value_mix=args.reanalyse_value_mix, digests=args.digests,
-                            holdout_arith=tuple(a for a in args.holdout_arith.split(",") if a), **hyper)
+                            holdout_arith=tuple(a for a in args.holdout_arith.split(",") if a), exploring_starts=args.exploring_starts,
+                            **hyper)
         if args.resume:
             loop.restore_state(args.resume)
     log = []

@@ -830,6 +830,73 @@ typedef struct syn_reanalyse_stats {
 int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_reanalyse_config* cfg,
                          syn_reanalyse_stats* out /*may be NULL*/, int64_t* selected_rows /*may be NULL*/, size_t capacity);
 
+/* ---- Recorded games (opt-in; csrc/record_kernels.cuh; not in the reference): training rows from games that start at
+ * given positions and are played by given players. syn_selfplay_run is run_game (alpha_zero.rs:229-268) from the empty board with one
+ * network on both sides; this call is run_game inside syn_tournament_run's loop, so exploring starts (positions of the replay buffer),
+ * curricula (a file of positions) and league data (the current network against an older one) leave rows a learner can use.
+ * Arguments and refusals are syn_tournament_run's, made before anything of the engine or the device changes. In addition:
+ *   network sides only: a baseline side is SYN_ERR_UNSUPPORTED (its search record has no target_pi / target_q);
+ *   deterministic search configurations only, the match's own rule (SYN_FPU_NORMAL, SYN_FPU_FUNC, SYN_NOISE_DIRICHLET:
+ *   SYN_ERR_UNSUPPORTED — their streams are keyed by job index);
+ *   rec NULL, an unknown value_target, a negative *_until, a record_mask bit at or above n_players, and seeds == NULL unless both *_until
+ *   are 0: SYN_ERR_INVALID_ARGUMENT.
+ * Definition. Game g is run_game with these substitutions. G::new() is (start_my[g], start_op[g]). At ply k (0-based from the start
+ * position; k is run_game's num_turns, so random_actions_until and sample_actions_until count from the START position) the tree is the
+ * mover's, players[k even ? first[g] : second[g]], with its blob, arithmetic, explores, mcts_cfg and action selection. sample_action's
+ * draws come from StdRng::seed_from_u64(seeds[g]), from the game's stream position on: gen_range one word per candidate (rejections
+ * included), WeightedIndex one word, exactly as syn_selfplay_run takes them; rng_words[g] is the first unused word. mcts.solution(&action),
+ * stop_games_when_solved, fill_state_info and store_rewards are the reference's (alpha_zero.rs:254-338): t = (k + 1) / plies[g] with
+ * plies[g] = ALL moves of the game, recorded or not, and z by parity from the game's last position. A ply whose mover has its bit clear
+ * in record_mask is played but leaves no row; the rows of a game are stored densely (row r = its r-th recorded ply, rows[g] <=
+ * plies[g]). With stop_games_when_solved a game may end before the board decides it: rewards[g] is then the solved outcome, final_bb[g]
+ * the position after the last move played.
+ * The property that pins it: one player (first = second = 0, record_mask = 1) with the engine's loaded weights as blob in the engine's
+ * arithmetic, the empty board as every start, seeds[g] = base_seed + first_game + g and a rollout configuration's fields copied over
+ * gives, bit for bit, syn_selfplay_run(cfg, base_seed, first_game, n)'s outputs: rows == its plies, states, pis, vs, actions, root_nodes,
+ * final_kind.
+ * Outputs. The tournament's per-game outputs, and `out` (may be NULL; each pointer may be NULL): the rows in syn_selfplay_run's padded
+ * shapes, slot = game; slots no row reaches are zero. On success the rows also stay in the engine's self-play output buffers: THE CALL
+ * REPLACES THE LAST SELF-PLAY LAUNCH'S OUTPUTS. syn_replay_append_selfplay(first_gid) and syn_selfplay_positions_device then compact
+ * them as they compact a launch of n_games games (game slot j gets gid first_gid + j; a game without rows adds nothing). After any
+ * error or refusal of this call they refuse, as after a failed syn_selfplay_run.
+ * Untouched: the engine's network, images, arithmetic, policy cache, trainer, replay buffer and both data sets. syn_cancel,
+ * syn_progress, the capacity errors and the 63-ply bound behave as documented for syn_tournament_run. syn_last_timing: two launches
+ * per non-empty group and two for the regroup, per ply, and one more for the kernel that finishes the rows.
+ * Not measured: whether rows from exploring starts, curricula or league games train a stronger player. Out of scope: noise or
+ * Fpu::Normal in recorded games, baseline sides. */
+typedef struct syn_record_config {
+    int32_t random_actions_until;    /* RolloutConfig fields, alpha_zero.rs:270-293; turns count from the START position */
+    int32_t sample_actions_until;
+    int32_t stop_games_when_solved;
+    int32_t value_target;            /* SYN_VALUE_* */
+    float value_target_p, value_target_from, value_target_to;
+    int32_t reserved;
+    uint64_t record_mask;            /* bit p: the plies player p moves in become rows */
+} syn_record_config;
+
+typedef struct syn_record_outputs {  /* host pointers, each may be NULL; syn_selfplay_run's shapes, slot = game */
+    int32_t* rows;          /* [n]      recorded rows of game g */
+    uint64_t* states_bb;    /* [n][63][2] */
+    float* pis;             /* [n][63][9] */
+    float* vs;              /* [n][63][3] */
+    uint8_t* actions;       /* [n][63]  the action played from that row's position */
+    uint32_t* root_nodes;   /* [n][63] */
+    uint8_t* final_kind;    /* [n] */
+} syn_record_outputs;
+
+int syn_games_run_recorded(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
+                           const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games,
+                           const syn_record_config* rec, float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb,
+                           uint64_t* rng_words, const syn_record_outputs* out);
+
+/* Start positions from the device replay buffer: "Reanalyse"'s selection alone — the same hash of (key, gid, my, op), the same gid
+ * bound and searchable test, buffer order — with the selected positions downloaded, 16 bytes each, into my_bb / op_bb (room for
+ * `capacity` positions). *n_selected = the number selected, also when SYN_ERR_CAPACITY says the arrays are too small (nothing is written
+ * to them then); *n_skipped (may be NULL) = rows that passed the bound and the hash but are not searchable. The buffer is read, never
+ * written. threshold > 2^32, n_selected NULL, or no buffer reserved: SYN_ERR_INVALID_ARGUMENT. */
+int syn_replay_select_positions(syn_engine* h, uint64_t key, uint64_t threshold, int64_t before_gid, uint64_t* my_bb, uint64_t* op_bb,
+                                size_t capacity, size_t* n_selected, size_t* n_skipped);
+
 /* ---- State digests (csrc/digest_kernels.cuh; not in the reference): a 64-bit fingerprint of a piece of engine state,
  * computed where the state lives, so that "these two runs hold the same bits" is one word in a log instead of a download.
  * Definition. A component is a sequence of 32-bit words w_0 .. w_{L-1}: its arrays, concatenated in the order given below, each read as

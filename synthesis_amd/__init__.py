@@ -15,12 +15,12 @@ Everything computes on the GPU through the C ABI in include/synthesis_amd.h (lib
 gfx950). There is no CPU fallback: importing works anywhere, creating an Engine without the library or without an
 MI355X raises.
 """
-from .config import (ActionSelection, Exploration, Fpu, MCTSConfig, PolicyNoise, RolloutConfig, ValueTarget,
+from .config import (ActionSelection, Exploration, Fpu, MCTSConfig, PolicyNoise, RecordConfig, RolloutConfig, ValueTarget,
                      parity_mcts_config, parity_rollout_config, reference_selfplay_mcts_config)
 from .engine import Engine, SynthesisAmdError, library_path, load_library, shard_games
 
 __all__ = [
-    "ActionSelection", "Exploration", "Fpu", "MCTSConfig", "PolicyNoise", "RolloutConfig", "ValueTarget",
+    "ActionSelection", "Exploration", "Fpu", "MCTSConfig", "PolicyNoise", "RecordConfig", "RolloutConfig", "ValueTarget",
     "parity_mcts_config", "parity_rollout_config", "reference_selfplay_mcts_config", "Engine", "SynthesisAmdError", "library_path", "load_library",
     "shard_games",
 ]

@@ -7,6 +7,7 @@ thread_rng). `PolicyNoise.Dirichlet` samples rand_distr's Dirichlet on the devic
 """
 import ctypes as C
 import enum
+import operator
 from dataclasses import dataclass, field
 
 
@@ -116,6 +117,47 @@ class RolloutConfig:                      # config.rs:46-56 (num_workers -> Engi
                               int(self.stop_games_when_solved), int(self.value_target), float(self.value_target_p),
                               float(self.value_target_from), float(self.value_target_to), int(self.action),
                               self.mcts_cfg.to_c())
+
+
+class CRecordConfig(C.Structure):         # struct syn_record_config
+    _fields_ = [("random_actions_until", C.c_int32), ("sample_actions_until", C.c_int32), ("stop_games_when_solved", C.c_int32),
+                ("value_target", C.c_int32), ("value_target_p", C.c_float), ("value_target_from", C.c_float),
+                ("value_target_to", C.c_float), ("reserved", C.c_int32), ("record_mask", C.c_uint64)]
+
+
+@dataclass
+class RecordConfig:                       # include/synthesis_amd.h "Recorded games": run_game's tail for Engine.games_run_recorded
+    random_actions_until: int = 0     # turns count from the START position
+    sample_actions_until: int = 0
+    stop_games_when_solved: bool = False
+    value_target: ValueTarget = ValueTarget.Q
+    value_target_p: float = 0.0
+    value_target_from: float = 0.0
+    value_target_to: float = 0.0
+    record_mask: int = 1              # bit p: the plies player p moves in become rows
+
+    def __post_init__(self):
+        for name in ("random_actions_until", "sample_actions_until", "record_mask"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not hasattr(v, "__index__") or operator.index(v) < 0:
+                raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
+        if int(self.record_mask) >= 1 << 64:
+            raise ValueError(f"record_mask must fit 64 bits (one per player), got {self.record_mask!r}")
+        if int(self.value_target) not in [int(t) for t in ValueTarget]:
+            raise ValueError(f"value_target must be a ValueTarget, got {self.value_target!r}")
+
+    @classmethod
+    def from_rollout(cls, cfg: "RolloutConfig", record_mask=1) -> "RecordConfig":
+        """The record configuration of a rollout configuration: its sample_action, stop rule and value target; the search settings
+        (num_explores, action, mcts_cfg) belong to the players of the call."""
+        return cls(random_actions_until=cfg.random_actions_until, sample_actions_until=cfg.sample_actions_until,
+                   stop_games_when_solved=cfg.stop_games_when_solved, value_target=cfg.value_target, value_target_p=cfg.value_target_p,
+                   value_target_from=cfg.value_target_from, value_target_to=cfg.value_target_to, record_mask=record_mask)
+
+    def to_c(self) -> CRecordConfig:
+        return CRecordConfig(int(self.random_actions_until), int(self.sample_actions_until), int(bool(self.stop_games_when_solved)),
+                             int(self.value_target), float(self.value_target_p), float(self.value_target_from),
+                             float(self.value_target_to), 0, int(self.record_mask))
 
 
 def parity_mcts_config(**kw) -> MCTSConfig:

@@ -32,6 +32,7 @@
 #include "sampler_kernels.cuh"
 #include "match_kernels.cuh"
 #include "tournament_kernels.cuh"
+#include "record_kernels.cuh"
 #include "train_mfma.cuh"
 #include "train_epoch.cuh"
 #include "convnet.cuh"
@@ -1662,11 +1663,12 @@ struct GamesLayout {   // byte offsets into syn_engine::Games::d_buf
     size_t first, second;                           // the schedule, per game
     size_t rewards, plies, moves, final_bb, rng_words;   // MatchOut, per game
     size_t seg;                                     // [0 .. K] group starts, [K + 1] error word, [K + 2] the advance kernels' stream-position flag
+    size_t row_ply;                                 // a recording call's [n][63] plies of its rows (record_kernels.cuh); no bytes otherwise
     size_t total;
 };
 constexpr size_t GAMES_RESULT_STRIDE =
     ((sizeof(DevSearchResult) > sizeof(FrozenResult) ? sizeof(DevSearchResult) : sizeof(FrozenResult)) + 15) & ~(size_t)15;
-static GamesLayout games_layout(size_t n, int n_players, size_t cells, size_t scan_bytes, size_t n_explores) {
+static GamesLayout games_layout(size_t n, int n_players, size_t cells, size_t scan_bytes, size_t n_explores, bool recording) {
     GamesLayout L{};
     Carve c;
     for (int k = 0; k < 2; k++) {
@@ -1678,19 +1680,35 @@ static GamesLayout games_layout(size_t n, int n_players, size_t cells, size_t sc
     L.first = c.take(n * 4); L.second = c.take(n * 4);
     L.rewards = c.take(n * 4); L.plies = c.take(n * 4); L.moves = c.take(n * MATCH_T); L.final_bb = c.take(n * 16); L.rng_words = c.take(n * 8);
     L.seg = c.take((size_t)(n_players + 3) * 4);
+    L.row_ply = c.take(recording ? n * MATCH_T : 0);
     L.total = c.at;
     return L;
 }
 
+// What makes a call of the loop a recording one (syn_games_run_recorded; record_kernels.cuh): the rules of run_game's tail, which
+// players' plies become rows, the value target, and where the rows go on the host.
+struct RecordCall {
+    RecordRules rules;
+    uint64_t mask;
+    int value_target;
+    float vt_p, vt_from, vt_to;
+    const syn_record_outputs* out;   // may be NULL
+};
+static int ensure_outputs(syn_engine* h, int n_games);
+
 // The loop. S: the call's K checked players; first / second: the schedule (host). `noun` names the call in messages ("match",
 // "tournament"). Everything that can still refuse the call — the schedule, the starts, an image without a plan — comes before anything
-// of the engine or the device changes; the entry point has selected the engine's device.
+// of the engine or the device changes; the entry point has selected the engine's device. `rec` (may be NULL) makes the call a recording
+// one: record_advance_kernel takes the advance kernel's place, the rows go to the engine's self-play output buffers, and
+// record_finish_kernel runs once after the last ply. With rec == NULL the function enqueues exactly what it enqueued before there was one.
 static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, const int32_t* second, const uint64_t* start_my,
                      const uint64_t* start_op, const uint64_t* seeds, int n_games, float* rewards, int32_t* plies, uint8_t* moves,
-                     uint64_t* final_bb, uint64_t* rng_words, const char* noun) {
+                     uint64_t* final_bb, uint64_t* rng_words, const char* noun, const RecordCall* rec = nullptr) {
+    const std::string fn_name = rec ? std::string("syn_games_run_recorded") : "syn_" + std::string(noun) + "_run";
+    const char* const fn = fn_name.c_str();
     for (int g = 0; g < n_games; g++) {
         if (first[g] < 0 || first[g] >= K || second[g] < 0 || second[g] >= K)
-            return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_%s_run: game %d names players %d and %d; there are %d", noun, g, first[g],
+            return fail(h, SYN_ERR_INVALID_ARGUMENT, "%s: game %d names players %d and %d; there are %d", fn, g, first[g],
                         second[g], K);
         if (const int rc = check_start(h, g, start_my[g], start_op[g])) return rc;
     }
@@ -1723,13 +1741,15 @@ static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, c
     const size_t cells = regroup_cells(n, K);
     size_t scan_bytes = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (const unsigned*)nullptr, (unsigned*)nullptr, (int)cells, h->stream));
-    const GamesLayout L = games_layout(n, K, cells, scan_bytes, n_explores);
+    const GamesLayout L = games_layout(n, K, cells, scan_bytes, n_explores, rec != nullptr);
     for (int p = 0; p < K; p++)
         if (!S[p].baseline && !h->games.d_img[p]) HIP_TRY(h, hipMalloc(&h->games.d_img[p], NET_IMAGE_MAX_BYTES));
     HIP_TRY(h, ensure_device_buffer(h->games.d_buf, h->games.buf_bytes, L.total));
     for (int p = 0; p < K; p++)
         if (S[p].baseline && appears[p] > 0)
             if (const int rc = ensure_frozen_path(h, S[p].part, appears[p])) return rc;
+    if (rec)
+        if (const int rc = ensure_outputs(h, n_games)) return rc;
     unsigned char* const base = h->games.d_buf;
     const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     MatchLive live_set[2];
@@ -1749,6 +1769,17 @@ static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, c
     out.moves = base + L.moves;
     out.final_bb = u64_at(L.final_bb);
     out.rng_words = u64_at(L.rng_words);
+    RecordOut rows{};
+    if (rec) {
+        rows.rows = h->d_plies;
+        rows.states_bb = reinterpret_cast<unsigned long long*>(h->d_states);
+        rows.pis = h->d_pis;
+        rows.vs = h->d_vs;
+        rows.actions = h->d_actions;
+        rows.root_nodes = h->d_root_nodes;
+        rows.final_kind = h->d_final;
+        rows.row_ply = base + L.row_ply;
+    }
 
     CallScope scope(h, n_games);
     std::vector<unsigned long long> s_my(n), s_op(n), s_seed(n, 0ull);
@@ -1780,6 +1811,17 @@ static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, c
     HIP_TRY(h, hipMemsetAsync(out.final_bb, 0, n * 16, h->stream));
     HIP_TRY(h, hipMemsetAsync(out.rng_words, 0, n * 8, h->stream));
     HIP_TRY(h, hipMemsetAsync(d_seg, 0, (size_t)(K + 3) * 4, h->stream));
+    if (rec) {   // no rows yet; the slots no row reaches read as zeros
+        const size_t slots = n * MATCH_T;
+        HIP_TRY(h, hipMemsetAsync(rows.rows, 0, n * 4, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.states_bb, 0, slots * 16, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.pis, 0, slots * 36, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.vs, 0, slots * 12, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.actions, 0, slots, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.root_nodes, 0, slots * 4, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.final_kind, 0, n, h->stream));
+        HIP_TRY(h, hipMemsetAsync(rows.row_ply, 0, slots, h->stream));
+    }
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the last upload from host memory: the loop below only launches and reads K + 2 words
 
     float kernel_ms = 0.0f;
@@ -1820,9 +1862,14 @@ static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, c
                 Q.in_op = A.op + lo;
                 Q.results = reinterpret_cast<DevSearchResult*>(res);
                 if (const int rc = launch_engine(h, Q, cnt, MODE_SEARCH, false, false, S[p].arith)) return rc;
-                hipLaunchKernelGGL(tournament_advance_kernel<DevSearchResult>, grid, block, 0, h->stream,
-                                   reinterpret_cast<const DevSearchResult*>(res), lo, cnt, ply, A.my, A.op, A.id, A.word, d_first, d_second, K,
-                                   d_key, d_stream_error, out);
+                if (rec)
+                    hipLaunchKernelGGL(record_advance_kernel, grid, block, 0, h->stream, reinterpret_cast<const unsigned*>(res), lo, cnt, ply,
+                                       (int)((rec->mask >> p) & 1ull), rec->rules, A.my, A.op, A.id, A.seed, A.word, d_first, d_second, K, d_key,
+                                       d_stream_error, out, rows);
+                else
+                    hipLaunchKernelGGL(tournament_advance_kernel<DevSearchResult>, grid, block, 0, h->stream,
+                                       reinterpret_cast<const DevSearchResult*>(res), lo, cnt, ply, A.my, A.op, A.id, A.word, d_first, d_second, K,
+                                       d_key, d_stream_error, out);
             }
             HIP_TRY(h, hipGetLastError());
             launches += 2;   // the search and the advance
@@ -1848,12 +1895,34 @@ static int run_games(syn_engine* h, MatchSide* S, int K, const int32_t* first, c
         if (const int rc = fail_search_error(h, -err, any_baseline ? "; or a baseline tree of the same ply ran out of node records" : "")) return rc;
         bool sane = h_seg[0] == 0 && h_seg[K] <= live;
         for (int p = 0; p < K && sane; p++) sane = h_seg[p] <= h_seg[p + 1];
-        if (!sane) return fail(h, SYN_ERR_HIP, "syn_%s_run: the regroup of ply %d returned group starts that are no partition of "
-                                               "at most %d games", noun, ply, live);
+        if (!sane) return fail(h, SYN_ERR_HIP, "%s: the regroup of ply %d returned group starts that are no partition of "
+                                               "at most %d games", fn, ply, live);
         for (int p = 0; p <= K; p++) seg[p] = h_seg[p];
         live = seg[K];
     }
-    if (live > 0) return fail(h, SYN_ERR_HIP, "syn_%s_run: %d games are unfinished after %d plies", noun, live, MATCH_T);
+    if (live > 0) return fail(h, SYN_ERR_HIP, "%s: %d games are unfinished after %d plies", fn, live, MATCH_T);
+    if (rec) {   // z, t and store_rewards over the staged q of every row
+        const size_t slots = n * MATCH_T;
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        hipLaunchKernelGGL(record_finish_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, n_games, out.plies,
+                           rec->value_target, rec->vt_p, rec->vt_from, rec->vt_to, rows);
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+        if (const syn_record_outputs* o = rec->out) {
+            if (o->rows) HIP_TRY(h, hipMemcpyAsync(o->rows, rows.rows, n * 4, hipMemcpyDeviceToHost, h->stream));
+            if (o->states_bb) HIP_TRY(h, hipMemcpyAsync(o->states_bb, rows.states_bb, slots * 16, hipMemcpyDeviceToHost, h->stream));
+            if (o->pis) HIP_TRY(h, hipMemcpyAsync(o->pis, rows.pis, slots * 36, hipMemcpyDeviceToHost, h->stream));
+            if (o->vs) HIP_TRY(h, hipMemcpyAsync(o->vs, rows.vs, slots * 12, hipMemcpyDeviceToHost, h->stream));
+            if (o->actions) HIP_TRY(h, hipMemcpyAsync(o->actions, rows.actions, slots, hipMemcpyDeviceToHost, h->stream));
+            if (o->root_nodes) HIP_TRY(h, hipMemcpyAsync(o->root_nodes, rows.root_nodes, slots * 4, hipMemcpyDeviceToHost, h->stream));
+            if (o->final_kind) HIP_TRY(h, hipMemcpyAsync(o->final_kind, rows.final_kind, n, hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        float ms = 0.0f;
+        HIP_TRY(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+        h->last_kernel_ms = kernel_ms + ms;
+        h->last_launches = launches + 1;
+    }
     HIP_TRY(h, hipMemcpyAsync(rewards, out.rewards, n * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipMemcpyAsync(plies, out.plies, n * 4, hipMemcpyDeviceToHost, h->stream));
     if (moves) HIP_TRY(h, hipMemcpyAsync(moves, out.moves, n * MATCH_T, hipMemcpyDeviceToHost, h->stream));
@@ -1923,6 +1992,59 @@ int syn_tournament_run(syn_engine* h, const syn_match_side* players, int n_playe
         if (const int rc = check_match_side(h, who, &players[p], seeds != nullptr, S[p])) return rc;
     }
     return run_games(h, S.data(), K, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words, "tournament");
+}
+
+// Recorded games (include/synthesis_amd.h "Recorded games"): syn_tournament_run's arguments and refusals, network sides only, and the
+// loop in its recording form. The rows stay in the engine's self-play output buffers: for syn_replay_append_selfplay and
+// syn_selfplay_positions_device the call is a self-play launch of n_games games.
+int syn_games_run_recorded(syn_engine* h, const syn_match_side* players, int n_players, const int32_t* first, const int32_t* second,
+                           const uint64_t* start_my, const uint64_t* start_op, const uint64_t* seeds, int n_games,
+                           const syn_record_config* rec, float* rewards, int32_t* plies, uint8_t* moves, uint64_t* final_bb,
+                           uint64_t* rng_words, const syn_record_outputs* out) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    h->last_selfplay_games = -1;   // what a failed syn_selfplay_run leaves: nothing to compact until this call has ended without an error
+    if (n_games < 0 || (n_games > 0 && (!first || !second || !start_my || !start_op || !rewards || !plies)))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_games_run_recorded");
+    if (n_players < 1 || n_players > SYN_TOURNAMENT_MAX_PLAYERS)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: n_players %d is outside 1 .. %d", n_players, SYN_TOURNAMENT_MAX_PLAYERS);
+    if (!players) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: players is NULL");
+    if (!rec) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: the record configuration is NULL");
+    if (rec->value_target < SYN_VALUE_Z || rec->value_target > SYN_VALUE_Q_TO_Z)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: unknown value target %d", rec->value_target);
+    if (rec->random_actions_until < 0 || rec->sample_actions_until < 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: random_actions_until / sample_actions_until must be >= 0");
+    if (n_players < 64 && (rec->record_mask >> n_players) != 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: record_mask 0x%llx has a bit at or above n_players %d",
+                    (unsigned long long)rec->record_mask, n_players);
+    if (!seeds && (rec->random_actions_until > 0 || rec->sample_actions_until > 0))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_games_run_recorded: seeds is NULL, but actions are drawn (random_actions_until %d, "
+                                                 "sample_actions_until %d)", rec->random_actions_until, rec->sample_actions_until);
+    HIP_TRY(h, hipSetDevice(h->device));   // (selecting the device changes nothing of the engine)
+    // ---- everything that can refuse the call, before anything of the engine or the device changes
+    const int K = n_players;
+    std::vector<MatchSide> S((size_t)K);
+    for (int p = 0; p < K; p++) {
+        if (players[p].kind == SYN_MATCH_SIDE_BASELINE)
+            return fail(h, SYN_ERR_UNSUPPORTED, "syn_games_run_recorded: player #%d is a baseline side, whose search record has no target_pi / "
+                                                "target_q: recorded games take network sides only", p);
+        char who[24];
+        std::snprintf(who, sizeof(who), "recorded games' #%d", p);
+        if (const int rc = check_match_side(h, who, &players[p], seeds != nullptr, S[p])) return rc;
+    }
+    RecordCall R{};
+    R.rules.random_until = rec->random_actions_until;
+    R.rules.sample_until = rec->sample_actions_until;
+    R.rules.stop_when_solved = rec->stop_games_when_solved != 0;
+    R.mask = rec->record_mask;
+    R.value_target = rec->value_target;
+    R.vt_p = rec->value_target_p;
+    R.vt_from = rec->value_target_from;
+    R.vt_to = rec->value_target_to;
+    R.out = out;
+    const int rc = run_games(h, S.data(), K, first, second, start_my, start_op, seeds, n_games, rewards, plies, moves, final_bb, rng_words,
+                             "recorded games", &R);
+    if (rc == SYN_OK) h->last_selfplay_games = n_games;
+    return rc;
 }
 
 int syn_debug_tournament_regroup(syn_engine* h, const int32_t* keys, int n, int n_keys, int32_t* perm_out, int32_t* seg_out) {
@@ -3872,6 +3994,66 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
     if (status == SYN_ERR_CANCELLED && (size_t)tail[1] < sel_n)
         return fail(h, SYN_ERR_CANCELLED, "cancelled by syn_cancel: %zu of %zu selected rows were not searched and keep their old targets",
                     sel_n - (size_t)tail[1], sel_n);
+    return SYN_OK;
+}
+
+// syn_replay_select_positions (include/synthesis_amd.h "Recorded games"): syn_replay_reanalyse's selection alone — the same flags
+// kernel, scan and compaction on the same scratch layout — and a download of the selected positions, 16 bytes each. The buffer is read,
+// never written.
+int syn_replay_select_positions(syn_engine* h, uint64_t key, uint64_t threshold, int64_t before_gid, uint64_t* my_bb, uint64_t* op_bb,
+                                size_t capacity, size_t* n_selected, size_t* n_skipped) {
+    if (!h) return SYN_ERR_INVALID_ARGUMENT;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (n_selected) *n_selected = 0;
+    if (n_skipped) *n_skipped = 0;
+    if (!n_selected) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_select_positions: n_selected is NULL");
+    if (threshold > (1ull << 32))
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_select_positions: threshold %llu exceeds 2^32", (unsigned long long)threshold);
+    if (capacity && (!my_bb || !op_bb)) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_select_positions: my_bb or op_bb is NULL");
+    if (!h->d_replay || h->replay_cap == 0)
+        return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_select_positions: no replay buffer is reserved (syn_replay_reserve)");
+    const size_t n = h->replay_n;
+    if (n == 0 || threshold == 0) return SYN_OK;
+    const int ni = (int)n;
+    size_t tmp_scan = 0, tmp_sum = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(nullptr, tmp_sum, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    const ReanalyseLayout L = reanalyse_layout(n, std::max(tmp_scan, tmp_sum), 0);
+    if (const int rc = ensure_scratch(h, L.total)) return rc;
+    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
+    unsigned* const d_sel = reinterpret_cast<unsigned*>(base + L.sel);
+    unsigned* const d_skip = reinterpret_cast<unsigned*>(base + L.skip);
+    unsigned* const d_dst = reinterpret_cast<unsigned*>(base + L.dst);
+    unsigned long long* const d_job_my = reinterpret_cast<unsigned long long*>(base + L.job_my);
+    unsigned long long* const d_job_op = reinterpret_cast<unsigned long long*>(base + L.job_op);
+    unsigned* const d_job_row = reinterpret_cast<unsigned*>(base + L.job_row);
+    unsigned* const d_counts = reinterpret_cast<unsigned*>(base + L.counts);
+    void* const d_tmp = base + L.tmp;
+    const ReplaySections R = replay_sections(h->d_replay, h->replay_cap);
+    const dim3 block(256), grid_rows((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(reanalyse_flags_kernel, grid_rows, block, 0, h->stream, R.gid, R.my, R.op, ni, (unsigned long long)key ^ REANALYSE_TAG,
+                       (unsigned long long)threshold, (long long)before_gid, d_sel, d_skip);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_scan, d_sel, d_dst, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_skip, d_counts, ni, h->stream));
+    unsigned head[3] = {0, 0, 0};   // dst[n-1], sel[n-1], skipped
+    HIP_TRY(h, hipMemcpyAsync(&head[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&head[1], d_sel + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&head[2], d_counts, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    const size_t sel_n = (size_t)head[0] + head[1];
+    if (sel_n > n) return fail(h, SYN_ERR_HIP, "syn_replay_select_positions: %zu rows selected out of %zu", sel_n, n);
+    *n_selected = sel_n;
+    if (n_skipped) *n_skipped = head[2];
+    if (sel_n > capacity)
+        return fail(h, SYN_ERR_CAPACITY, "syn_replay_select_positions: %zu rows are selected, the arrays have room for %zu", sel_n, capacity);
+    if (sel_n == 0) return SYN_OK;
+    hipLaunchKernelGGL(reanalyse_compact_kernel, grid_rows, block, 0, h->stream, d_sel, d_dst, ni, (unsigned)n, R.my, R.op, d_job_my, d_job_op,
+                       d_job_row);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(my_bb, d_job_my, sel_n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(op_bb, d_job_op, sel_n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
 

@@ -8,7 +8,7 @@ import os
 
 import numpy as np
 
-from .config import CEngineConfig, CMctsConfig, CRolloutConfig, MCTSConfig, RolloutConfig
+from .config import CEngineConfig, CMctsConfig, CRecordConfig, CRolloutConfig, MCTSConfig, RecordConfig, RolloutConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 NUM_PARAMS = 30492  # Connect4Net: 63->128->96->64->48->12 (study-connect4/src/policies.rs:20-24)
@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "syn_dataset_set", "syn_dataset_get", "syn_dataset_evaluate", "syn_dataset_evaluate_arith", "syn_replay_set_holdout", "syn_dataset_counts",
     "syn_replay_reanalyse",
     "syn_trainer_set_state", "syn_state_digest",
+    "syn_games_run_recorded", "syn_replay_select_positions",
 ]
 TOURNAMENT_MAX_PLAYERS = 64  # SYN_TOURNAMENT_MAX_PLAYERS
 
@@ -106,6 +107,10 @@ class CReanalyseConfig(C.Structure):  # struct syn_reanalyse_config
 class CReanalyseStats(C.Structure):  # struct syn_reanalyse_stats
     _fields_ = [("rows", C.c_uint64), ("selected", C.c_uint64), ("skipped", C.c_uint64), ("moved", C.c_uint64),
                 ("chunks", C.c_uint32), ("launches", C.c_uint32)]
+
+
+class CRecordOutputs(C.Structure):  # struct syn_record_outputs
+    _fields_ = [(n, C.c_void_p) for n in ("rows", "states_bb", "pis", "vs", "actions", "root_nodes", "final_kind")]
 
 
 class CCounters(C.Structure):  # struct syn_counters
@@ -258,7 +263,11 @@ def load_library():
                            ("syn_replay_reanalyse", [C.c_void_p, C.POINTER(CMctsConfig), C.POINTER(CReanalyseConfig),
                                                      C.POINTER(CReanalyseStats), C.c_void_p, C.c_size_t]),
                            ("syn_trainer_set_state", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_longlong]),
-                           ("syn_state_digest", [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])):
+                           ("syn_state_digest", [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+                           ("syn_games_run_recorded", [C.c_void_p, C.POINTER(CMatchSide), C.c_int] + [C.c_void_p] * 5 + [
+                               C.c_int, C.POINTER(CRecordConfig)] + [C.c_void_p] * 5 + [C.POINTER(CRecordOutputs)]),
+                           ("syn_replay_select_positions", [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                            C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)])):
         if hasattr(lib, name) or not os.environ.get("SYNTHESIS_AMD_LIB"):
             getattr(lib, name).argtypes = argtypes
     _lib = lib
@@ -600,6 +609,47 @@ class Engine:
         self._check(self._lib.syn_tournament_run(self._h, arr, len(sides) if n_players is None else int(n_players), _p(fi), _p(se), _p(my),
                                                  _p(op), _p(sd), n, _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]),
                                                  _p(out["final_bb"]), _p(out["rng_words"])))
+        return out
+
+    def games_run_recorded(self, players, first, second, start_my, start_op, seeds=None, record=None, outputs=True):
+        """syn_games_run_recorded (include/synthesis_amd.h "Recorded games"): tournament_run's schedule of games, each played as
+        run_game — sample_action, the stop rule and the value target of `record` (a RecordConfig; RecordConfig.from_rollout(cfg, mask)
+        copies a rollout configuration's) — from (start_my[g], start_op[g]) on the generator of seeds[g], with training rows for the plies
+        of the players whose bit is set in record.record_mask. Network players only, deterministic search configurations only.
+        Returns tournament_run's dict (plies = all moves of a game) plus rows [n], and with outputs=True the padded rows in selfplay()'s
+        shapes: states [n, 63, 2] (also under selfplay()'s name states_bb), pis, vs, actions, root_nodes, final_kind. The rows replace
+        the last selfplay()'s in the engine: replay_append_selfplay(first_gid) / selfplay_positions_device compact them next."""
+        sides, keep = [], []
+        for p in players:
+            side, blob = self.match_side(p)
+            sides.append(side)
+            keep.append(blob)   # (the struct holds a raw pointer into it)
+        return self.games_run_recorded_c(sides, first, second, start_my, start_op, seeds, record, outputs)
+
+    def games_run_recorded_c(self, sides, first, second, start_my, start_op, seeds=None, record=None, outputs=True, n_players=None):
+        """games_run_recorded on CMatchSide structs as they are (the blobs they point to must stay alive for the call); n_players
+        overrides len(sides) (the refusal tests)"""
+        record = RecordConfig() if record is None else record
+        if not isinstance(record, RecordConfig):
+            raise ValueError(f"record must be a RecordConfig, got {type(record).__name__}")
+        fi = np.ascontiguousarray(first, dtype=np.int32).ravel()
+        se = np.ascontiguousarray(second, dtype=np.int32).ravel()
+        my, op, sd = self._match_starts(start_my, start_op, seeds, "first, second, start_my and start_op", (fi.size, se.size))
+        n = int(my.size)
+        arr = (CMatchSide * max(len(sides), 1))(*sides)
+        out = self._match_outputs(n)
+        out["rows"] = np.zeros(n, np.int32)
+        if outputs:
+            out.update(states=np.zeros((n, 63, 2), np.uint64), pis=np.zeros((n, 63, 9), np.float32), vs=np.zeros((n, 63, 3), np.float32),
+                       actions=np.zeros((n, 63), np.uint8), root_nodes=np.zeros((n, 63), np.uint32), final_kind=np.zeros(n, np.uint8))
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        ro = CRecordOutputs(ptr("rows"), ptr("states"), ptr("pis"), ptr("vs"), ptr("actions"), ptr("root_nodes"), ptr("final_kind"))
+        rc = record.to_c()
+        self._check(self._lib.syn_games_run_recorded(self._h, arr, len(sides) if n_players is None else int(n_players), _p(fi), _p(se), _p(my),
+                                                     _p(op), _p(sd), n, C.byref(rc), _p(out["rewards"]), _p(out["plies"]), _p(out["moves"]),
+                                                     _p(out["final_bb"]), _p(out["rng_words"]), C.byref(ro)))
+        if outputs:
+            out["states_bb"] = out["states"]
         return out
 
     @staticmethod
@@ -1032,6 +1082,25 @@ class Engine:
         if rows:
             out["selected_rows"] = sel[: out["selected"]]
         return out
+
+    def replay_select_positions(self, key, fraction=None, threshold=None, before_gid=None):
+        """syn_replay_select_positions: the positions of the buffer's rows that replay_reanalyse(key, fraction / threshold, before_gid)
+        would select (learner.reanalyse_flags is its host twin), in buffer order, downloaded alone; the buffer is untouched. Returns
+        dict(my, op, skipped)."""
+        if (fraction is None) == (threshold is None):
+            raise ValueError("give exactly one of fraction and threshold")
+        if threshold is None:
+            if not 0.0 <= float(fraction) <= 1.0:
+                raise ValueError(f"fraction must be in [0, 1], got {fraction!r}")
+            threshold = int(np.floor(float(fraction) * 4294967296.0))
+        if int(threshold) < 0:
+            raise ValueError("threshold must be >= 0")
+        args = (int(key) & 0xFFFFFFFFFFFFFFFF, int(threshold), (1 << 63) - 1 if before_gid is None else int(before_gid))
+        n, skipped = C.c_size_t(), C.c_size_t()
+        cap = self.replay_size()   # (host arrays for every row: the device sends the selected ones alone)
+        my, op = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        self._check(self._lib.syn_replay_select_positions(self._h, *args, _p(my), _p(op), cap, C.byref(n), C.byref(skipped)))
+        return dict(my=my[: int(n.value)].copy(), op=op[: int(n.value)].copy(), skipped=int(skipped.value))
 
     def replay_deduplicate_to_trainer(self, symmetry="none"):
         """De-duplicates the buffer on the device and makes the unique set the learner's data set (what replay_deduplicate +

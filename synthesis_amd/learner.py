@@ -82,6 +82,26 @@ def _reanalyse_key(seed, i_iter):
     return _sampler_key(seed, i_iter)
 
 
+EXPLORING_TAG = 0xE8F10A1D57A27500   # exploring starts: what separates their selection key from the same iteration's reanalysis key
+
+
+def _exploring_key(seed, i_iter):
+    """exploring_starts > 0: the selection key of iteration i_iter's start positions (0-based) — _sampler_key's number under a tag of its
+    own, so that a run with reanalysis and exploring starts draws the two sets of rows independently"""
+    return _sampler_key(seed, i_iter) ^ EXPLORING_TAG
+
+
+def exploring_threshold(n_games, rows_in_buffer):
+    """The selection threshold that draws about n_games of rows_in_buffer rows: min(2^32 - 1, (n_games * 2^32) // rows_in_buffer), in
+    integers (0 for an empty buffer: nothing to start from)"""
+    n_games, rows_in_buffer = int(n_games), int(rows_in_buffer)
+    if n_games < 0 or rows_in_buffer < 0:
+        raise ValueError("exploring_threshold: need n_games >= 0 and rows_in_buffer >= 0")
+    if rows_in_buffer == 0:
+        return 0
+    return min((1 << 32) - 1, (n_games << 32) // rows_in_buffer)
+
+
 def searchable_positions(my, op):
     """The positions a search takes as a root: Engine.mcts_search's check (disjoint boards inside the 63 cells — bit index row + 7 * col —
     every column filled from the bottom without holes, at least one free column) and neither side with four in a row (connect4.rs:70-83:
@@ -130,6 +150,9 @@ STATE_FORMAT_VERSION = 1
 # buffer is stored as arrays, so a run saved with replay="host" may continue with replay="device" and the reverse)
 FINGERPRINT_FIELDS = ("net", "seed", "precision", "batch_mode", "sampler", "flip", "symmetry", "holdout", "reanalyse",
                       "reanalyse_explores", "reanalyse_value_mix", "lr_schedule", "hyper", "network_arithmetic", "world")
+# optional fields: name -> the value a fingerprint without the field has. A field is written only when it differs from that value, so
+# the files of runs that do not use it are the files they always were
+FINGERPRINT_OPTIONAL = dict(exploring_starts=0.0)
 _HYPER_DEFAULTS = dict(weight_decay=1e-6, policy_weight=1.0, value_weight=1.0, beta1=0.9, beta2=0.999, eps=1e-8)   # Engine.trainer_init*
 # every array of the file: name -> (dtype, trailing shape); `torch_generator` is present only with sampler="torch"
 _STATE_ARRAYS = dict(format_version=(np.int64, ()), fingerprint=(np.uint8, (-1,)), iterations_done=(np.int64, ()), games_played=(np.int64, ()),
@@ -149,7 +172,9 @@ def _normal_fingerprint(fp):
     if missing:
         raise ValueError(f"a run's fingerprint needs the fields {list(FINGERPRINT_FIELDS)}; missing: {missing}")
     plain = lambda x: x.item() if isinstance(x, np.generic) else x
-    return json.loads(json.dumps({k: fp[k] for k in FINGERPRINT_FIELDS}, default=plain, sort_keys=True))
+    out = {k: fp[k] for k in FINGERPRINT_FIELDS}
+    out.update({k: fp[k] for k, default in FINGERPRINT_OPTIONAL.items() if k in fp and fp[k] != default})
+    return json.loads(json.dumps(out, default=plain, sort_keys=True))
 
 
 def pack_state(state):
@@ -246,11 +271,15 @@ def read_state_file(path):
 
 
 def check_fingerprint(saved, current, where="state file"):
-    """Raises ValueError naming the first field of FINGERPRINT_FIELDS in which the run that wrote the file and this loop differ."""
+    """Raises ValueError naming the first field of FINGERPRINT_FIELDS, then of FINGERPRINT_OPTIONAL (a missing one reads as its default),
+    in which the run that wrote the file and this loop differ."""
     saved, current = _normal_fingerprint(saved), _normal_fingerprint(current)
     for k in FINGERPRINT_FIELDS:
         if saved[k] != current[k]:
             raise ValueError(f"{where}: written by a run with {k}={saved[k]!r}, this loop has {k}={current[k]!r}")
+    for k, default in FINGERPRINT_OPTIONAL.items():
+        if saved.get(k, default) != current.get(k, default):
+            raise ValueError(f"{where}: written by a run with {k}={saved.get(k, default)!r}, this loop has {k}={current.get(k, default)!r}")
 
 
 class LearningLoop:
@@ -310,6 +339,21 @@ class LearningLoop:
                  selected rows + assignment into the host buffer — same bits. The record gains `reanalysed`, `reanalyse_moved` (rows whose
                  arg-max column of pi changed) and a `reanalyse` phase time. Not measured: any training run with reanalysis, and more than
                  one rank (the other ranks idle during the learner's reanalysis).
+    exploring_starts  0.0 (default: every bit and every record as without the argument) | a fraction F of an iteration's GAMES in (0, 1):
+                 from the second iteration on, n_t = floor(F * games_per_train) of the games are replaced by games that start at stored
+                 positions. The ranks share games_per_train - n_t ordinary self-play games; then the learner's rank takes ALL rows of
+                 the buffer as it stood before the iteration that "Reanalyse"'s selection draws under `_exploring_key(seed, iteration)`,
+                 threshold `exploring_threshold(n_t, rows in the buffer)` (about n_t rows, not exactly) and before_gid = the iteration's
+                 first game id, in buffer order, and plays one recorded game from each (Engine.games_run_recorded: one player, the current
+                 weights, the iteration's cfg unchanged, so a game's first move from a stored position is the configuration's random
+                 move; game j on the generator of seed + its game id). Their rows are appended after the ordinary games' with the game
+                 ids that follow them (the iteration's id games_per_train - n_t onwards; when more than n_t rows are drawn, the surplus
+                 games carry ids of the next iteration's range — ids only order the keep-window and the holdout split). replay="host"
+                 selects with reanalyse_flags and takes the padded rows; replay="device" uses Engine.replay_select_positions and
+                 replay_append_selfplay — same buffer, weights and records. The record gains `exploring_games`, `exploring_rows` and an
+                 `exploring` phase time. The run's fingerprint carries the field only when it is non-zero (a file without it reads as
+                 0.0). cfg must be a deterministic search configuration. Not measured: whether exploring starts train a stronger player;
+                 more than one rank (the other ranks idle while the learner's rank plays the exploring games).
     digests      False (default: every record as without the argument) | True: the learner's record gains `digests` = dict(trainer,
                  replay, train_data, and with a holdout eval_data) — the 64-bit fingerprints of that state (Engine.state_digest;
                  include/synthesis_amd.h "State digests") as 16-digit hex strings, taken after the iteration's epochs and before the
@@ -333,7 +377,8 @@ class LearningLoop:
 
     def __init__(self, engine, net, blob, dist=None, device=0, lr_schedule=((1, 1e-3),), seed=0, precision="f32", logs_dir=None, sampler="numpy",
                  network_arithmetic="f32", replay="host", symmetry="none", batch_mode="chained", flip=False, holdout=0.0,
-                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, digests=False, holdout_arith=("f32",), **hyper):
+                 reanalyse=0.0, reanalyse_explores=None, reanalyse_value_mix=0.0, digests=False, holdout_arith=("f32",), exploring_starts=0.0,
+                 **hyper):
         holdout_arith = (holdout_arith,) if isinstance(holdout_arith, str) else tuple(holdout_arith)
         for a in holdout_arith:
             if a not in HOLDOUT_ARITHMETICS:
@@ -341,6 +386,8 @@ class LearningLoop:
             if a == "bf16" and net != "conv":
                 raise ValueError("holdout_arith 'bf16' exists for net='conv' only (the conv learner's bf16 precision)")
         _real = lambda x: not isinstance(x, bool) and isinstance(x, (int, float, np.floating, np.integer))
+        if not _real(exploring_starts) or not 0.0 <= float(exploring_starts) < 1.0:
+            raise ValueError(f"exploring_starts must be a fraction of an iteration's games in [0, 1), got {exploring_starts!r}")
         if not _real(reanalyse) or not 0.0 <= float(reanalyse) <= 1.0:
             raise ValueError(f"reanalyse must be a fraction of rows in [0, 1], got {reanalyse!r}")
         if reanalyse_explores is not None and (isinstance(reanalyse_explores, bool) or not isinstance(reanalyse_explores, (int, np.integer))
@@ -411,6 +458,7 @@ class LearningLoop:
         self._reanalyse_threshold = int(np.floor(self.reanalyse * 4294967296.0))
         self.reanalyse_explores = None if reanalyse_explores is None else int(reanalyse_explores)
         self.reanalyse_value_mix = float(reanalyse_value_mix)
+        self.exploring_starts = float(exploring_starts)
         self.logs_dir = logs_dir if self.rank == 0 else None
         if self.logs_dir:
             self._save_model(0)
@@ -430,10 +478,13 @@ class LearningLoop:
     # ---- stopping and continuing a run (save_state / restore_state) and the per-iteration fingerprints (digests=True)
     def fingerprint(self):
         """What identifies this run (FINGERPRINT_FIELDS): restore_state continues a file only when every field agrees"""
-        return dict(net=self.net, seed=self.seed, precision=self.precision, batch_mode=self.batch_mode, sampler=self.sampler, flip=self.flip,
-                    symmetry=self.symmetry, holdout=self.holdout, reanalyse=self.reanalyse, reanalyse_explores=self.reanalyse_explores,
-                    reanalyse_value_mix=self.reanalyse_value_mix, lr_schedule=[[int(i), float(v)] for i, v in self.lr_schedule],
-                    hyper={k: float(v) for k, v in sorted(self.hyper.items())}, network_arithmetic=self.network_arithmetic, world=self.world)
+        fp = dict(net=self.net, seed=self.seed, precision=self.precision, batch_mode=self.batch_mode, sampler=self.sampler, flip=self.flip,
+                  symmetry=self.symmetry, holdout=self.holdout, reanalyse=self.reanalyse, reanalyse_explores=self.reanalyse_explores,
+                  reanalyse_value_mix=self.reanalyse_value_mix, lr_schedule=[[int(i), float(v)] for i, v in self.lr_schedule],
+                  hyper={k: float(v) for k, v in sorted(self.hyper.items())}, network_arithmetic=self.network_arithmetic, world=self.world)
+        if self.exploring_starts != FINGERPRINT_OPTIONAL["exploring_starts"]:   # (an optional field: present only when it is used)
+            fp["exploring_starts"] = self.exploring_starts
+        return fp
 
     def _replay_arrays(self):
         """The learner's rank: the buffer's five arrays (my, op, gid, pi, v), from the engine (replay="device") or from self.R"""
@@ -668,10 +719,15 @@ class LearningLoop:
         """`iteration` with the replay buffer in the engine's device memory (replay="device"): same games, same record."""
         it = self.iterations_done
         t0 = time.perf_counter()
-        off, count = shard_games(games_per_train, self.rank, self.world)
+        n_t = self._exploring_games(it, games_per_train)
+        off, count = shard_games(games_per_train - n_t, self.rank, self.world)
         first = it * games_per_train + off
+        starts = None
+        if n_t and self.rank == 0:   # the buffer as it stood before the iteration
+            starts = self.engine.replay_select_positions(_exploring_key(self.seed, it), before_gid=it * games_per_train,
+                                                         threshold=exploring_threshold(n_t, self.engine.replay_size()))
         if self.rank == 0:   # (grows, keeping the contents, when an iteration's shape changes)
-            want = (int(games_to_keep) + int(games_per_train)) * 63
+            want = (int(games_to_keep) + int(games_per_train) + (max(0, int(starts["my"].size) - n_t) if starts else 0)) * 63
             if want > self._replay_reserved:
                 self.engine.replay_reserve(want)
                 self._replay_reserved = want
@@ -685,6 +741,14 @@ class LearningLoop:
         else:
             self.engine.replay_append_selfplay(first)
         t_gather = time.perf_counter() - t1 - self._last_gather_wait
+        t_ex = time.perf_counter()
+        exploring = (0, 0)
+        if starts is not None and starts["my"].size:
+            ex_first = it * games_per_train + (games_per_train - n_t)
+            ex = self._play_exploring(cfg, starts["my"], starts["op"], ex_first, outputs=False)
+            assert self.engine.replay_append_selfplay(ex_first) == int(ex["rows"].sum())
+            exploring = (int(ex["rows"].size), int(ex["rows"].sum()))
+        t_ex = time.perf_counter() - t_ex
         self.games_played += games_per_train
         lr = _lr_at(self.lr_schedule, it)
         rec = dict(iteration=it + 1, lr=lr, games=int(games_per_train), games_this_rank=int(count),
@@ -720,6 +784,8 @@ class LearningLoop:
                 rec["unique_canonical"] = n_canonical
             if self._reanalyse_threshold:
                 rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
+            if self.exploring_starts:
+                rec.update(exploring_games=exploring[0], exploring_rows=exploring[1])
             if self.digests:
                 rec["digests"] = self.state_digests()
             if self.logs_dir:
@@ -734,7 +800,31 @@ class LearningLoop:
         self._finish_iteration(rec, t0, t_play, t_gather, t_dedup, t_train)
         if self.rank == 0 and self._reanalyse_threshold:
             rec["seconds"]["reanalyse"] = round(t_re, 4)
+        if self.rank == 0 and self.exploring_starts:
+            rec["seconds"]["exploring"] = round(t_ex, 4)
         return rec
+
+    def _exploring_games(self, it, games_per_train):
+        """How many of iteration `it`'s games (0-based) are replaced by games from stored positions: floor(exploring_starts *
+        games_per_train) from the second iteration on — every rank computes it, the ordinary self-play shares the rest"""
+        if not self.exploring_starts or it == 0:
+            return 0
+        return int(np.floor(self.exploring_starts * int(games_per_train)))
+
+    def _play_exploring(self, cfg, start_my, start_op, first_gid, outputs):
+        """The learner's rank: one recorded game per start position (Engine.games_run_recorded), the current weights on both sides in the
+        engine's arithmetic, the iteration's cfg unchanged — a game's first move from a stored position is the configuration's random
+        move — and game j on the generator of seed + first_gid + j, as self-play seeds game first_gid + j. A cfg whose search draws
+        random numbers (Fpu.Func, Dirichlet noise) is refused by the engine: recorded games take deterministic searches only."""
+        from .config import RecordConfig
+        from .match import Player
+
+        n = int(start_my.size)
+        me = Player("current", int(cfg.num_explores), cfg.mcts_cfg, action=cfg.action, weights=self.weights)
+        seeds = np.array([(self.seed + int(first_gid) + j) & _M64 for j in range(n)], np.uint64)
+        zeros = np.zeros(n, np.int32)
+        return self.engine.games_run_recorded([me], zeros, zeros, start_my, start_op, seeds, record=RecordConfig.from_rollout(cfg, 1),
+                                              outputs=outputs)
 
     def _holdout_metrics(self, n_eval, n_unseen, arith="f32"):
         """The trainer's current weights on the evaluation set: dict(all=..., unseen=...) of dict(rows, mean_pi, mean_v, pi_acc, v_acc)"""
@@ -855,8 +945,15 @@ class LearningLoop:
         it = self.iterations_done
         t0 = time.perf_counter()
         # ---- gather_experience: this rank's share of the new games; global game index = seed offset, never reused
-        off, count = shard_games(games_per_train, self.rank, self.world)
+        n_t = self._exploring_games(it, games_per_train)
+        off, count = shard_games(games_per_train - n_t, self.rank, self.world)
         first = it * games_per_train + off
+        starts = None
+        if n_t and self.rank == 0:   # the buffer as it stood before the iteration
+            R = self.R
+            sel = reanalyse_flags(_exploring_key(self.seed, it), exploring_threshold(n_t, R["my"].size), it * games_per_train, R["gid"],
+                                  R["my"], R["op"])
+            starts = dict(my=R["my"][sel].copy(), op=R["op"][sel].copy())
         sp = self.engine.selfplay(cfg, base_seed=self.seed, n_games=count, first_game=first)
         t_play = time.perf_counter() - t0
         n = sp["plies"]
@@ -868,6 +965,17 @@ class LearningLoop:
         if self.dist is not None:
             new = self._gather_positions(new)
         t_gather = time.perf_counter() - t1 - self._last_gather_wait   # pack + gather + unpack, without the wait for the slowest rank
+        t_ex = time.perf_counter()
+        exploring = (0, 0)
+        if starts is not None and starts["my"].size:
+            ex_first = it * games_per_train + (games_per_train - n_t)
+            ex = self._play_exploring(cfg, starts["my"], starts["op"], ex_first, outputs=True)
+            emask = np.arange(63)[None, :] < ex["rows"][:, None]
+            extra = dict(my=ex["states"][..., 0][emask], op=ex["states"][..., 1][emask], pi=ex["pis"][emask], v=ex["vs"][emask],
+                         gid=(ex_first + np.arange(ex["rows"].size))[:, None].repeat(63, 1)[emask])
+            new = {k: np.concatenate([new[k], extra[k]]) for k in extra}
+            exploring = (int(ex["rows"].size), int(ex["rows"].sum()))
+        t_ex = time.perf_counter() - t_ex
         self.games_played += games_per_train
         lr = _lr_at(self.lr_schedule, it)
         rec = dict(iteration=it + 1, lr=lr, games=int(games_per_train), games_this_rank=int(count),
@@ -909,6 +1017,8 @@ class LearningLoop:
                 rec["unique_canonical"] = D["canonical"]
             if self._reanalyse_threshold:
                 rec.update(reanalysed=reanalysed[0], reanalyse_moved=reanalysed[1])
+            if self.exploring_starts:
+                rec.update(exploring_games=exploring[0], exploring_rows=exploring[1])
             if self.digests:
                 rec["digests"] = self.state_digests()
             if self.logs_dir:   # alpha_zero.rs:97-100
@@ -936,6 +1046,8 @@ class LearningLoop:
                               broadcast=round(t_bcast, 4), total=round(time.perf_counter() - t0, 4))
         if self.rank == 0 and self._reanalyse_threshold:
             rec["seconds"]["reanalyse"] = round(t_re, 4)
+        if self.rank == 0 and self.exploring_starts:
+            rec["seconds"]["exploring"] = round(t_ex, 4)
         return rec
 
 
