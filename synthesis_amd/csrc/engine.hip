@@ -45,6 +45,7 @@
 #include "digest_kernels.cuh"
 #include "lane_instances.h"
 #include "launch_plan.hpp"
+#include "position_layout.hpp"
 #include "free_kernel.cuh"
 #ifdef SYN_DEBUG_SHAPES
 #include "pool_kernel.cuh"   // round 6's measured dead end (trees unbound from the lanes): a debug shape like the two above
@@ -200,8 +201,7 @@ struct syn_engine {
         unsigned* d_tsync = nullptr;  // its arrival counter and status word
         float* d_tsnap = nullptr;     // snapshot of [w][m][v][fwd image][transposed image] taken before an epoch launch (restored if it aborts)
         float* d_cxbuf = nullptr;     // Connect4ConvNet learner on four workgroups: the exchange buffer (train_conv_mfma.cuh ConvMwGeom)
-        void* d_train_data = nullptr;  // syn_train_set_data: [my u64 n][op u64 n][pi 9 f32 n][v 3 f32 n] (TrainSections)
-        size_t train_data_cap = 0, train_data_n = 0;
+        PositionRows data;  // syn_train_set_data: the learner's data set
         long long train_step = 0;
         DevTrainHyper train_hp{};
         bool has_trainer = false;
@@ -220,11 +220,10 @@ struct syn_engine {
         float* d_micro_rows = nullptr;  // the block buffer: row j = [g_j][l_j] of micro-batch j (MicroPlan::row_stride); grown on demand
         size_t micro_rows_bytes = 0;
     } learner;
-    // The evaluation set (syn_dataset_set / syn_dataset_get / syn_dataset_evaluate): a second data set in the learner's TrainSections
-    // layout that no trainer call reads or writes, and the image buffer a syn_dataset_evaluate with a blob of its own builds into.
+    // The evaluation set (syn_dataset_set / syn_dataset_get / syn_dataset_evaluate): a second data set in the learner's layout that
+    // no trainer call reads or writes, and the image buffer a syn_dataset_evaluate with a blob of its own builds into.
     struct EvalSet {
-        void* d_data = nullptr;
-        size_t cap = 0, n = 0;
+        PositionRows rows;
         size_t n_unseen = 0;      // rows [0, n_unseen): states that are not in the learner's data set (syn_dataset_counts); syn_dataset_set: n
         uint64_t holdout_key = 0, holdout_threshold = 0;   // syn_replay_set_holdout; threshold 0 = nothing is held out
         float* d_img = nullptr;   // sized for the larger of Connect4Net's f32 image and Connect4ConvNet's parameters; allocated on first use
@@ -285,17 +284,6 @@ static int ensure_scratch(syn_engine* h, size_t bytes) {
     h->scratch_bytes = want;
     return SYN_OK;
 }
-
-// One device allocation carved into sections, each 256-byte aligned: take() returns the next section's byte offset, `at` ends as the total.
-static size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-struct Carve {
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t o = at;
-        at += align256(bytes);
-        return o;
-    }
-};
 
 // The search kernels' error word (EngineParams::error) as a call's refusal: 0 = none (SYN_OK), 2 = a tree's node blocks ran out, anything
 // else = a bounded spin gave up. `suffix` is appended to the capacity message.
@@ -664,9 +652,9 @@ int syn_engine_destroy(syn_engine* h) {
     hipFree(h->d_job_next);
     hipFree(h->d_path);
     hipFree(h->d_vw);
-    hipFree(h->learner.d_train_data);
+    hipFree(h->learner.data.d);
     hipFree(h->learner.d_micro_rows);
-    hipFree(h->evalset.d_data);
+    hipFree(h->evalset.rows.d);
     hipFree(h->evalset.d_img);
     hipFree(h->evalset.d_img16);
     hipFree(h->d_replay);
@@ -2517,7 +2505,7 @@ static bool learner_self_check(syn_engine* h, const LearnerStart& start, bool* s
     }
     L.conv_mw_force = -1;
     L.train_step = 0;
-    L.train_data_n = 0;   // the synthetic batch replaced whatever syn_train_set_data had uploaded: the caller uploads again (once per engine)
+    L.data.n = 0;   // the synthetic batch replaced whatever syn_train_set_data had uploaded: the caller uploads again (once per engine)
     *same_bits = ok && std::memcmp(w[0].data(), w[1].data(), nw * 4) == 0;
     return ok;
 }
@@ -2638,64 +2626,28 @@ int syn_trainer_get_batch_mode(syn_engine* h, int* mode, int* max_workgroups, in
 }
 
 // ------------------------------------------------------------------------------------------------ learner step
-// The learner's data set (d_train_data) and every staged batch: sections my | op | pi | v of n positions each, 64 bytes a position.
-struct TrainSections {
-    unsigned long long* my;
-    unsigned long long* op;
-    float* pi;
-    float* v;
-};
-static TrainSections train_sections(void* base, size_t n) {
-    unsigned char* b = static_cast<unsigned char*>(base);
-    return {reinterpret_cast<unsigned long long*>(b), reinterpret_cast<unsigned long long*>(b + n * 8),
-            reinterpret_cast<float*>(b + n * 16), reinterpret_cast<float*>(b + n * 52)};
-}
-// the same four arrays read-only: a caller's batch, or sections that are only read
-struct TrainSource {
-    const unsigned long long* my;
-    const unsigned long long* op;
-    const float* pi;
-    const float* v;
-    TrainSource(const unsigned long long* my_, const unsigned long long* op_, const float* pi_, const float* v_) : my(my_), op(op_), pi(pi_), v(v_) {}
-    TrainSource(const TrainSections& s) : my(s.my), op(s.op), pi(s.pi), v(s.v) {}
-};
-static TrainSource train_source(const uint64_t* my, const uint64_t* op, const float* pi, const float* v) {
-    return {reinterpret_cast<const unsigned long long*>(my), reinterpret_cast<const unsigned long long*>(op), pi, v};
-}
-// n positions from `src` into the sections `dst` on h->stream
-static int train_copy(syn_engine* h, const TrainSections& dst, const TrainSource& src, size_t n, hipMemcpyKind kind) {
-    HIP_TRY(h, hipMemcpyAsync(dst.my, src.my, n * 8, kind, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dst.op, src.op, n * 8, kind, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dst.pi, src.pi, n * 36, kind, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(dst.v, src.v, n * 12, kind, h->stream));
+// Stored positions (position_layout.hpp): the replay buffer is columns_at(.., capacity, true); the learner's data set, the evaluation
+// set and every staged batch are columns_at(.., n, false), 64 bytes a position.
+static_assert(sizeof(DevSearchResult) == SEARCH_RESULT_BYTES, "position_layout.hpp restates engine_kernels.cuh's search result");
+// n positions from `src` to `dst` on h->stream: one block copy per column, a column that is null on either side is skipped
+static int copy_positions(syn_engine* h, const PositionColumns& dst, const PositionColumns& src, size_t n, hipMemcpyKind kind) {
+    if (n == 0) return SYN_OK;
+    if (dst.my && src.my) HIP_TRY(h, hipMemcpyAsync(dst.my, src.my, n * POS_BOARD_BYTES, kind, h->stream));
+    if (dst.op && src.op) HIP_TRY(h, hipMemcpyAsync(dst.op, src.op, n * POS_BOARD_BYTES, kind, h->stream));
+    if (dst.gid && src.gid) HIP_TRY(h, hipMemcpyAsync(dst.gid, src.gid, n * POS_GID_BYTES, kind, h->stream));
+    if (dst.pi && src.pi) HIP_TRY(h, hipMemcpyAsync(dst.pi, src.pi, n * POS_PI_BYTES, kind, h->stream));
+    if (dst.v && src.v) HIP_TRY(h, hipMemcpyAsync(dst.v, src.v, n * POS_V_BYTES, kind, h->stream));
     return SYN_OK;
 }
-// Room for `need` positions in d_train_data. A buffer that has to grow is allocated for `grow_to` >= need positions (the caller's
-// growth policy) once the stream's work on the old one is done; the data set it held is gone then.
-static int ensure_train_data(syn_engine* h, size_t need, size_t grow_to) {
-    auto& L = h->learner;
-    if (need <= L.train_data_cap) return SYN_OK;
+// Room for `need` positions in a data set of the engine's. A buffer that has to grow is allocated for `grow_to` >= need positions (the
+// caller's growth policy) once the stream's work on the old one is done; the data set it held is gone then (R.n == 0).
+static int ensure_position_rows(syn_engine* h, PositionRows& R, size_t need, size_t grow_to) {
+    if (need <= R.cap) return SYN_OK;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(L.d_train_data);
-    L.d_train_data = nullptr;
-    L.train_data_cap = 0;
-    L.train_data_n = 0;
-    HIP_TRY(h, hipMalloc(&L.d_train_data, grow_to * 64));
-    L.train_data_cap = grow_to;
-    return SYN_OK;
-}
-
-// the same for the evaluation set (syn_engine::EvalSet)
-static int ensure_eval_data(syn_engine* h, size_t need, size_t grow_to) {
-    auto& E = h->evalset;
-    if (need <= E.cap) return SYN_OK;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    (void)hipFree(E.d_data);
-    E.d_data = nullptr;
-    E.cap = 0;
-    E.n = E.n_unseen = 0;
-    HIP_TRY(h, hipMalloc(&E.d_data, grow_to * 64));
-    E.cap = grow_to;
+    (void)hipFree(R.d);
+    R = PositionRows{};
+    HIP_TRY(h, hipMalloc(&R.d, grow_to * POS_ROW_BYTES));
+    R.cap = grow_to;
     return SYN_OK;
 }
 
@@ -2715,7 +2667,7 @@ static int check_micro_batch(syn_engine* h, int batch) {
 }
 
 // The micro-batch gradient (train_micro.cuh): the blocks kernel over plan_micro_grads' grid, then the reduce, both on `st`.
-static int launch_grads_micro(syn_engine* h, hipStream_t st, const TrainSource& b, int batch, float* d_grads, float* d_losses) {
+static int launch_grads_micro(syn_engine* h, hipStream_t st, const PositionColumns& b, int batch, float* d_grads, float* d_losses) {
     auto& L = h->learner;
     const int rc = check_micro_batch(h, batch);
     if (rc != SYN_OK) return rc;
@@ -2751,7 +2703,7 @@ static int launch_grads_micro(syn_engine* h, hipStream_t st, const TrainSource& 
 }
 
 // (the *_enqueue entry points run the step on the caller's stream `st` — which may be the null stream: torch's default)
-static int launch_grads(syn_engine* h, hipStream_t st, const TrainSource& b, int batch, float* d_grads, float* d_losses = nullptr) {
+static int launch_grads(syn_engine* h, hipStream_t st, const PositionColumns& b, int batch, float* d_grads, float* d_losses = nullptr) {
     auto& L = h->learner;
     if (!d_losses) d_losses = L.d_tloss;
     if (L.batch_mode == SYN_TRAIN_BATCH_MICRO) return launch_grads_micro(h, st, b, batch, d_grads, d_losses);
@@ -2817,7 +2769,7 @@ int syn_train_gradients_device(syn_engine* h, const uint64_t* d_my_bb, const uin
     if (batch < 1 || !d_my_bb || !d_op_bb || !d_target_pi || !d_target_v || !d_grads)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_gradients_device");
     HIP_TRY(h, hipSetDevice(h->device));
-    rc = launch_grads(h, h->stream, train_source(d_my_bb, d_op_bb, d_target_pi, d_target_v), batch, d_grads);
+    rc = launch_grads(h, h->stream, columns_of(d_my_bb, d_op_bb, nullptr, d_target_pi, d_target_v), batch, d_grads);
     if (rc != SYN_OK) return rc;
     if (losses) HIP_TRY(h, hipMemcpyAsync(losses, h->learner.d_tloss, 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -2845,7 +2797,7 @@ int syn_train_gradients_enqueue(syn_engine* h, void* stream, const uint64_t* d_m
     if (batch < 1 || !d_my_bb || !d_op_bb || !d_target_pi || !d_target_v || !d_grads)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_gradients_enqueue");
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_grads(h, static_cast<hipStream_t>(stream), train_source(d_my_bb, d_op_bb, d_target_pi, d_target_v), batch, d_grads, d_losses);
+    return launch_grads(h, static_cast<hipStream_t>(stream), columns_of(d_my_bb, d_op_bb, nullptr, d_target_pi, d_target_v), batch, d_grads, d_losses);
 }
 
 int syn_train_apply_enqueue(syn_engine* h, void* stream, const float* d_grads, float lr, float grad_scale) {
@@ -2866,10 +2818,10 @@ int syn_train_step(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, 
     HIP_TRY(h, hipSetDevice(h->device));
     auto& L = h->learner;
     const size_t nb = (size_t)batch;
-    rc = ensure_scratch(h, nb * 64 + 256);
+    rc = ensure_scratch(h, nb * POS_ROW_BYTES + 256);
     if (rc != SYN_OK) return rc;
-    const TrainSections staged = train_sections(h->d_scratch, nb);
-    rc = train_copy(h, staged, train_source(my_bb, op_bb, target_pi, target_v), nb, hipMemcpyHostToDevice);
+    const PositionColumns staged = columns_at(h->d_scratch, nb, false);
+    rc = copy_positions(h, staged, columns_of(my_bb, op_bb, nullptr, target_pi, target_v), nb, hipMemcpyHostToDevice);
     if (rc != SYN_OK) return rc;
     rc = launch_grads(h, h->stream, staged, batch, L.d_tgrad);
     if (rc != SYN_OK) return rc;
@@ -2888,12 +2840,12 @@ int syn_train_set_data(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_
     if (n < 1 || n > 0x7FFFFFFFu || !my_bb || !op_bb || !target_pi || !target_v)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_set_data");
     HIP_TRY(h, hipSetDevice(h->device));
-    rc = ensure_train_data(h, n, n);
+    rc = ensure_position_rows(h, h->learner.data, n, n);
     if (rc != SYN_OK) return rc;
-    rc = train_copy(h, train_sections(h->learner.d_train_data, n), train_source(my_bb, op_bb, target_pi, target_v), n, hipMemcpyHostToDevice);
+    rc = copy_positions(h, columns_at(h->learner.data.d, n, false), columns_of(my_bb, op_bb, nullptr, target_pi, target_v), n, hipMemcpyHostToDevice);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    h->learner.train_data_n = n;
+    h->learner.data.n = n;
     return SYN_OK;
 }
 
@@ -2902,7 +2854,7 @@ int syn_train_set_data(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_
 struct EpochStage {
     int* d_perm;
     float* d_losses;
-    TrainSections batches;
+    PositionColumns batches;
     float* d_adam;
     unsigned long long* d_stamps;
 };
@@ -2910,7 +2862,7 @@ struct EpochStage {
 static int check_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch) {
     const int rc = learner_check(h);
     if (rc != SYN_OK) return rc;
-    const size_t n = h->learner.train_data_n, ni = n_steps * (size_t)batch;
+    const size_t n = h->learner.data.n, ni = n_steps * (size_t)batch;
     if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "call syn_train_set_data first");
     if (batch < 1 || (n_steps > 0 && !perm) || ni > 0x7FFFFFFFu) return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_train_epoch");
     if (n_steps == 0) return SYN_OK;
@@ -2927,7 +2879,7 @@ struct EpochStageLayout {
 };
 static EpochStageLayout epoch_stage_layout(size_t n_steps, int batch) {
     const size_t ni = n_steps * (size_t)batch;
-    return {(ni * 4 + 255) & ~(size_t)255, (n_steps * 8 + 255) & ~(size_t)255, (ni * 64 + 255) & ~(size_t)255};
+    return {(ni * 4 + 255) & ~(size_t)255, (n_steps * 8 + 255) & ~(size_t)255, (ni * POS_ROW_BYTES + 255) & ~(size_t)255};
 }
 // the stage's pointers into the scratch at `base` (derived after ensure_scratch: the buffer may have moved)
 static EpochStage epoch_stage_at(void* base, const EpochStageLayout& lay, size_t ni) {
@@ -2935,14 +2887,14 @@ static EpochStage epoch_stage_at(void* base, const EpochStageLayout& lay, size_t
     EpochStage st{};
     st.d_perm = reinterpret_cast<int*>(sc);
     st.d_losses = reinterpret_cast<float*>(sc + lay.perm_bytes);
-    st.batches = train_sections(sc + lay.perm_bytes + lay.loss_bytes, ni);
+    st.batches = columns_at(sc + lay.perm_bytes + lay.loss_bytes, ni, false);
     st.d_adam = reinterpret_cast<float*>(sc + lay.perm_bytes + lay.loss_bytes + lay.batch_bytes);
     st.d_stamps = reinterpret_cast<unsigned long long*>(sc + lay.perm_bytes + lay.loss_bytes + lay.batch_bytes + lay.loss_bytes);
     return st;
 }
 // "stage the step-ordered batches" from the caller's permutation: lays the scratch out and gathers the epoch's batches
 static int stage_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int batch, EpochStage* st) {
-    const size_t n = h->learner.train_data_n, ni = n_steps * (size_t)batch;
+    const size_t n = h->learner.data.n, ni = n_steps * (size_t)batch;
     const EpochStageLayout lay = epoch_stage_layout(n_steps, batch);
     const int rc = ensure_scratch(h, lay.bytes() + 256);
     if (rc != SYN_OK) return rc;
@@ -2950,8 +2902,8 @@ static int stage_epoch(syn_engine* h, const int32_t* perm, size_t n_steps, int b
     HIP_TRY(h, hipMemcpyAsync(st->d_perm, perm, ni * 4, hipMemcpyHostToDevice, h->stream));
     // one gather for the whole epoch (the sampler's index_select), so a step reads its batch from consecutive addresses
     // instead of chasing perm -> sample inside the latency-bound step kernel
-    const TrainSource data = train_sections(h->learner.d_train_data, n);
-    const TrainSections g = st->batches;
+    const PositionColumns data = columns_at(h->learner.data.d, n, false);
+    const PositionColumns g = st->batches;
     hipLaunchKernelGGL(train_gather_kernel, dim3((unsigned)((ni * 16 + 255) / 256)), dim3(256), 0, h->stream, st->d_perm, (int)ni, data.my,
                        data.op, data.pi, data.v, g.my, g.op, g.pi, g.v);
     HIP_TRY(h, hipGetLastError());
@@ -3152,8 +3104,7 @@ static int epoch_queued(syn_engine* h, const EpochStage& st, size_t n_steps, int
     auto& L = h->learner;
     for (size_t s = 0; s < n_steps; s++) {
         const size_t o = s * (size_t)batch;
-        const TrainSource b = {st.batches.my + o, st.batches.op + o, st.batches.pi + o * 9, st.batches.v + o * 3};
-        int rc = launch_grads(h, h->stream, b, batch, L.d_tgrad, st.d_losses + 2 * s);
+        int rc = launch_grads(h, h->stream, columns_from(st.batches, o), batch, L.d_tgrad, st.d_losses + 2 * s);
         if (rc != SYN_OK) return rc;
         rc = launch_adam(h, h->stream, L.d_tgrad, lr, 1.0f);
         if (rc != SYN_OK) return rc;
@@ -3240,7 +3191,7 @@ int syn_train_epochs_sampled(syn_engine* h, const syn_sampler_config* cfg, int n
     if (n_epochs < 0 || batch < 1) return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: n_epochs = %d, batch = %d", n_epochs, batch);
     if ((uint64_t)cfg->first_epoch + (uint64_t)n_epochs > (1ull << 32))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_train_epochs_sampled: epochs %u + %d run past 2^32", cfg->first_epoch, n_epochs);
-    const size_t n = h->learner.train_data_n;
+    const size_t n = h->learner.data.n;
     if (n == 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "call syn_train_set_data first");
     const size_t n_steps = n / (size_t)batch, ni = n_steps * (size_t)batch;
     if (n_epochs == 0 || n_steps == 0) return SYN_OK;
@@ -3259,7 +3210,7 @@ int syn_train_epochs_sampled(syn_engine* h, const syn_sampler_config* cfg, int n
     EpochStage st = epoch_stage_at(h->d_scratch, lay, ni);
     const SamplerBuffers B = sampler_buffers_at(static_cast<unsigned char*>(h->d_scratch) + o_sort, n, tmp_bytes);
     st.d_perm = B.i_out;
-    const TrainSource data = train_sections(h->learner.d_train_data, n);
+    const PositionColumns data = columns_at(h->learner.data.d, n, false);
     for (int e = 0; e < n_epochs; e++) {
         rc = enqueue_sampler(h, B, cfg->key, cfg->first_epoch + (uint32_t)e, n);
         if (rc != SYN_OK) return rc;
@@ -3353,18 +3304,17 @@ int syn_trainer_publish_weights(syn_engine* h) {
 
 // ------------------------------------------------------------------------------------------------ deduplicate
 // The device core of ReplayBuffer::deduplicate (data.rs:196-235): n positions at device pointers -> the unique states in ascending
-// (my_bb, op_bb) order, targets summed in buffer order. `work` is the caller's scratch of dedup_work_bytes(n) bytes; the outputs
-// point into it. Stream-ordered on h->stream with ONE synchronise in the middle (the number of unique states sizes the reduce's grid).
+// (my_bb, op_bb) order, targets summed in buffer order. `work` is the caller's scratch of dedup_layout(n, tmp, mirror).total bytes with
+// tmp from dedup_tmp_bytes; the outputs point into it. Stream-ordered on h->stream with ONE synchronise in the middle (the number of
+// unique states sizes the reduce's grid).
 struct DedupOut {
-    unsigned long long* my = nullptr;
-    unsigned long long* op = nullptr;
-    float* pi = nullptr;
-    float* v = nullptr;
+    PositionColumns rows{};
     unsigned* num = nullptr;
     int m = 0;       // unique (with mirror: canonical) states, rows [0, m)
     int total = 0;   // rows in all: m, with mirror m + the mirror images of the classes that are not self-symmetric
 };
-static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* total, bool mirror = false) {
+// hipcub's temporary storage for the core's sorts and scans over n positions
+static int dedup_tmp_bytes(syn_engine* h, size_t n, bool mirror, size_t* tmp_bytes) {
     const int ni = (int)n;
     size_t tmp_sort = 0, tmp_scan = 0;
     HIP_TRY(h, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const unsigned long long*)nullptr,
@@ -3373,35 +3323,41 @@ static int dedup_work_bytes(syn_engine* h, size_t n, size_t* tmp_bytes, size_t* 
     HIP_TRY(h, hipcub::DeviceScan::InclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni,
                                                 h->stream));
     *tmp_bytes = tmp_sort > tmp_scan ? tmp_sort : tmp_scan;
-    // sort keys/values (double buffers) | heads | scan | seg_start | outputs | cub temp
-    *total = 2 * align256(n * 8) + 2 * align256(n * 4) + 3 * align256(n * 4) + 2 * align256(n * 8) + align256(n * 36) +
-             align256(n * 12) + align256(n * 4) + align256(*tmp_bytes);
     if (mirror) {
-        // the symmetric form (replay_kernels.cuh): outputs of 2n rows instead of n | canonical keys | flip | expand flags | their scan
         size_t tmp_excl = 0;
         HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_excl, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
         if (tmp_excl > *tmp_bytes) *tmp_bytes = tmp_excl;
-        const size_t r = 2 * n;
-        *total = 2 * align256(n * 8) + 2 * align256(n * 4) + 3 * align256(n * 4) + 2 * align256(r * 8) + align256(r * 36) +
-                 align256(r * 12) + align256(r * 4) + align256(*tmp_bytes) + 2 * align256(n * 8) + 3 * align256(n * 4);
     }
     return SYN_OK;
+}
+// The number of set words among n 0/1 flags whose exclusive scan is in `ranks`: the last rank and the last flag to the host, ONE
+// synchronise. A further device word (`d_also`) rides along in the same synchronise.
+static int read_flag_count(syn_engine* h, const unsigned* flags, const unsigned* ranks, int n, size_t* count, const unsigned* d_also = nullptr,
+                           unsigned* also = nullptr) {
+    unsigned last[2] = {0, 0};
+    HIP_TRY(h, hipMemcpyAsync(&last[0], ranks + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(&last[1], flags + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    if (d_also) HIP_TRY(h, hipMemcpyAsync(also, d_also, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *count = (size_t)last[0] + last[1];
+    return SYN_OK;
+}
+// the scan as well: flags -> ranks with hipcub's temporary storage at `tmp`, then the count
+static int count_flags(syn_engine* h, void* tmp, size_t tmp_bytes, const unsigned* flags, unsigned* ranks, int n, size_t* count) {
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, flags, ranks, n, h->stream));
+    return read_flag_count(h, flags, ranks, n, count);
 }
 static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsigned long long* d_my, const unsigned long long* d_op,
                              const float* d_pi, const float* d_v, size_t n, DedupOut* out, bool mirror = false) {
     const int ni = (int)n;
-    const size_t rows = mirror ? 2 * n : n;   // (dedup_work_bytes' layout)
-    Carve c;
-    size_t o_k0 = c.take(n * 8), o_k1 = c.take(n * 8), o_i0 = c.take(n * 4), o_i1 = c.take(n * 4);
-    size_t o_head = c.take(n * 4), o_scan = c.take(n * 4), o_start = c.take(n * 4);
-    size_t o_omy = c.take(rows * 8), o_oop = c.take(rows * 8), o_opi = c.take(rows * 36), o_ov = c.take(rows * 12), o_on = c.take(rows * 4);
-    size_t o_tmp = c.take(tmp);
-    size_t o_cmy = 0, o_cop = 0, o_flip = 0, o_exp = 0, o_dst = 0;
-    if (mirror) { o_cmy = c.take(n * 8); o_cop = c.take(n * 8); o_flip = c.take(n * 4); o_exp = c.take(n * 4); o_dst = c.take(n * 4); }
+    const DedupLayout lay = dedup_layout(n, tmp, mirror);
+    const size_t rows = lay.rows;
+    const size_t o_k0 = lay.k0, o_k1 = lay.k1, o_i0 = lay.i0, o_i1 = lay.i1, o_head = lay.head, o_scan = lay.scan, o_start = lay.start;
+    const size_t o_on = lay.out_num, o_tmp = lay.tmp, o_cmy = lay.c_my, o_cop = lay.c_op, o_flip = lay.flip, o_exp = lay.expand, o_dst = lay.dst;
     char* base = work;
+    const PositionColumns O = columns_in(base, lay.out);
     auto P8 = [&](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
     auto P4 = [&](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
-    auto PF = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
     const int blocks = (ni + 255) / 256;
     const unsigned long long* in_my = d_my;
     const unsigned long long* in_op = d_op;
@@ -3436,31 +3392,23 @@ static int dedup_device_core(syn_engine* h, char* work, size_t tmp, const unsign
     int total = m;
     if (!mirror) {
         hipLaunchKernelGGL(dedup_reduce_kernel, dim3((m * 16 + 255) / 256), dim3(256), 0, h->stream, P4(o_i0), P4(o_start),
-                           m, ni, d_my, d_op, d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
+                           m, ni, d_my, d_op, d_pi, d_v, O.my, O.op, O.pi, O.v, P4(o_on));
         HIP_TRY(h, hipGetLastError());
     } else if (m > 0) {
         const dim3 rows16((unsigned)(((size_t)m * 16 + 255) / 256));
         hipLaunchKernelGGL(dedup_reduce_mirror_kernel, rows16, dim3(256), 0, h->stream, P4(o_i0), P4(o_start), m, ni, d_my, d_op,
-                           P4(o_flip), d_pi, d_v, P8(o_omy), P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on), P4(o_exp));
+                           P4(o_flip), d_pi, d_v, O.my, O.op, O.pi, O.v, P4(o_on), P4(o_exp));
         HIP_TRY(h, hipGetLastError());
         // rows [m, m + M): the mirror images of the classes that are not self-symmetric, in class order
-        t1 = tmp;
-        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(base + o_tmp, t1, P4(o_exp), P4(o_dst), m, h->stream));
-        unsigned last[2] = {0, 0};
-        HIP_TRY(h, hipMemcpyAsync(&last[0], P4(o_dst) + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipMemcpyAsync(&last[1], P4(o_exp) + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        const size_t extra = (size_t)last[0] + last[1];
+        size_t extra = 0;
+        if (const int rc = count_flags(h, base + o_tmp, tmp, P4(o_exp), P4(o_dst), m, &extra)) return rc;
         if (extra > (size_t)m) return fail(h, SYN_ERR_HIP, "%zu mirror images for %d canonical states", extra, m);
-        hipLaunchKernelGGL(dedup_expand_mirror_kernel, rows16, dim3(256), 0, h->stream, P4(o_exp), P4(o_dst), m, rows, P8(o_omy),
-                           P8(o_oop), PF(o_opi), PF(o_ov), P4(o_on));
+        hipLaunchKernelGGL(dedup_expand_mirror_kernel, rows16, dim3(256), 0, h->stream, P4(o_exp), P4(o_dst), m, rows, O.my,
+                           O.op, O.pi, O.v, P4(o_on));
         HIP_TRY(h, hipGetLastError());
         total = m + (int)extra;
     }
-    out->my = P8(o_omy);
-    out->op = P8(o_oop);
-    out->pi = PF(o_opi);
-    out->v = PF(o_ov);
+    out->rows = O;
     out->num = P4(o_on);
     out->m = m;
     out->total = total;
@@ -3483,30 +3431,24 @@ static int replay_deduplicate_host(syn_engine* h, const char* who, bool mirror, 
         n > (mirror ? DEDUP_MIRROR_MAX_N : (size_t)0x7FFFFFFFu))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to %s", who);
     // device layout: inputs | the core's work area
-    size_t tmp = 0, work = 0;
-    int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
+    size_t tmp = 0;
+    int rc = dedup_tmp_bytes(h, n, mirror, &tmp);
     if (rc != SYN_OK) return rc;
-    const size_t o_my = 0, o_op = o_my + align256(n * 8), o_pi = o_op + align256(n * 8), o_v = o_pi + align256(n * 36);
-    const size_t o_work = o_v + align256(n * 12);
-    rc = ensure_scratch(h, o_work + work + 256);
+    Carve c;
+    const ColumnOffsets staged = carve_columns(c, n);
+    const size_t o_work = c.at;
+    rc = ensure_scratch(h, o_work + dedup_layout(n, tmp, mirror).total + 256);
     if (rc != SYN_OK) return rc;
     char* base = static_cast<char*>(h->d_scratch);
-    unsigned long long* d_my = reinterpret_cast<unsigned long long*>(base + o_my);
-    unsigned long long* d_op = reinterpret_cast<unsigned long long*>(base + o_op);
-    float* d_pi = reinterpret_cast<float*>(base + o_pi);
-    float* d_v = reinterpret_cast<float*>(base + o_v);
-    HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_pi, pis, n * 36, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_v, vs, n * 12, hipMemcpyHostToDevice, h->stream));
+    const PositionColumns in = columns_in(base, staged);
+    rc = copy_positions(h, in, columns_of(my_bb, op_bb, nullptr, pis, vs), n, hipMemcpyHostToDevice);
+    if (rc != SYN_OK) return rc;
     DedupOut o;
-    rc = dedup_device_core(h, base + o_work, tmp, d_my, d_op, d_pi, d_v, n, &o, mirror);
+    rc = dedup_device_core(h, base + o_work, tmp, in.my, in.op, in.pi, in.v, n, &o, mirror);
     if (rc != SYN_OK) return rc;
     const size_t m = (size_t)o.total;
-    HIP_TRY(h, hipMemcpyAsync(out_my, o.my, m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_op, o.op, m * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_pi, o.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_v, o.v, m * 12, hipMemcpyDeviceToHost, h->stream));
+    rc = copy_positions(h, columns_of(out_my, out_op, nullptr, out_pi, out_v), o.rows, m, hipMemcpyDeviceToHost);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipMemcpyAsync(out_num, o.num, m * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     *out_count = m;
@@ -3541,26 +3483,19 @@ int syn_positions_mirror(syn_engine* h, const uint64_t* my_bb, const uint64_t* o
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_positions_mirror");
     HIP_TRY(h, hipSetDevice(h->device));
     // device layout: my | op | pi | mirrored my | op | pi
-    const size_t s8 = align256(n * 8), s36 = pis ? align256(n * 36) : 0;
-    int rc = ensure_scratch(h, 4 * s8 + 2 * s36 + 256);
+    Carve c;
+    const ColumnOffsets o_in = carve_columns(c, n, pis != nullptr, false), o_out = carve_columns(c, n, pis != nullptr, false);
+    int rc = ensure_scratch(h, c.at + 256);
     if (rc != SYN_OK) return rc;
-    char* base = static_cast<char*>(h->d_scratch);
-    unsigned long long* d_my = reinterpret_cast<unsigned long long*>(base);
-    unsigned long long* d_op = reinterpret_cast<unsigned long long*>(base + s8);
-    float* d_pi = pis ? reinterpret_cast<float*>(base + 2 * s8) : nullptr;
-    unsigned long long* d_omy = reinterpret_cast<unsigned long long*>(base + 2 * s8 + s36);
-    unsigned long long* d_oop = reinterpret_cast<unsigned long long*>(base + 3 * s8 + s36);
-    float* d_opi = pis ? reinterpret_cast<float*>(base + 4 * s8 + s36) : nullptr;
-    HIP_TRY(h, hipMemcpyAsync(d_my, my_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(d_op, op_bb, n * 8, hipMemcpyHostToDevice, h->stream));
-    if (pis) HIP_TRY(h, hipMemcpyAsync(d_pi, pis, n * 36, hipMemcpyHostToDevice, h->stream));
-    const size_t threads = pis ? n * 9 : n;
-    hipLaunchKernelGGL(replay_mirror_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, d_my, d_op, d_pi, (int)n,
-                       d_omy, d_oop, d_opi);
+    const PositionColumns in = columns_in(h->d_scratch, o_in), mirrored = columns_in(h->d_scratch, o_out);
+    rc = copy_positions(h, in, columns_of(my_bb, op_bb, nullptr, pis, nullptr), n, hipMemcpyHostToDevice);
+    if (rc != SYN_OK) return rc;
+    const size_t threads = pis ? n * POS_PI_FLOATS : n;
+    hipLaunchKernelGGL(replay_mirror_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->stream, in.my, in.op, in.pi, (int)n,
+                       mirrored.my, mirrored.op, mirrored.pi);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out_my, d_omy, n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(out_op, d_oop, n * 8, hipMemcpyDeviceToHost, h->stream));
-    if (pis) HIP_TRY(h, hipMemcpyAsync(out_pi, d_opi, n * 36, hipMemcpyDeviceToHost, h->stream));
+    rc = copy_positions(h, columns_of(out_my, out_op, nullptr, out_pi, nullptr), mirrored, n, hipMemcpyDeviceToHost);
+    if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -3568,45 +3503,10 @@ int syn_positions_mirror(syn_engine* h, const uint64_t* my_bb, const uint64_t* o
 // ------------------------------------------------------------------------------------------------ device-resident replay buffer
 // (data.rs:107-235 on the device; kernels in replay_kernels.cuh). Everything is ordered on h->stream; the host waits only where a
 // count has to reach it.
-struct ReplaySections {
-    unsigned long long* my;
-    unsigned long long* op;
-    long long* gid;
-    float* pi;
-    float* v;
-};
-static ReplaySections replay_sections(unsigned char* base, size_t cap) {
-    ReplaySections s;
-    s.my = reinterpret_cast<unsigned long long*>(base);
-    s.op = reinterpret_cast<unsigned long long*>(base + cap * 8);
-    s.gid = reinterpret_cast<long long*>(base + cap * 16);
-    s.pi = reinterpret_cast<float*>(base + cap * 24);
-    s.v = reinterpret_cast<float*>(base + cap * 60);
-    return s;
-}
-static ReplaySections replay_tail(const ReplaySections& s, size_t at) {
-    ReplaySections t;
-    t.my = s.my + at;
-    t.op = s.op + at;
-    t.gid = s.gid + at;
-    t.pi = s.pi + at * 9;
-    t.v = s.v + at * 3;
-    return t;
-}
-// n positions from `src` to `dst` (five block copies of the given kind)
-static int replay_copy(syn_engine* h, const ReplaySections& dst, const ReplaySections& src, size_t n, hipMemcpyKind kind) {
-    if (n == 0) return SYN_OK;
-    if (dst.my && src.my) HIP_TRY(h, hipMemcpyAsync(dst.my, src.my, n * 8, kind, h->stream));
-    if (dst.op && src.op) HIP_TRY(h, hipMemcpyAsync(dst.op, src.op, n * 8, kind, h->stream));
-    if (dst.gid && src.gid) HIP_TRY(h, hipMemcpyAsync(dst.gid, src.gid, n * 8, kind, h->stream));
-    if (dst.pi && src.pi) HIP_TRY(h, hipMemcpyAsync(dst.pi, src.pi, n * 36, kind, h->stream));
-    if (dst.v && src.v) HIP_TRY(h, hipMemcpyAsync(dst.v, src.v, n * 12, kind, h->stream));
-    return SYN_OK;
-}
-
+// The buffer is columns_at(h->d_replay, h->replay_cap, true): my | op | gid | pi | v, 72 bytes a position.
 // The last syn_selfplay_run's positions, compacted to `dst` (room for `room` positions): exclusive sum of plies, the total to the
 // host (one synchronise), then one wave per game. Nothing is written when the total does not fit (SYN_ERR_CAPACITY).
-static int replay_compact_last_selfplay(syn_engine* h, long long first_gid, const ReplaySections& dst, size_t room, size_t* n_out) {
+static int replay_compact_last_selfplay(syn_engine* h, long long first_gid, const PositionColumns& dst, size_t room, size_t* n_out) {
     *n_out = 0;
     if (h->last_selfplay_games < 0)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "no syn_selfplay_run has completed on this engine: there are no positions to compact");
@@ -3614,7 +3514,7 @@ static int replay_compact_last_selfplay(syn_engine* h, long long first_gid, cons
     if (ng == 0) return SYN_OK;
     size_t tmp = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const int*)nullptr, (unsigned*)nullptr, ng, h->stream));
-    const size_t off_bytes = ((size_t)ng * 4 + 255) & ~(size_t)255;
+    const size_t off_bytes = align256((size_t)ng * 4);
     int rc = ensure_scratch(h, off_bytes + tmp + 256);
     if (rc != SYN_OK) return rc;
     unsigned* d_off = static_cast<unsigned*>(h->d_scratch);
@@ -3643,10 +3543,10 @@ int syn_replay_reserve(syn_engine* h, size_t capacity_positions) {
     if (capacity_positions <= h->replay_cap) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     unsigned char* fresh = nullptr;
-    HIP_TRY(h, hipMalloc(&fresh, capacity_positions * 72));
+    HIP_TRY(h, hipMalloc(&fresh, capacity_positions * POS_ROW_GID_BYTES));
     if (h->replay_n) {
-        int rc = replay_copy(h, replay_sections(fresh, capacity_positions), replay_sections(h->d_replay, h->replay_cap), h->replay_n,
-                             hipMemcpyDeviceToDevice);
+        int rc = copy_positions(h, columns_at(fresh, capacity_positions, true), columns_at(h->d_replay, h->replay_cap, true), h->replay_n,
+                                hipMemcpyDeviceToDevice);
         if (rc != SYN_OK) {
             (void)hipFree(fresh);
             return rc;
@@ -3684,13 +3584,7 @@ int syn_selfplay_positions_device(syn_engine* h, int64_t first_gid, uint64_t* d_
     if (capacity && (!d_my || !d_op || !d_gid || !d_pi || !d_v))
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "bad arguments to syn_selfplay_positions_device");
     HIP_TRY(h, hipSetDevice(h->device));
-    ReplaySections dst;
-    dst.my = reinterpret_cast<unsigned long long*>(d_my);
-    dst.op = reinterpret_cast<unsigned long long*>(d_op);
-    dst.gid = reinterpret_cast<long long*>(d_gid);
-    dst.pi = d_pi;
-    dst.v = d_v;
-    int rc = replay_compact_last_selfplay(h, (long long)first_gid, dst, capacity, n_positions);
+    int rc = replay_compact_last_selfplay(h, (long long)first_gid, columns_of(d_my, d_op, d_gid, d_pi, d_v), capacity, n_positions);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));   // the sections belong to the caller, who reads them on a stream of their own
     return SYN_OK;
@@ -3701,7 +3595,7 @@ int syn_replay_append_selfplay(syn_engine* h, int64_t first_gid, size_t* n_appen
     if (n_appended) *n_appended = 0;
     HIP_TRY(h, hipSetDevice(h->device));
     size_t n = 0;
-    int rc = replay_compact_last_selfplay(h, (long long)first_gid, replay_tail(replay_sections(h->d_replay, h->replay_cap), h->replay_n),
+    int rc = replay_compact_last_selfplay(h, (long long)first_gid, columns_from(columns_at(h->d_replay, h->replay_cap, true), h->replay_n),
                                           h->replay_cap - h->replay_n, &n);
     if (rc != SYN_OK) return rc;
     h->replay_n += n;
@@ -3709,13 +3603,13 @@ int syn_replay_append_selfplay(syn_engine* h, int64_t first_gid, size_t* n_appen
     return SYN_OK;
 }
 
-static int replay_append_impl(syn_engine* h, const ReplaySections& src, size_t n, hipMemcpyKind kind) {
+static int replay_append_impl(syn_engine* h, const PositionColumns& src, size_t n, hipMemcpyKind kind) {
     if (n == 0) return SYN_OK;
     if (!src.my || !src.op || !src.gid || !src.pi || !src.v) return fail(h, SYN_ERR_INVALID_ARGUMENT, "a section pointer is NULL");
     if (n > h->replay_cap - h->replay_n)
         return fail(h, SYN_ERR_CAPACITY, "%zu positions do not fit: the replay buffer holds %zu of %zu (syn_replay_reserve)", n,
                     h->replay_n, h->replay_cap);
-    int rc = replay_copy(h, replay_tail(replay_sections(h->d_replay, h->replay_cap), h->replay_n), src, n, kind);
+    int rc = copy_positions(h, columns_from(columns_at(h->d_replay, h->replay_cap, true), h->replay_n), src, n, kind);
     if (rc != SYN_OK) return rc;
     if (kind == hipMemcpyHostToDevice) HIP_TRY(h, hipStreamSynchronize(h->stream));   // pageable host memory: the caller may reuse it
     h->replay_n += n;
@@ -3726,26 +3620,14 @@ int syn_replay_append_device(syn_engine* h, const uint64_t* d_my, const uint64_t
                              const float* d_v, size_t n) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    ReplaySections src;
-    src.my = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d_my));
-    src.op = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(d_op));
-    src.gid = reinterpret_cast<long long*>(const_cast<int64_t*>(d_gid));
-    src.pi = const_cast<float*>(d_pi);
-    src.v = const_cast<float*>(d_v);
-    return replay_append_impl(h, src, n, hipMemcpyDeviceToDevice);
+    return replay_append_impl(h, columns_of(d_my, d_op, d_gid, d_pi, d_v), n, hipMemcpyDeviceToDevice);
 }
 
 int syn_replay_append(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb, const int64_t* gid, const float* pis, const float* vs,
                       size_t n) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    ReplaySections src;
-    src.my = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(my_bb));
-    src.op = reinterpret_cast<unsigned long long*>(const_cast<uint64_t*>(op_bb));
-    src.gid = reinterpret_cast<long long*>(const_cast<int64_t*>(gid));
-    src.pi = const_cast<float*>(pis);
-    src.v = const_cast<float*>(vs);
-    return replay_append_impl(h, src, n, hipMemcpyHostToDevice);
+    return replay_append_impl(h, columns_of(my_bb, op_bb, gid, pis, vs), n, hipMemcpyHostToDevice);
 }
 
 int syn_replay_keep_games_from(syn_engine* h, int64_t min_gid) {
@@ -3756,30 +3638,28 @@ int syn_replay_keep_games_from(syn_engine* h, int64_t min_gid) {
     const int ni = (int)n;
     size_t tmp = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
-    const size_t sec = (n * 4 + 255) & ~(size_t)255;
-    int rc = ensure_scratch(h, 2 * sec + tmp + 256);
+    Carve c;   // keep flags | their ranks | cub temp
+    const size_t o_keep = c.take(n * 4), o_dst = c.take(n * 4), o_tmp = c.at;
+    int rc = ensure_scratch(h, o_tmp + tmp + 256);
     if (rc != SYN_OK) return rc;
     char* sc = static_cast<char*>(h->d_scratch);
-    unsigned* d_keep = reinterpret_cast<unsigned*>(sc);
-    unsigned* d_dst = reinterpret_cast<unsigned*>(sc + sec);
-    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    unsigned* d_keep = reinterpret_cast<unsigned*>(sc + o_keep);
+    unsigned* d_dst = reinterpret_cast<unsigned*>(sc + o_dst);
+    const PositionColumns cur = columns_at(h->d_replay, h->replay_cap, true);
     hipLaunchKernelGGL(replay_keep_flags_kernel, dim3((ni + 255) / 256), dim3(256), 0, h->stream, cur.gid, ni, (long long)min_gid,
                        d_keep);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(sc + 2 * sec, tmp, d_keep, d_dst, ni, h->stream));
-    unsigned last[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(&last[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&last[1], d_keep + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t kept = (size_t)last[0] + last[1];
+    size_t kept = 0;
+    rc = count_flags(h, sc + o_tmp, tmp, d_keep, d_dst, ni, &kept);
+    if (rc != SYN_OK) return rc;
     if (kept == n) return SYN_OK;   // nothing to drop: the buffer stays where it is
     if (kept == 0) {
         h->replay_n = 0;
         return SYN_OK;
     }
     // stable scatter into the second buffer, which then becomes the buffer
-    if (!h->d_replay_alt) HIP_TRY(h, hipMalloc(&h->d_replay_alt, h->replay_cap * 72));
-    const ReplaySections alt = replay_sections(h->d_replay_alt, h->replay_cap);
+    if (!h->d_replay_alt) HIP_TRY(h, hipMalloc(&h->d_replay_alt, h->replay_cap * POS_ROW_GID_BYTES));
+    const PositionColumns alt = columns_at(h->d_replay_alt, h->replay_cap, true);
     auto U = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
     auto W = [](void* p) { return reinterpret_cast<unsigned*>(p); };
     hipLaunchKernelGGL(replay_keep_scatter_kernel, dim3((unsigned)((n * 9 + 255) / 256), 5), dim3(256), 0, h->stream, d_keep, d_dst, ni,
@@ -3799,13 +3679,8 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
     if (h->replay_n > capacity)
         return fail(h, SYN_ERR_CAPACITY, "the replay buffer holds %zu positions, the caller's arrays %zu", h->replay_n, capacity);
     HIP_TRY(h, hipSetDevice(h->device));
-    ReplaySections dst;
-    dst.my = reinterpret_cast<unsigned long long*>(my_bb);
-    dst.op = reinterpret_cast<unsigned long long*>(op_bb);
-    dst.gid = reinterpret_cast<long long*>(gid);
-    dst.pi = pis;
-    dst.v = vs;
-    int rc = replay_copy(h, dst, replay_sections(h->d_replay, h->replay_cap), h->replay_n, hipMemcpyDeviceToHost);
+    int rc = copy_positions(h, columns_of(my_bb, op_bb, gid, pis, vs), columns_at(h->d_replay, h->replay_cap, true), h->replay_n,
+                            hipMemcpyDeviceToHost);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
@@ -3814,23 +3689,55 @@ int syn_replay_read(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, int64_t* gi
 // ------------------------------------------------------------------------------------------------ reanalyse
 // syn_replay_reanalyse (include/synthesis_amd.h "Reanalyse"; kernels in reanalyse_kernels.cuh): the selected rows of the buffer are
 // compacted into job arrays, searched in chunks by the MODE_SEARCH kernels (as run_games drives them: roots and results stay on
-// the device) and rewritten by the write-back kernel. Scratch, each section 256-byte aligned:
-//   [sel n][skip n][dst n][job_my n][job_op n][job_row n][moved n][done n][counts: skipped, moved, done][cub temp][results of one chunk]
-// (the job arrays are sized for every row: the scratch is laid out before the number of selected rows is known)
-struct ReanalyseLayout {
-    size_t sel, skip, dst, job_my, job_op, job_row, moved, done, counts, tmp, results, total;
+// the device) and rewritten by the write-back kernel. The scratch is position_layout.hpp's reanalyse_layout.
+// The selection that syn_replay_reanalyse and syn_replay_select_positions share: the flags kernel over the n stored rows (n >= 1), the
+// exclusive scan of the selected flags, the sum of the skipped ones, and both counts to the host in one synchronise. The job arrays are
+// not filled yet: the caller checks its capacity and launches the compaction.
+struct ReanalyseSelection {
+    unsigned *d_sel, *d_dst, *d_job_row, *d_moved, *d_done, *d_counts;
+    unsigned long long *d_job_my, *d_job_op;
+    void* d_tmp;
+    DevSearchResult* d_res;
+    size_t tmp_sum;        // hipcub's temporary bytes for a DeviceReduce::Sum over n words
+    PositionColumns R;     // the buffer's columns (the ones syn_replay_read reads)
+    dim3 grid_rows;        // one thread per stored row, blocks of 256
+    size_t sel_n;
+    unsigned skipped;
 };
-static ReanalyseLayout reanalyse_layout(size_t n, size_t tmp_bytes, size_t chunk) {
-    ReanalyseLayout L{};
-    Carve c;
-    L.sel = c.take(n * 4); L.skip = c.take(n * 4); L.dst = c.take(n * 4);
-    L.job_my = c.take(n * 8); L.job_op = c.take(n * 8); L.job_row = c.take(n * 4);
-    L.moved = c.take(n * 4); L.done = c.take(n * 4);
-    L.counts = c.take(16);
-    L.tmp = c.take(tmp_bytes);
-    L.results = c.take(chunk * sizeof(DevSearchResult));
-    L.total = c.at;
-    return L;
+static int reanalyse_select(syn_engine* h, const char* who, uint64_t key, uint64_t threshold, int64_t before_gid, size_t chunk_rows,
+                            ReanalyseSelection* S) {
+    const size_t n = h->replay_n;
+    const int ni = (int)n;
+    size_t tmp_scan = 0, tmp_sum = 0;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(nullptr, tmp_sum, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
+    const ReanalyseLayout L = reanalyse_layout(n, std::max(tmp_scan, tmp_sum), chunk_rows);
+    if (const int rc = ensure_scratch(h, L.total)) return rc;
+    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
+    const auto u32_at = [base](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
+    S->d_sel = u32_at(L.sel);
+    unsigned* const d_skip = u32_at(L.skip);
+    S->d_dst = u32_at(L.dst);
+    S->d_job_my = reinterpret_cast<unsigned long long*>(base + L.job_my);
+    S->d_job_op = reinterpret_cast<unsigned long long*>(base + L.job_op);
+    S->d_job_row = u32_at(L.job_row);
+    S->d_moved = u32_at(L.moved);
+    S->d_done = u32_at(L.done);
+    S->d_counts = u32_at(L.counts);
+    S->d_tmp = base + L.tmp;
+    S->d_res = reinterpret_cast<DevSearchResult*>(base + L.results);
+    S->tmp_sum = tmp_sum;
+    S->R = columns_at(h->d_replay, h->replay_cap, true);
+    S->grid_rows = dim3((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(reanalyse_flags_kernel, S->grid_rows, dim3(256), 0, h->stream, S->R.gid, S->R.my, S->R.op, ni,
+                       (unsigned long long)key ^ REANALYSE_TAG, (unsigned long long)threshold, (long long)before_gid, S->d_sel, d_skip);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(S->d_tmp, tmp_scan, S->d_sel, S->d_dst, ni, h->stream));
+    HIP_TRY(h, hipcub::DeviceReduce::Sum(S->d_tmp, tmp_sum, d_skip, S->d_counts, ni, h->stream));
+    S->skipped = 0;
+    if (const int rc = read_flag_count(h, S->d_sel, S->d_dst, ni, &S->sel_n, S->d_counts, &S->skipped)) return rc;
+    if (S->sel_n > n) return fail(h, SYN_ERR_HIP, "%s: %zu rows selected out of %zu", who, S->sel_n, n);
+    return SYN_OK;
 }
 
 int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_reanalyse_config* cfg, syn_reanalyse_stats* out,
@@ -3864,43 +3771,20 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
     const int ni = (int)n;
     const size_t chunk_max = cfg->chunk_roots > 0 ? (size_t)cfg->chunk_roots : std::max((size_t)65536, (size_t)h->slots);
     const size_t chunk_rows = std::min(chunk_max, n);
-    size_t tmp_scan = 0, tmp_sum = 0;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
-    HIP_TRY(h, hipcub::DeviceReduce::Sum(nullptr, tmp_sum, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
-    const size_t tmp_bytes = std::max(tmp_scan, tmp_sum);
-    const ReanalyseLayout L = reanalyse_layout(n, tmp_bytes, chunk_rows);
-    rc = ensure_scratch(h, L.total);
+    ReanalyseSelection S{};
+    rc = reanalyse_select(h, "syn_replay_reanalyse", cfg->key, cfg->threshold, cfg->before_gid, chunk_rows, &S);
     if (rc != SYN_OK) return rc;
-    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
-    const auto u32_at = [base](size_t o) { return reinterpret_cast<unsigned*>(base + o); };
-    const auto u64_at = [base](size_t o) { return reinterpret_cast<unsigned long long*>(base + o); };
-    unsigned* const d_sel = u32_at(L.sel);
-    unsigned* const d_skip = u32_at(L.skip);
-    unsigned* const d_dst = u32_at(L.dst);
-    unsigned long long* const d_job_my = u64_at(L.job_my);
-    unsigned long long* const d_job_op = u64_at(L.job_op);
-    unsigned* const d_job_row = u32_at(L.job_row);
-    unsigned* const d_moved = u32_at(L.moved);
-    unsigned* const d_done = u32_at(L.done);
-    unsigned* const d_counts = u32_at(L.counts);
-    void* const d_tmp = base + L.tmp;
-    DevSearchResult* const d_res = reinterpret_cast<DevSearchResult*>(base + L.results);
-    const ReplaySections R = replay_sections(h->d_replay, h->replay_cap);   // the sections syn_replay_read reads
-    const dim3 block(256), grid_rows((unsigned)((n + 255) / 256));
-    int launches = 0;
-    hipLaunchKernelGGL(reanalyse_flags_kernel, grid_rows, block, 0, h->stream, R.gid, R.my, R.op, ni, (unsigned long long)cfg->key ^ REANALYSE_TAG,
-                       (unsigned long long)cfg->threshold, (long long)cfg->before_gid, d_sel, d_skip);
-    HIP_TRY(h, hipGetLastError());
-    launches++;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_scan, d_sel, d_dst, ni, h->stream));
-    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_skip, d_counts, ni, h->stream));
-    unsigned head[3] = {0, 0, 0};   // dst[n-1], sel[n-1], skipped
-    HIP_TRY(h, hipMemcpyAsync(&head[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&head[1], d_sel + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&head[2], d_counts, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t sel_n = (size_t)head[0] + head[1];
-    if (sel_n > n) return fail(h, SYN_ERR_HIP, "syn_replay_reanalyse: %zu rows selected out of %zu", sel_n, n);
+    const size_t sel_n = S.sel_n;
+    size_t tmp_sum = S.tmp_sum;
+    unsigned* const d_job_row = S.d_job_row;
+    unsigned* const d_moved = S.d_moved;
+    unsigned* const d_done = S.d_done;
+    unsigned* const d_counts = S.d_counts;
+    void* const d_tmp = S.d_tmp;
+    DevSearchResult* const d_res = S.d_res;
+    const PositionColumns R = S.R;
+    const dim3 block(256), grid_rows = S.grid_rows;
+    int launches = 1;   // the flags kernel
     if (selected_rows && sel_n > capacity)
         return fail(h, SYN_ERR_CAPACITY, "syn_replay_reanalyse: %zu rows are selected, selected_rows has room for %zu", sel_n, capacity);
     h->last_kernel_ms = 0.0f;
@@ -3908,12 +3792,12 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
     h->last_cache_hits = h->last_cache_misses = 0;
     if (out) {
         out->rows = n;
-        out->skipped = head[2];
+        out->skipped = S.skipped;
         out->launches = (uint32_t)launches;
     }
     if (sel_n == 0) return SYN_OK;
-    hipLaunchKernelGGL(reanalyse_compact_kernel, grid_rows, block, 0, h->stream, d_sel, d_dst, ni, (unsigned)n, R.my, R.op, d_job_my, d_job_op,
-                       d_job_row);
+    hipLaunchKernelGGL(reanalyse_compact_kernel, grid_rows, block, 0, h->stream, S.d_sel, S.d_dst, ni, (unsigned)n, R.my, R.op, S.d_job_my,
+                       S.d_job_op, d_job_row);
     HIP_TRY(h, hipGetLastError());
     launches++;
     HIP_TRY(h, hipMemsetAsync(d_moved, 0, sel_n * 4, h->stream));
@@ -3947,8 +3831,8 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
         HIP_TRY(h, hipMemsetAsync(d_res, 0, (size_t)jobs * sizeof(DevSearchResult), h->stream));
         EngineParams Q = P;
         Q.n_jobs = jobs;
-        Q.in_my = d_job_my + c0;
-        Q.in_op = d_job_op + c0;
+        Q.in_my = S.d_job_my + c0;
+        Q.in_op = S.d_job_op + c0;
         Q.base_seed = cfg->stream_base + (unsigned long long)c0;
         HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
         if (const int lrc = launch_engine(h, Q, jobs, MODE_SEARCH, false, false)) return lrc;
@@ -3997,9 +3881,8 @@ int syn_replay_reanalyse(syn_engine* h, const syn_mcts_config* mcts, const syn_r
     return SYN_OK;
 }
 
-// syn_replay_select_positions (include/synthesis_amd.h "Recorded games"): syn_replay_reanalyse's selection alone — the same flags
-// kernel, scan and compaction on the same scratch layout — and a download of the selected positions, 16 bytes each. The buffer is read,
-// never written.
+// syn_replay_select_positions (include/synthesis_amd.h "Recorded games"): syn_replay_reanalyse's selection alone (reanalyse_select and
+// the compaction) and a download of the selected positions, 16 bytes each. The buffer is read, never written.
 int syn_replay_select_positions(syn_engine* h, uint64_t key, uint64_t threshold, int64_t before_gid, uint64_t* my_bb, uint64_t* op_bb,
                                 size_t capacity, size_t* n_selected, size_t* n_skipped) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
@@ -4014,45 +3897,19 @@ int syn_replay_select_positions(syn_engine* h, uint64_t key, uint64_t threshold,
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "syn_replay_select_positions: no replay buffer is reserved (syn_replay_reserve)");
     const size_t n = h->replay_n;
     if (n == 0 || threshold == 0) return SYN_OK;
-    const int ni = (int)n;
-    size_t tmp_scan = 0, tmp_sum = 0;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
-    HIP_TRY(h, hipcub::DeviceReduce::Sum(nullptr, tmp_sum, (const unsigned*)nullptr, (unsigned*)nullptr, ni, h->stream));
-    const ReanalyseLayout L = reanalyse_layout(n, std::max(tmp_scan, tmp_sum), 0);
-    if (const int rc = ensure_scratch(h, L.total)) return rc;
-    unsigned char* const base = static_cast<unsigned char*>(h->d_scratch);
-    unsigned* const d_sel = reinterpret_cast<unsigned*>(base + L.sel);
-    unsigned* const d_skip = reinterpret_cast<unsigned*>(base + L.skip);
-    unsigned* const d_dst = reinterpret_cast<unsigned*>(base + L.dst);
-    unsigned long long* const d_job_my = reinterpret_cast<unsigned long long*>(base + L.job_my);
-    unsigned long long* const d_job_op = reinterpret_cast<unsigned long long*>(base + L.job_op);
-    unsigned* const d_job_row = reinterpret_cast<unsigned*>(base + L.job_row);
-    unsigned* const d_counts = reinterpret_cast<unsigned*>(base + L.counts);
-    void* const d_tmp = base + L.tmp;
-    const ReplaySections R = replay_sections(h->d_replay, h->replay_cap);
-    const dim3 block(256), grid_rows((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(reanalyse_flags_kernel, grid_rows, block, 0, h->stream, R.gid, R.my, R.op, ni, (unsigned long long)key ^ REANALYSE_TAG,
-                       (unsigned long long)threshold, (long long)before_gid, d_sel, d_skip);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(d_tmp, tmp_scan, d_sel, d_dst, ni, h->stream));
-    HIP_TRY(h, hipcub::DeviceReduce::Sum(d_tmp, tmp_sum, d_skip, d_counts, ni, h->stream));
-    unsigned head[3] = {0, 0, 0};   // dst[n-1], sel[n-1], skipped
-    HIP_TRY(h, hipMemcpyAsync(&head[0], d_dst + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&head[1], d_sel + (ni - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&head[2], d_counts, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t sel_n = (size_t)head[0] + head[1];
-    if (sel_n > n) return fail(h, SYN_ERR_HIP, "syn_replay_select_positions: %zu rows selected out of %zu", sel_n, n);
+    ReanalyseSelection S{};
+    if (const int rc = reanalyse_select(h, "syn_replay_select_positions", key, threshold, before_gid, 0, &S)) return rc;
+    const size_t sel_n = S.sel_n;
     *n_selected = sel_n;
-    if (n_skipped) *n_skipped = head[2];
+    if (n_skipped) *n_skipped = S.skipped;
     if (sel_n > capacity)
         return fail(h, SYN_ERR_CAPACITY, "syn_replay_select_positions: %zu rows are selected, the arrays have room for %zu", sel_n, capacity);
     if (sel_n == 0) return SYN_OK;
-    hipLaunchKernelGGL(reanalyse_compact_kernel, grid_rows, block, 0, h->stream, d_sel, d_dst, ni, (unsigned)n, R.my, R.op, d_job_my, d_job_op,
-                       d_job_row);
+    hipLaunchKernelGGL(reanalyse_compact_kernel, S.grid_rows, dim3(256), 0, h->stream, S.d_sel, S.d_dst, (int)n, (unsigned)n, S.R.my, S.R.op,
+                       S.d_job_my, S.d_job_op, S.d_job_row);
     HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(my_bb, d_job_my, sel_n * 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(op_bb, d_job_op, sel_n * 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(my_bb, S.d_job_my, sel_n * POS_BOARD_BYTES, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(op_bb, S.d_job_op, sel_n * POS_BOARD_BYTES, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -4070,11 +3927,11 @@ static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_cano
     size_t tmp_scan = 0;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_scan, (const unsigned*)nullptr, (unsigned*)nullptr, (int)rows_max, h->stream));
     Carve c;
-    const size_t o_part = c.take(n * 64), o_flag = c.take(rows_max * 4), o_rank = c.take(rows_max * 4), o_tmp = c.take(tmp_scan);
+    const size_t o_part = c.take(n * POS_ROW_BYTES), o_flag = c.take(rows_max * 4), o_rank = c.take(rows_max * 4), o_tmp = c.take(tmp_scan);
     const size_t o_work = c.at;
     int rc = ensure_scratch(h, o_work + 4096);
     if (rc != SYN_OK) return rc;
-    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    const PositionColumns cur = columns_at(h->d_replay, h->replay_cap, true);
     auto U = [](const void* p) { return reinterpret_cast<const unsigned*>(p); };
     auto W = [](void* p) { return reinterpret_cast<unsigned*>(p); };
     // ---- the split by game: flags and their ranks (enqueued; run again if the scratch buffer has to grow for the work area)
@@ -4091,19 +3948,19 @@ static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_cano
     };
     rc = flags_and_ranks();
     if (rc != SYN_OK) return rc;
-    unsigned last[2] = {0, 0};
-    HIP_TRY(h, hipMemcpyAsync(&last[0], static_cast<char*>(h->d_scratch) + o_rank + (size_t)(ni - 1) * 4, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&last[1], static_cast<char*>(h->d_scratch) + o_flag + (size_t)(ni - 1) * 4, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t n_held = (size_t)last[0] + last[1];
+    size_t n_held = 0;
+    rc = read_flag_count(h, reinterpret_cast<unsigned*>(static_cast<char*>(h->d_scratch) + o_flag),
+                         reinterpret_cast<unsigned*>(static_cast<char*>(h->d_scratch) + o_rank), ni, &n_held);
+    if (rc != SYN_OK) return rc;
     if (n_held > n) return fail(h, SYN_ERR_HIP, "internal: %zu of %zu positions held out", n_held, n);
     const size_t n_train = n - n_held;
     if (n_train == 0)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "the holdout threshold holds out every game of the buffer: the learner would have no data set");
-    size_t tmp_t = 0, work_t = 0, tmp_h = 0, work_h = 0;
-    rc = dedup_work_bytes(h, n_train, &tmp_t, &work_t, mirror);
-    if (rc == SYN_OK && n_held > 0) rc = dedup_work_bytes(h, n_held, &tmp_h, &work_h, mirror);
+    size_t tmp_t = 0, tmp_h = 0;
+    rc = dedup_tmp_bytes(h, n_train, mirror, &tmp_t);
+    if (rc == SYN_OK && n_held > 0) rc = dedup_tmp_bytes(h, n_held, mirror, &tmp_h);
     if (rc != SYN_OK) return rc;
+    const size_t work_t = dedup_layout(n_train, tmp_t, mirror).total, work_h = n_held > 0 ? dedup_layout(n_held, tmp_h, mirror).total : 0;
     const size_t need = o_work + (work_t > work_h ? work_t : work_h) + 4096;
     if (need > h->scratch_bytes) {
         rc = ensure_scratch(h, need);
@@ -4113,7 +3970,7 @@ static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_cano
     char* sc = static_cast<char*>(h->d_scratch);
     unsigned* d_flag = reinterpret_cast<unsigned*>(sc + o_flag);
     unsigned* d_rank = reinterpret_cast<unsigned*>(sc + o_rank);
-    const TrainSections part = train_sections(sc + o_part, n);
+    const PositionColumns part = columns_at(sc + o_part, n, false);
     hipLaunchKernelGGL(replay_partition_scatter_kernel, dim3((unsigned)((n * 9 + 255) / 256), 4), dim3(256), 0, h->stream, d_flag, d_rank, ni,
                        (unsigned)n_train, U(cur.my), U(cur.op), U(cur.pi), U(cur.v), W(part.my), W(part.op), W(part.pi), W(part.v));
     HIP_TRY(h, hipGetLastError());
@@ -4123,43 +3980,40 @@ static int replay_deduplicate_holdout(syn_engine* h, bool mirror, size_t* n_cano
     if (rc != SYN_OK) return rc;
     const size_t m = (size_t)o.total, m_canonical = (size_t)o.m;
     if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n_train);
-    rc = ensure_train_data(h, m, m + m / 4);
+    rc = ensure_position_rows(h, h->learner.data, m, m + m / 4);
     if (rc != SYN_OK) return rc;
-    const TrainSections tr = train_sections(h->learner.d_train_data, m);
-    rc = train_copy(h, tr, TrainSource{o.my, o.op, o.pi, o.v}, m, hipMemcpyDeviceToDevice);
+    const PositionColumns tr = columns_at(h->learner.data.d, m, false);
+    rc = copy_positions(h, tr, o.rows, m, hipMemcpyDeviceToDevice);
     if (rc != SYN_OK) return rc;
-    h->learner.train_data_n = m;
+    h->learner.data.n = m;
     if (n_unique) *n_unique = m;
     if (n_canonical) *n_canonical = m_canonical;
     // ---- the evaluation set: the held-out part, its unseen rows first
-    E.n = E.n_unseen = 0;
+    E.rows.n = E.n_unseen = 0;
     if (n_held == 0) return SYN_OK;
+    const PositionColumns held = columns_from(part, n_train);
     DedupOut e;
-    rc = dedup_device_core(h, sc + o_work, tmp_h, part.my + n_train, part.op + n_train, part.pi + n_train * 9, part.v + n_train * 3, n_held, &e,
-                           mirror);
+    rc = dedup_device_core(h, sc + o_work, tmp_h, held.my, held.op, held.pi, held.v, n_held, &e, mirror);
     if (rc != SYN_OK) return rc;
     const size_t me = (size_t)e.total;
     if (me == 0 || me > rows_max) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu held-out positions reported %zu rows", n_held, me);
-    rc = ensure_eval_data(h, me, me + me / 4);
+    rc = ensure_position_rows(h, E.rows, me, me + me / 4);
     if (rc != SYN_OK) return rc;
     // seen = the state (symmetric: its canonical form) is among the learner's rows [0, m_canonical): sorted ascending by (my, op)
     const int mei = (int)me;
-    hipLaunchKernelGGL(replay_seen_flags_kernel, dim3((mei + 255) / 256), dim3(256), 0, h->stream, e.my, e.op, mei, tr.my, tr.op,
+    hipLaunchKernelGGL(replay_seen_flags_kernel, dim3((mei + 255) / 256), dim3(256), 0, h->stream, e.rows.my, e.rows.op, mei, tr.my, tr.op,
                        (int)m_canonical, mirror ? 1 : 0, d_flag);
     HIP_TRY(h, hipGetLastError());
-    size_t t1 = tmp_scan;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(sc + o_tmp, t1, d_flag, d_rank, mei, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&last[0], d_rank + (mei - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(&last[1], d_flag + (mei - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const size_t n_seen = (size_t)last[0] + last[1];
+    size_t n_seen = 0;
+    rc = count_flags(h, sc + o_tmp, tmp_scan, d_flag, d_rank, mei, &n_seen);
+    if (rc != SYN_OK) return rc;
     if (n_seen > me) return fail(h, SYN_ERR_HIP, "internal: %zu of %zu held-out rows seen", n_seen, me);
-    const TrainSections ev = train_sections(E.d_data, me);
+    const PositionColumns ev = columns_at(E.rows.d, me, false);
     hipLaunchKernelGGL(replay_partition_scatter_kernel, dim3((unsigned)((me * 9 + 255) / 256), 4), dim3(256), 0, h->stream, d_flag, d_rank, mei,
-                       (unsigned)(me - n_seen), U(e.my), U(e.op), U(e.pi), U(e.v), W(ev.my), W(ev.op), W(ev.pi), W(ev.v));
+                       (unsigned)(me - n_seen), U(e.rows.my), U(e.rows.op), U(e.rows.pi), U(e.rows.v), W(ev.my), W(ev.op), W(ev.pi), W(ev.v));
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    E.n = me;
+    E.rows.n = me;
     E.n_unseen = me - n_seen;
     return SYN_OK;
 }
@@ -4175,24 +4029,24 @@ static int replay_deduplicate_to_trainer(syn_engine* h, bool mirror, size_t* n_c
     if (mirror && n > DEDUP_MIRROR_MAX_N)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "the symmetric de-duplication takes at most %zu positions", DEDUP_MIRROR_MAX_N);
     if (h->evalset.holdout_threshold != 0) return replay_deduplicate_holdout(h, mirror, n_canonical, n_unique);
-    size_t tmp = 0, work = 0;
-    int rc = dedup_work_bytes(h, n, &tmp, &work, mirror);
+    size_t tmp = 0;
+    int rc = dedup_tmp_bytes(h, n, mirror, &tmp);
     if (rc != SYN_OK) return rc;
-    rc = ensure_scratch(h, work + 256);
+    rc = ensure_scratch(h, dedup_layout(n, tmp, mirror).total + 256);
     if (rc != SYN_OK) return rc;
-    const ReplaySections cur = replay_sections(h->d_replay, h->replay_cap);
+    const PositionColumns cur = columns_at(h->d_replay, h->replay_cap, true);
     DedupOut o;
     rc = dedup_device_core(h, static_cast<char*>(h->d_scratch), tmp, cur.my, cur.op, cur.pi, cur.v, n, &o, mirror);
     if (rc != SYN_OK) return rc;
     const size_t m = (size_t)o.total;   // (with mirror: the canonical rows and their mirror images, all of them the learner's)
     if (m == 0) return fail(h, SYN_ERR_HIP, "the de-duplication of %zu positions reported no unique state", n);
     // the unique set becomes the learner's data set (the state syn_train_set_data leaves): syn_train_epoch stages in d_scratch too,
-    // so it moves to d_train_data before this call returns
-    rc = ensure_train_data(h, m, m + m / 4);   // (the unique count drifts from iteration to iteration: do not reallocate for every rise)
+    // so it moves to the learner's own buffer before this call returns
+    rc = ensure_position_rows(h, h->learner.data, m, m + m / 4);   // (the unique count drifts from iteration to iteration: do not reallocate for every rise)
     if (rc != SYN_OK) return rc;
-    rc = train_copy(h, train_sections(h->learner.d_train_data, m), TrainSource{o.my, o.op, o.pi, o.v}, m, hipMemcpyDeviceToDevice);
+    rc = copy_positions(h, columns_at(h->learner.data.d, m, false), o.rows, m, hipMemcpyDeviceToDevice);
     if (rc != SYN_OK) return rc;
-    h->learner.train_data_n = m;
+    h->learner.data.n = m;
     if (n_unique) *n_unique = m;
     if (n_canonical) *n_canonical = (size_t)o.m;
     return SYN_OK;
@@ -4223,16 +4077,14 @@ int syn_train_get_data(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* t
                        size_t* n) {
     const int rc = learner_check(h);
     if (rc != SYN_OK) return rc;
-    const size_t m = h->learner.train_data_n;
+    const size_t m = h->learner.data.n;
     if (n) *n = m;
     if (m > capacity) return fail(h, SYN_ERR_CAPACITY, "the learner's data set has %zu states, the caller's arrays %zu", m, capacity);
     if (m == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const TrainSections data = train_sections(h->learner.d_train_data, m);
-    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, data.my, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, data.op, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, data.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
-    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, data.v, m * 12, hipMemcpyDeviceToHost, h->stream));
+    if (const int crc = copy_positions(h, columns_of(my_bb, op_bb, nullptr, target_pi, target_v), columns_at(h->learner.data.d, m, false), m,
+                                       hipMemcpyDeviceToHost))
+        return crc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -4249,39 +4101,38 @@ int syn_dataset_set(syn_engine* h, const uint64_t* my_bb, const uint64_t* op_bb,
     HIP_TRY(h, hipSetDevice(h->device));
     auto& E = h->evalset;
     if (n == 0) {
-        E.n = E.n_unseen = 0;
+        E.rows.n = E.n_unseen = 0;
         return SYN_OK;
     }
-    int rc = ensure_eval_data(h, n, n);
+    int rc = ensure_position_rows(h, E.rows, n, n);
+    if (E.rows.n == 0) E.n_unseen = 0;   // (a buffer that had to grow dropped its rows)
     if (rc != SYN_OK) return rc;
-    E.n = E.n_unseen = 0;
-    rc = train_copy(h, train_sections(E.d_data, n), train_source(my_bb, op_bb, target_pi, target_v), n, hipMemcpyHostToDevice);
+    E.rows.n = E.n_unseen = 0;
+    rc = copy_positions(h, columns_at(E.rows.d, n, false), columns_of(my_bb, op_bb, nullptr, target_pi, target_v), n, hipMemcpyHostToDevice);
     if (rc != SYN_OK) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    E.n = E.n_unseen = n;
+    E.rows.n = E.n_unseen = n;
     return SYN_OK;
 }
 
 int syn_dataset_counts(syn_engine* h, size_t* n_eval, size_t* n_unseen) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    if (n_eval) *n_eval = h->evalset.n;
+    if (n_eval) *n_eval = h->evalset.rows.n;
     if (n_unseen) *n_unseen = h->evalset.n_unseen;
     return SYN_OK;
 }
 
 int syn_dataset_get(syn_engine* h, uint64_t* my_bb, uint64_t* op_bb, float* target_pi, float* target_v, size_t capacity, size_t* n) {
     if (!h) return SYN_ERR_INVALID_ARGUMENT;
-    const size_t m = h->evalset.n;
+    const size_t m = h->evalset.rows.n;
     if (n) *n = m;
     if (m > capacity) return fail(h, SYN_ERR_CAPACITY, "the evaluation set has %zu rows, the caller's arrays %zu", m, capacity);
     if (m == 0) return SYN_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const TrainSections data = train_sections(h->evalset.d_data, m);
-    if (my_bb) HIP_TRY(h, hipMemcpyAsync(my_bb, data.my, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (op_bb) HIP_TRY(h, hipMemcpyAsync(op_bb, data.op, m * 8, hipMemcpyDeviceToHost, h->stream));
-    if (target_pi) HIP_TRY(h, hipMemcpyAsync(target_pi, data.pi, m * 36, hipMemcpyDeviceToHost, h->stream));
-    if (target_v) HIP_TRY(h, hipMemcpyAsync(target_v, data.v, m * 12, hipMemcpyDeviceToHost, h->stream));
+    if (const int rc = copy_positions(h, columns_of(my_bb, op_bb, nullptr, target_pi, target_v), columns_at(h->evalset.rows.d, m, false), m,
+                                      hipMemcpyDeviceToHost))
+        return rc;
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return SYN_OK;
 }
@@ -4302,8 +4153,8 @@ int syn_dataset_evaluate_arith(syn_engine* h, int which, size_t first_row, size_
     if (which != SYN_DATASET_TRAIN && which != SYN_DATASET_EVAL) return fail(h, SYN_ERR_INVALID_ARGUMENT, "unknown data set %d", which);
     if (max_workgroups < 0) return fail(h, SYN_ERR_INVALID_ARGUMENT, "max_workgroups is negative (%d); 0 lets the library choose", max_workgroups);
     auto& L = h->learner;
-    const size_t set_n = which == SYN_DATASET_TRAIN ? L.train_data_n : h->evalset.n;
-    void* set_base = which == SYN_DATASET_TRAIN ? L.d_train_data : h->evalset.d_data;
+    const size_t set_n = which == SYN_DATASET_TRAIN ? L.data.n : h->evalset.rows.n;
+    void* set_base = which == SYN_DATASET_TRAIN ? L.data.d : h->evalset.rows.d;
     if (set_n == 0 || !set_base)
         return fail(h, SYN_ERR_INVALID_ARGUMENT, "%s", which == SYN_DATASET_TRAIN ? "the learner has no data set" : "there is no evaluation set");
     if (first_row > set_n || n_rows > set_n - first_row)
@@ -4371,12 +4222,12 @@ int syn_dataset_evaluate_arith(syn_engine* h, int which, size_t first_row, size_
     } else {
         d_w = kind == 0 ? L.d_twimg : L.d_tw;
     }
-    const TrainSections s = train_sections(set_base, set_n);
+    const PositionColumns s = columns_from(columns_at(set_base, set_n, false), first_row);
     DsArgs A;
-    A.my_bb = s.my + first_row;
-    A.op_bb = s.op + first_row;
-    A.tpi = s.pi + first_row * 9;
-    A.tv = s.v + first_row * 3;
+    A.my_bb = s.my;
+    A.op_bb = s.op;
+    A.tpi = s.pi;
+    A.tv = s.v;
     A.n = (long long)n_rows;
     A.n_blocks = (long long)nb;
     A.records = reinterpret_cast<DsBlockRecord*>(sc + o_rec);
@@ -4484,7 +4335,7 @@ int syn_state_digest(syn_engine* h, int what, int max_workgroups, uint64_t* dige
     } else if (what == SYN_DIGEST_REPLAY) {
         const uint64_t n = h->d_replay ? h->replay_n : 0;
         if (n) {
-            const ReplaySections s = replay_sections(h->d_replay, h->replay_cap);
+            const PositionColumns s = columns_at(h->d_replay, h->replay_cap, true);
             add(s.my, 2 * n);
             add(s.op, 2 * n);
             add(s.gid, 2 * n);
@@ -4493,10 +4344,10 @@ int syn_state_digest(syn_engine* h, int what, int max_workgroups, uint64_t* dige
         }
     } else {
         const bool train = what == SYN_DIGEST_TRAIN_DATA;
-        void* base = train ? L.d_train_data : h->evalset.d_data;
-        const uint64_t n = base ? (train ? L.train_data_n : h->evalset.n) : 0;
+        void* base = train ? L.data.d : h->evalset.rows.d;
+        const uint64_t n = base ? (train ? L.data.n : h->evalset.rows.n) : 0;
         if (n) {
-            const TrainSections s = train_sections(base, n);
+            const PositionColumns s = columns_at(base, n, false);
             add(s.my, 2 * n);
             add(s.op, 2 * n);
             add(s.pi, 9 * n);
